@@ -12,10 +12,11 @@ compaction, results left in HBM.  Queries are independent, so ranks share nothin
 10 000 queries per GPU == configs[2] at N = 8); after the timed region the results travel once, device to device:
 records to every rank (all_gather), alignment pairs to rank 0 (gather) — poasta_amd/dist.py, RCCL over xGMI.
 
-Rank 0 prints ONE JSON line (task contract) with
+Rank 0 prints ONE JSON line (task contract) with the headline (`value`, `ms_per_step` of the timed steps) and
   roofline      the forward kernel against the ceiling that binds it (VALU issue, measured by
                 profiles/microbench/valu_issue.hip), with the HBM figures beside it: `alg_*` = SURVEY.md §8(d)'s fixed
-                12 B/cell accounting, `traffic*` = PMC bytes;
+                12 B/cell accounting, `traffic*` = PMC bytes (from the timed steps' own kernel events: no run of its own).
+With --full the line also holds the extras below, each measured in runs of its own after the timed steps:
   like_for_like the same step with u32 score planes (12 real bytes per cell: where §8(d)'s accounting is physical);
   value_incl_d2h  the step including the device->host copy of scores, flags and pairs (SURVEY.md §8(d)'s wall time);
   steps_in_flight the same step with three resident batches round robin on three HIP streams (traceback under the next forward pass);
@@ -23,6 +24,8 @@ Rank 0 prints ONE JSON line (task contract) with
                 could not certify — over the whole batch: throughput and how many alignments equal the restated
                 reference's;
   cpu_baseline  (N = 1) the restated reference CPU path on the host's cores, all physical cores and one thread.
+
+--dump-outputs DIR writes what the last timed step computed, as float64 .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -38,6 +41,7 @@ if ROOT not in sys.path:
 ALG_BYTES_PER_CELL = 12.0      # three u32 planes written once per cell
 HBM_PEAK_GBPS = 8000.0         # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
 N_SIMD = 1024                  # 256 CUs x 4
+RUNS_PER_STATS = 256           # poa_batch_run keeps the HIP events of at most 256 runs: poa_batch_stats / fetch must collect them
 
 
 def _free_port():
@@ -93,6 +97,16 @@ def valu_ceiling():
     return None, None
 
 
+def _add_stats(acc, s):
+    """Engine stats of two stretches of runs of one batch: the timings and counts of runs add up, the rest describes the batch."""
+    if acc is None:
+        return dict(s)
+    out = dict(s)
+    for k in ("n_runs", "n_forward_launches", "ms_forward", "ms_traceback", "ms_exact", "ms_total"):
+        out[k] = acc[k] + s[k]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -100,20 +114,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--queries", type=int, default=10000, help="queries per GPU")
     ap.add_argument("--length", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extras (like_for_like, value_incl_d2h, steps_in_flight, cpu_baseline, bit_exact, "
+                         "bit_exact_unpadded) after the timed steps; a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of the last timed step to DIR/<name>.npy (float64; a seeded sample of the alignment pairs)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="queries timed on the CPU baseline at all cores (-1 = the whole batch, 0 = skip baseline and bit_exact)")
+                    help="with --full: queries timed on the CPU baseline at all cores (-1 = the whole batch, 0 = skip baseline and bit_exact)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--model", default="affine", choices=["affine", "2piece"],
                     help="2piece: an extra, not the headline — the two-piece affine dense pass (poa_align_batch_2piece, SURVEY.md 8(f) row 3) "
                          "on the configs[1] shape under the CLI's example costs -g 6,24 -e 2,1; one GPU; prints its own JSON line")
-    ap.add_argument("--no-extras", action="store_true", help="skip like_for_like / value_incl_d2h / bit_exact (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the extras of --full (profiling runs)")
     ap.add_argument("--rehearse", action="store_true",
                     help="multi-rank dry run on ONE GPU (or none for the spawn path): every rank uses cuda:0 and the gather runs "
                          "over gloo on CPU tensors (not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1 and args.no_gather:
+        ap.error("--dump-outputs with --gpus > 1 writes the gathered results: drop --no-gather")
+    extras = args.full and not args.no_extras
 
     if args.model == "2piece":
-        return bench_two_piece(args)
+        return bench_two_piece(args, extras)
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
         # no launcher: become one.  Nothing has touched the GPU yet (torch is not even imported).
@@ -178,24 +202,33 @@ def main():
         else:
             torch.cuda.synchronize()
         b.stats()
+        st_ = None
         t_start = time.perf_counter()
-        for _ in range(k):
+        for i in range(k):
+            if i and i % RUNS_PER_STATS == 0:   # (synchronises once per 256 steps)
+                st_ = _add_stats(st_, b.stats())
             b.run(costs, stream, cfg)
         if collective:
             barrier()
         else:
             torch.cuda.synchronize()
         el = time.perf_counter() - t_start
-        st_ = b.stats()  # HIP events recorded on `stream` around every kernel of the timed steps
+        st_ = _add_stats(st_, b.stats())  # HIP events recorded on `stream` around every kernel of the timed steps
         if dist is not None and collective:
             t = torch.tensor([el], dtype=torch.float64, device=torch.device("cpu") if args.rehearse else dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         return el, st_
 
-    for _ in range(args.warmup):
+    for i in range(args.warmup):
+        if i and i % RUNS_PER_STATS == 0:
+            batch.stats()
         batch.run(costs, stream)
     elapsed_max, st = timed(batch, args.steps)
+    if args.dump_outputs and world == 1:
+        r_ = batch.fetch(want_pairs=True)
+        dump_outputs(args.dump_outputs, r_.score, r_.flags, r_.pair_off, r_.pairs, int(np.diff(qoff).max(initial=0)) + n_rows)
+        del r_
 
     # ---- result gather (the path's only exchange step), from the engine's result buffers in HBM ----
     gather_ms = None
@@ -213,15 +246,24 @@ def main():
         gather_ms = (time.perf_counter() - g0) * 1e3
         flagged_total = int((g_flags != 0).sum().item())
         score_sum = int(g_score.sum().item())
+        if args.dump_outputs:   # the longest query of the whole batch bounds the pairs of one query (dump_outputs' sample)
+            t = torch.tensor([int(np.diff(qoff).max(initial=0))], dtype=torch.int64, device=torch.device("cpu") if args.rehearse else dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            max_len = int(t.item())
         if rank == 0:
             assert int(g_np.sum().item()) == int(g_pairs.shape[0])
             pairs_at_root = int(g_pairs.shape[0])
+            if args.dump_outputs:
+                g_off = np.zeros(int(g_np.shape[0]) + 1, np.uint64)
+                g_off[1:] = np.cumsum(g_np.cpu().numpy())
+                dump_outputs(args.dump_outputs, g_score.cpu().numpy(), g_flags.cpu().numpy(), g_off,
+                             g_pairs.cpu().numpy(), max_len + n_rows)
         del g_score, g_flags, g_np, g_pairs
     del d_score, d_flags, d_off, d_pairs
 
     # ---- device -> host copy of one step's results (SURVEY.md §8(d) counts it; `value` does not) ----
     incl_d2h = None
-    if not args.no_extras:
+    if extras:
         batch.fetch(want_pairs=True, pinned=True)   # page-locks the host buffers once (not part of a step)
         barrier()
         t1 = time.perf_counter()
@@ -236,13 +278,11 @@ def main():
         incl_d2h = {"value": round(cells_rank * world / dt / 1e9, 3), "unit": "Gcells/s", "ms_per_step": round(dt * 1e3, 3),
                     "d2h_ms": round(res.stats["ms_d2h"], 3), "d2h_bytes": int(res.pairs.nbytes + res.score.nbytes + res.flags.nbytes + res.pair_off.nbytes),
                     "note": "one step + poa_batch_fetch into page-locked host buffers, single shot"}
-    else:
-        res = batch.fetch(want_pairs=(rank == 0))
 
     # ---- steps in flight: three resident batches on three HIP streams, round robin (rank-local, not part of `value`):
     #      the traceback of a step (latency bound, few issue slots) runs under the forward pass of the next ----
     piped = None
-    if not args.no_extras and not args.rehearse and "POA_PLANES" not in os.environ:
+    if extras and not args.rehearse and "POA_PLANES" not in os.environ:
         try:
             depth = 3
             # (each batch gets what the compact layout needs, not the u32-sized default, so that three fit beside the first)
@@ -251,10 +291,15 @@ def main():
             ps = [torch.cuda.Stream(device=dev) for _ in range(depth)]
             for k in range(2 * depth):
                 pb[k % depth].run(costs, ps[k % depth].cuda_stream)
+            for b_ in pb:
+                b_.stats()
             torch.cuda.synchronize()
             n_p = max(12, args.steps)
             t1 = time.perf_counter()
             for k in range(n_p):
+                if k and k % (RUNS_PER_STATS * depth) == 0:   # (each batch has run 256 times since the last collection)
+                    for b_ in pb:
+                        b_.stats()
                 pb[k % depth].run(costs, ps[k % depth].cuda_stream)
             torch.cuda.synchronize()
             dtp = time.perf_counter() - t1
@@ -275,7 +320,7 @@ def main():
 
     # ---- the same step with u32 planes: 12 real bytes per cell (rank-local, not part of `value`) ----
     like = None
-    if not args.no_extras and not args.rehearse and "POA_PLANES" not in os.environ:   # (a rehearsal's ranks share one GPU: 2 x 123 GB of u32 planes do not fit)
+    if extras and not args.rehearse and "POA_PLANES" not in os.environ:   # (a rehearsal's ranks share one GPU: 2 x 123 GB of u32 planes do not fit)
         os.environ["POA_PLANES"] = "32"
         try:
             b32 = aligner.ResidentBatch(graph, qseq, qoff, device=local_rank)
@@ -373,7 +418,7 @@ def main():
             line["value_incl_d2h"] = incl_d2h
         if piped is not None:
             line["steps_in_flight"] = piped
-        if world == 1 and args.cpu_sample != 0 and not args.no_extras:
+        if world == 1 and args.cpu_sample != 0 and extras:
             n_cpu = len(qs) if args.cpu_sample < 0 else min(args.cpu_sample, len(qs))
             line["cpu_baseline"], A = cpu_baseline(graph, qs[:n_cpu], n_rows)
             line["bit_exact"] = bit_exact(batch, costs, stream, res, A, n_cpu, cells_rank, flagged_total)
@@ -394,6 +439,46 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_QUERY_CAP = 1 << 19          # per-query arrays: 3 x 8 B x 512 Ki = 12 MiB at most
+DUMP_PAIR_BYTES = 48 << 20        # alignment pairs: 48 MiB at most (with the above: < 64 MB in all)
+
+
+def dump_outputs(out_dir, score, flags, pair_off, pairs, max_pairs_per_query):
+    """Writes a step's results, as a caller receives them (poa_batch_fetch: u32 score / flags, u64 pair_off, u32 pairs with
+    0xFFFFFFFF = None), to out_dir as float64 .npy files (exact for every u32 and for these offsets):
+      queries.npy        the query indices the three per-query arrays below hold (all, or a seeded sample above DUMP_QUERY_CAP)
+      score.npy, flags.npy, n_pairs.npy   per query (n_pairs = pair_off[i+1] - pair_off[i])
+      pairs_queries.npy  the query indices whose alignments pairs.npy holds, in order: a seeded sample, sized from the worst case
+                         (max_pairs_per_query = longest query + graph rows) so that it depends on the inputs alone
+      pairs.npy          [sum of their n_pairs, 2] (rpos, qpos) pairs of those queries, concatenated
+    Both samples depend on the inputs alone (number of queries, longest query, graph rows), not on the results: two builds run
+    with the same arguments dump the same entries."""
+    import numpy as np
+    n = len(score)
+    pair_off = np.asarray(pair_off, np.int64)
+
+    def sample(k, seed):
+        if n <= k:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=k, replace=False))
+
+    q = sample(DUMP_QUERY_CAP, 11)
+    qp = sample(max(1, DUMP_PAIR_BYTES // (16 * max(1, max_pairs_per_query))), 12)
+    sel = [np.arange(pair_off[i], pair_off[i + 1]) for i in qp]
+    rows = np.concatenate(sel) if sel else np.zeros(0, np.int64)
+    pairs = np.asarray(pairs).view(np.uint32).reshape(-1, 2)
+    u32 = lambda a: np.asarray(a).astype(np.int64) & 0xFFFFFFFF   # (the gathered records carry the u32 values in signed types)
+    out = {"queries": q, "score": u32(score)[q], "flags": u32(flags)[q],
+           "n_pairs": (pair_off[1:] - pair_off[:-1])[q], "pairs_queries": qp, "pairs": pairs[rows]}
+    out = {k: np.ascontiguousarray(v, np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > 64 * 10**6:
+        raise RuntimeError("dump_outputs: %d bytes exceed the 64 MB bound (a query has more pairs than rows + length)" % total)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def _detach(res):
@@ -519,7 +604,7 @@ def bit_exact(batch, costs, stream, dense_res, A, n_checked, cells_rank, dense_f
     return out
 
 
-def bench_two_piece(args):
+def bench_two_piece(args, extras):
     """Extra: the two-piece affine model's dense pass (forward kernel poa2_forward_kernel + traceback poa2_traceback_kernel) over
     configs[1]'s graph and reads, through the one-shot C entry point (host buffers in, host buffers out; the kernel times are HIP
     events inside it).  roofline: HBM — the five planes M, D1, D2, I1, I2 a traceback of this model reads (20 B/cell as u32, the
@@ -537,6 +622,8 @@ def bench_two_piece(args):
         dt = time.perf_counter() - t0
         if best is None or res.stats["ms_forward"] < best[1]["ms_forward"]:
             best = (dt, res.stats)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res.score, res.flags, res.pair_off, res.pairs, int(np.diff(qoff).max(initial=0)) + int(g.n))
     dt, st = best
     cells, ms_f, ms_t = st["cells"], st["ms_forward"], st["ms_traceback"]
     launches = max(st["n_forward_launches"], 1)
@@ -555,21 +642,22 @@ def bench_two_piece(args):
                          "note": "achieved = 20 B/cell (five u32 planes: the reference's visited cell of this model) x cells / forward time, HIP events inside the "
                                  "call; the engine writes the planes as u16 when the score bound allows (stored_*); PMC traffic: profiles/r03_two_piece/"}}
     # the model's own search replayed (Affine2PieceMinGapCost + pruning: what the CLI runs), on a sample: queries per second and
-    # how far its scores lie above the dense optimum
-    try:
-        k = min(n, 4096)
-        ex = aligner.PoastaAligner(aligner.Affine2PieceMinGapCost(aligner.GapAffine2Piece(4, 2, 6, 1, 24)), mode="exact")
-        t0 = time.perf_counter()
-        rx = ex.align_batch(g, qseq=qseq[:int(qoff[k])], qoff=qoff[:k + 1], want_pairs=False)
-        dtx = time.perf_counter() - t0
-        dn = al.align_batch(g, qseq=qseq[:int(qoff[k])], qoff=qoff[:k + 1], want_pairs=False)
-        line["bit_exact"] = {"mode": "exact (poa_align_batch_2piece_ex: replay of the five-state search, min-gap heuristic, pruning)", "queries": k,
-                             "seconds": round(dtx, 3), "ms_replay": round(rx.stats["ms_exact"], 1), "queries_per_s": round(k / dtx, 1),
-                             "value": round(int(g.n) * float((np.diff(qoff[:k + 1]).astype(np.int64) + 1).sum()) / dtx / 1e9, 4), "unit": "Gcells/s",
-                             "states_visited_mean": round(float(rx.search_counters[:, 1].mean()), 1), "flagged": int((rx.flags != 0).sum()),
-                             "scores_above_dense_optimum": int((rx.score > dn.score).sum()), "scores_below_dense_optimum": int((rx.score < dn.score).sum())}
-    except Exception as exc:   # (extra: never takes the line down)
-        line["bit_exact"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+    # how far its scores lie above the dense optimum (--full)
+    if extras:
+        try:
+            k = min(n, 4096)
+            ex = aligner.PoastaAligner(aligner.Affine2PieceMinGapCost(aligner.GapAffine2Piece(4, 2, 6, 1, 24)), mode="exact")
+            t0 = time.perf_counter()
+            rx = ex.align_batch(g, qseq=qseq[:int(qoff[k])], qoff=qoff[:k + 1], want_pairs=False)
+            dtx = time.perf_counter() - t0
+            dn = al.align_batch(g, qseq=qseq[:int(qoff[k])], qoff=qoff[:k + 1], want_pairs=False)
+            line["bit_exact"] = {"mode": "exact (poa_align_batch_2piece_ex: replay of the five-state search, min-gap heuristic, pruning)", "queries": k,
+                                 "seconds": round(dtx, 3), "ms_replay": round(rx.stats["ms_exact"], 1), "queries_per_s": round(k / dtx, 1),
+                                 "value": round(int(g.n) * float((np.diff(qoff[:k + 1]).astype(np.int64) + 1).sum()) / dtx / 1e9, 4), "unit": "Gcells/s",
+                                 "states_visited_mean": round(float(rx.search_counters[:, 1].mean()), 1), "flagged": int((rx.flags != 0).sum()),
+                                 "scores_above_dense_optimum": int((rx.score > dn.score).sum()), "scores_below_dense_optimum": int((rx.score < dn.score).sum())}
+        except Exception as exc:   # (extra: never takes the line down)
+            line["bit_exact"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
     print(json.dumps(line), flush=True)
 
 

@@ -6,12 +6,12 @@ O=$ROOT/gpurun_out/r03; mkdir -p $O
 cd $ROOT
 timeout -k 10 120 profiles/microbench/valu_issue > $O/valu_issue_r03.json 2> $O/valu_issue.err; echo "microbench rc=$?"
 timeout -k 10 300 python scripts/sequential_poa_latency.py > $O/sequential_poa_latency.json 2> $O/seq.err; echo "seq latency rc=$?"
-timeout -k 10 200 python bench.py --model 2piece --steps 2 --warmup 1 > $O/bench_2piece.json 2> $O/b2.err; echo "bench 2piece rc=$?"
+timeout -k 10 200 python bench.py --model 2piece --full --steps 2 --warmup 1 > $O/bench_2piece.json 2> $O/b2.err; echo "bench 2piece rc=$?"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/tp_trace -- python3 $ROOT/bench.py --model 2piece --steps 1 --warmup 1 > $O/tp_trace.log 2>&1; echo "2piece trace rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/tp_trace -- python3 $ROOT/bench.py --model 2piece --full --steps 1 --warmup 1 > $O/tp_trace.log 2>&1; echo "2piece trace rc=$?"
 for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   N=$(echo $C | tr ' ' '_' | cut -c1-30)
-  rocprofv3 --pmc $C --output-format csv -d $O/tp_pmc_$N -- python3 $ROOT/bench.py --model 2piece --steps 1 --warmup 1 > $O/tp_pmc_$N.log 2>&1; echo "2piece pmc $N rc=$?"
+  rocprofv3 --pmc $C --output-format csv -d $O/tp_pmc_$N -- python3 $ROOT/bench.py --model 2piece --full --steps 1 --warmup 1 > $O/tp_pmc_$N.log 2>&1; echo "2piece pmc $N rc=$?"
 done
 python3 - <<PY
 import csv, glob, json, collections

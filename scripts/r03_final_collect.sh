@@ -34,4 +34,4 @@ for tag, pat in (("wave", "wsearch"), ("tp", "poa2_exact")):
         open("$O/%s_kernel_stats.csv" % tag, "w").write(open(f).read())
 PY
 find $O -name "*.csv" -size +1000k -delete; find $O -name "*.db" -delete
-cd $ROOT && timeout -k 10 300 python bench.py > $O/bench_r03_final.json 2> $O/bench.err; echo "bench rc=$?"
+cd $ROOT && timeout -k 10 300 python bench.py --full > $O/bench_r03_final.json 2> $O/bench.err; echo "bench rc=$?"

@@ -315,16 +315,62 @@ def test_mingap_with_pruning_can_be_suboptimal(oracle):
 def test_bench_spawns_its_own_launcher_for_n_gpus():
     """`python bench.py --gpus 2` with no launcher in the environment starts torch.distributed.run itself (as a child, before
     anything touches a GPU) and hands back its exit code.  Here, without a GPU, both ranks must get as far as the engine's
-    "needs a GPU" exit — which proves the spawn, the rendezvous arguments and that rank discovery reads the launcher's env."""
+    "needs a GPU" exit — which proves the spawn, the rendezvous arguments and that rank discovery reads the launcher's env.
+    With a GPU the rehearsal itself runs: both ranks on device 0, the gather over gloo, one JSON line from rank 0."""
+    import json
     import subprocess
     import sys
+    from poasta_amd import _lib
+    # the engine's device count, not torch.cuda.is_available(): once earlier tests have loaded the engine's HIP runtime
+    # into this process, torch's own runtime can report no device although there is one
+    gpu = _lib.lib().poa_device_count() > 0
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "1"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     err = p.stderr.decode(errors="replace")
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is present: the rehearsal itself runs (covered on the GPU box)")
+    if gpu:
+        assert p.returncode == 0, err[-2000:]
+        line = json.loads(p.stdout.decode().strip().splitlines()[-1])
+        assert line["n_gpus"] == 2 and line["steps"] == 1 and line["config"]["gather_ms"] is not None
+        return
     assert p.returncode != 0
     assert err.count("bench.py needs a GPU") >= 1, err[-2000:]
     assert "--nproc-per-node" not in err or "error: unrecognized" not in err
+
+
+def test_bench_dump_outputs_writes_a_seeded_sample(oracle, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the per-query results whole, the pairs of a sample of queries that depends on the number of
+    queries alone, all as float64 (exact for the u32 values, POA_NONE included).  The oracle's dense results stand in for a step's."""
+    import bench
+    poa = W.LinearishPOA(60, 5, 3, seed=1)
+    qseq, qoff = pack_queries(poa.queries(40, length=70, seed=2))
+    D = oracle.OracleGraph.from_csr(poa.graph.as_dict()).dense_batch(qseq, qoff, oracle.Costs(4, 6, 2))
+    off = np.zeros(41, np.uint64)
+    off[1:] = np.cumsum(D["n_pairs"].astype(np.uint64))
+    pairs = np.concatenate([D["pairs"][int(D["pair_off"][i]):int(D["pair_off"][i]) + int(D["n_pairs"][i])] for i in range(40)])
+    assert (pairs == 0xFFFFFFFF).any()
+    monkeypatch.setattr(bench, "DUMP_PAIR_BYTES", 16 * (70 + poa.graph.n) * 10)   # room for the pairs of 10 queries
+    dumps = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), D["score"], D["flags"], off, pairs, 70 + poa.graph.n)
+        dumps.append({f.stem: np.load(f) for f in d.iterdir()})
+    z = dumps[0]
+    assert sorted(z) == ["flags", "n_pairs", "pairs", "pairs_queries", "queries", "score"]
+    assert all(v.dtype == np.float64 for v in z.values())
+    assert all(np.array_equal(z[k], dumps[1][k]) for k in z)
+    assert np.array_equal(z["queries"], np.arange(40)) and np.array_equal(z["score"], D["score"])
+    assert np.array_equal(z["flags"], D["flags"]) and np.array_equal(z["n_pairs"], D["n_pairs"])
+    sel = z["pairs_queries"].astype(np.int64)
+    assert len(sel) == 10 and np.all(np.diff(sel) > 0)
+    want = np.concatenate([pairs[int(off[i]):int(off[i + 1])] for i in sel])
+    assert np.array_equal(z["pairs"], want.astype(np.float64))
+
+
+def test_bench_rejects_zero_steps():
+    """--steps sets the number of timed steps: ms_per_step is undefined without one."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 2 and b"--steps must be >= 1" in p.stderr

@@ -127,3 +127,37 @@ def test_config2_hybrid_full_size_is_the_reference(engine, oracle):
     replayed = sc[:, 3] > 0
     assert int(replayed.sum()) == 9928 and np.array_equal(sc[replayed, :3].astype(np.uint64), A["counters"][replayed])
     rb.close()
+
+
+def _bench(*args):
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--queries", "256", "--length", "300"] + list(args),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+    return json.loads(p.stdout.decode().strip().splitlines()[-1])
+
+
+def test_bench_takes_more_steps_than_the_engine_keeps_events_for(engine, tmp_path):
+    """poa_batch_run keeps the HIP events of at most 256 runs until poa_batch_stats / fetch collects them: bench.py collects
+    them as it goes, so --steps and --warmup are not bounded by it, the timings of every step are counted, and the results
+    of the last step are those of a single one."""
+    line = _bench("--steps", "600", "--warmup", "300", "--dump-outputs", str(tmp_path / "many"))
+    assert line["steps"] == 600 and line["ms_per_step"] > 0
+    assert line["roofline"]["launches_timed"] == 600 * line["config"]["plane_chunks"]
+    one = _bench("--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "one"))
+    assert one["config"]["score_checksum"] == line["config"]["score_checksum"]
+    for f in sorted((tmp_path / "one").iterdir()):
+        assert np.array_equal(np.load(f), np.load(tmp_path / "many" / f.name)), f.name
+
+
+def test_bench_full_takes_more_steps_than_the_engine_keeps_events_for(engine):
+    """--full with more steps than 3 x 256: steps_in_flight round-robins them over three batches, each past 256 runs."""
+    line = _bench("--steps", "800", "--warmup", "1", "--full")
+    assert line["steps"] == 800
+    for k in ("steps_in_flight", "like_for_like", "value_incl_d2h", "cpu_baseline", "bit_exact", "bit_exact_unpadded"):
+        assert k in line and "error" not in line[k], (k, line.get(k))
+    assert line["steps_in_flight"]["steps"] == 800 and line["steps_in_flight"]["results_equal_the_timed_steps"]
