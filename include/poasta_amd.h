@@ -106,7 +106,7 @@ enum {
     POA_TUNE_PACKED,          /* 0: scalar-arithmetic forward kernel */
     POA_TUNE_RELATIVE,        /* 0 / 1: relative encoding off / on */
     POA_TUNE_PX,              /* 0: adjacent-pairs packed kernel instead of pairs-across-quads */
-    POA_TUNE_MF,              /* 0 / 1 / 2: at most that many flag pairs beside the score */
+    POA_TUNE_MF,              /* 0 / 1 / 2: at most that many flag pairs beside the score; 3: one pair, the other derived */
     POA_TUNE_MW,              /* 0: no multi-wave pipeline */
     POA_TUNE_PXMW,            /* 0 / 1: 1024-column multi-wave kernel off / on */
     POA_TUNE_FWD_QUADS,
@@ -291,6 +291,7 @@ int poa_batch_fetch_search_counters(poa_batch_t* b, uint32_t* out);
  * encoding is provably exact for everything the result depends on). */
 #define POA_LAYOUT_U16 1u       /* 2-byte cells (bound <= 65534) */
 #define POA_LAYOUT_COMPACT 2u   /* M plane + 4 flag bits per cell + the D rows that are read back */
+#define POA_LAYOUT_DERIVED_GAPS 8u /* compact cells keep the two Match-state flags only; the traceback derives the gap-state ones */
 #define POA_LAYOUT_RELATIVE 4u  /* cells hold score - e * (shortest-path depth of the row - column): scores beyond u16 */
 int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological

@@ -338,10 +338,10 @@ class ResidentBatch:
         return out
 
     def layout(self):
-        """How the dense pass of the last run stored its planes: subset of {"u16", "compact", "relative"} (empty: u32 planes)."""
+        """How the dense pass of the last run stored its planes: subset of {"u16", "compact", "relative", "derived_gaps"} (empty: u32 planes)."""
         v = C.c_uint32(0)
         _lib.check(_lib.lib().poa_batch_last_layout(self.handle, C.byref(v)))
-        return {name for bit, name in ((1, "u16"), (2, "compact"), (4, "relative")) if v.value & bit}
+        return {name for bit, name in ((1, "u16"), (2, "compact"), (4, "relative"), (8, "derived_gaps")) if v.value & bit}
 
     def device_results(self):
         ptrs = [C.c_void_p() for _ in range(4)]

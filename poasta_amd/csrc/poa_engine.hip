@@ -203,7 +203,7 @@ struct poa_batch {
     DevBuf<uint32_t> d_row_depth, d_pred_k;   // depth potential of the relative u16 encoding (FlatGraph::row_depth / pred_k)
     DevBuf<uint32_t> d_dslot, d_pred_dslot;   // compact layout: slots of the kept D rows (FlatGraph::d_slot / pred_dslot)
     bool relative = false;                    // last run stored scores relative to that potential
-    bool dense_narrow = false, dense_compact = false, dense_relative = false;   // layout of the last run's dense pass (poa_batch_last_layout)
+    bool dense_narrow = false, dense_compact = false, dense_relative = false, dense_derived_gaps = false;   // layout of the last run's dense pass (poa_batch_last_layout)
     DevBuf<uint8_t> d_qseq;
     DevBuf<uint64_t> d_qoff, d_scratch_off, d_pair_off;
     DevBuf<uint32_t> d_pitch, d_carry, d_score, d_flags, d_npairs;
@@ -673,7 +673,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     }
     if (relative) { narrow = true; compact = true; }
     b->relative = relative;
-    b->dense_narrow = narrow; b->dense_compact = compact; b->dense_relative = relative;
+    b->dense_narrow = narrow; b->dense_compact = compact; b->dense_relative = relative; b->dense_derived_gaps = false;
     b->narrow = narrow;
     b->compact = compact;
     // 2-byte elements let twice the queries share the workspace; the exact replay needs the u32 plan
@@ -758,11 +758,17 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                 if (const int* xv = T.ptr(POA_TUNE_PX)) px = (px && (*xv) != 0) || (px && relative);
                 if (px) {
                     // scores below 0x3FFF (same bound as for u16, one power lower): two flags ride in the stored M value
-                    // (below 0x0FFF: all four; POA_MF = 0 / 1 / 2 caps the variant for A-B runs)
+                    // (below 0x0FFF: all four; POA_MF = 0 / 1 / 2 caps the variant for A-B runs).  Wherever flags fit beside the
+                    // score the engine takes variant 3: the two Match-state flags in the score and no gap-state flags at all (the
+                    // traceback derives them, poa_tb_derive.hpp) - the forward pass is instruction-issue bound and they are a
+                    // fifth of its instructions
                     int mf = relative ? 0 : (ub <= 4094 ? 2 : (ub <= 16382 ? 1 : 0));
-                    if (const int* fv2 = T.ptr(POA_TUNE_MF)) mf = std::min(mf, std::max(0, (*fv2)));
-                    tp.code_fmt = mf == 2 ? 3u : (mf == 1 ? 2u : 1u);
-                    if (mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, dim3(blocks), dim3(256), 0, stream, fp);
+                    if (const int* fv2 = T.ptr(POA_TUNE_MF)) mf = (*fv2) == 3 ? (mf >= 1 ? 3 : 0) : std::min(mf, std::max(0, (*fv2)));
+                    else if (mf >= 1) mf = 3;
+                    tp.code_fmt = mf == 3 ? 4u : (mf == 2 ? 3u : (mf == 1 ? 2u : 1u));
+                    b->dense_derived_gaps = mf == 3;
+                    if (mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, dim3(blocks), dim3(256), 0, stream, fp);
+                    else if (mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, dim3(blocks), dim3(256), 0, stream, fp);
                     else if (mf == 1) hipLaunchKernelGGL(poa_forward_px_kernel<1>, dim3(blocks), dim3(256), 0, stream, fp);
                     else hipLaunchKernelGGL(poa_forward_px_kernel<0>, dim3(blocks), dim3(256), 0, stream, fp);
                 } else if (mw && (relative || pxmw_ok(T, ch.count, max_pitch))) {
@@ -1191,7 +1197,8 @@ int poa_batch_device_results(poa_batch_t* b, void** score, void** flags, void** 
 int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout) {
     if (!b || !layout) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_layout: null argument");
     if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_layout: poa_batch_run has not been called");
-    *layout = (b->dense_narrow ? POA_LAYOUT_U16 : 0u) | (b->dense_compact ? POA_LAYOUT_COMPACT : 0u) | (b->dense_relative ? POA_LAYOUT_RELATIVE : 0u);
+    *layout = (b->dense_narrow ? POA_LAYOUT_U16 : 0u) | (b->dense_compact ? POA_LAYOUT_COMPACT : 0u) | (b->dense_relative ? POA_LAYOUT_RELATIVE : 0u) |
+              (b->dense_derived_gaps ? POA_LAYOUT_DERIVED_GAPS : 0u);
     return POA_OK;
 }
 

@@ -67,6 +67,10 @@ __device__ __forceinline__ uint32_t pk_hi_hi(uint32_t a, uint32_t b) { return __
 // Match-state traceback step reads — I == M, D == M — are stored in bits 14 and 15 of the M value itself (0x3FFF = INF,
 // larger finite values of irrelevant cells are clamped to it), and the flag plane keeps only the two gap-state flags
 // (one dword per lane and row).  The traceback then needs ONE load per diagonal step instead of two.
+// MF = 3 (same bound as MF = 1): the M plane of MF = 1 and nothing else per cell (TbParams::code_fmt 4).  The two gap-state
+// flags are read only by the few traceback steps that stand in a gap state, and both follow from the stored M values, the
+// kept D rows and the value the walk carries (poa_tb_derive.hpp): leaving them out saves ~7 of the ~37 instructions per
+// register and row.
 template <int MF>
 __global__ __launch_bounds__(256) void poa_forward_px_kernel(FwdParams P) {
     constexpr int K = 8;                 // columns per lane and quad == packed registers per row array
@@ -226,18 +230,26 @@ __global__ __launch_bounds__(256) void poa_forward_px_kernel(FwdParams P) {
 #pragma unroll
                 for (int k = 0; k < K; ++k) u[k] = pk_add_sat(Hc[k], ioe2);
                 __builtin_amdgcn_sched_barrier(0);
+                // insertion open: A = (q != child symbol) ? H + oe : INF.  MF == 3 has no deletion flag to fill the chain's wait
+                // states: there the open of column k + 1 is issued inside the chain's step k instead
 #pragma unroll
-                for (int k = 0; k < K; ++k) u[k] = pk_max(u[k], mI[k]);   // insertion open: A = (q != child symbol) ? H + oe : INF
+                for (int k = 0; k < (MF == 3 ? 1 : K); ++k) u[k] = pk_max(u[k], mI[k]);
                 __builtin_amdgcn_sched_barrier(0);
                 // in-lane insertion chain, both quads at once; the deletion flag (independent of it) fills its wait states
                 uint32_t t = INF2;
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const uint32_t te = pk_add_sat(t, e2);
-                    const uint32_t dd = pk_sub_sat(PDe[k], Dc[k]);
-                    Ic[k] = t;
-                    t = pk_min(te, u[k]);
-                    fDv[k] = pk_sub_sat(0x00010001u, dd);
+                    if (MF == 3) {
+                        if (k + 1 < K) u[k + 1] = pk_max(u[k + 1], mI[k + 1]);
+                        Ic[k] = t;
+                        t = pk_min(te, u[k]);
+                    } else {
+                        const uint32_t dd = pk_sub_sat(PDe[k], Dc[k]);
+                        Ic[k] = t;
+                        t = pk_min(te, u[k]);
+                        fDv[k] = pk_sub_sat(0x00010001u, dd);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 const uint32_t Pm = ~wave_scan_max_minus_pk(~t, step2, w15_2, w31_2);
@@ -253,12 +265,16 @@ __global__ __launch_bounds__(256) void poa_forward_px_kernel(FwdParams P) {
             }
 
             // flag bit-planes: A: I == M, B: I[j] == I[j-1] + e, C: D == M, D: D == PD + e  (lhs >= rhs by construction)
-            uint32_t i_left = shr_lane(Ic[K - 1]);
+            uint32_t i_left = MF == 3 ? 0u : shr_lane(Ic[K - 1]);
             uint32_t accA = 0, accB = 0, accC = 0, accD = 0;  // bit k (quad 0) and bit 16 + k (quad 1)
             uint32_t Ms[K];                                   // what is stored for M
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const uint32_t fA = pk_eq_ge(Ic[k], Mc[k]), fC = pk_eq_ge(Dc[k], Mc[k]);
+                if (MF == 3) {   // only the two flags of a Match-state step: the traceback derives B and D (poa_tb_derive.hpp)
+                    Ms[k] = (fC << 15) | ((fA << 14) | pk_min(Mc[k], 0x3FFF3FFFu));
+                    continue;
+                }
                 const uint32_t fB = pk_eq_ge(pk_add_sat(i_left, e2), Ic[k]), fD = fDv[k];
                 if (MF == 2) {
                     Ms[k] = (fC << 15) | ((fA << 14) | ((fD << 13) | ((fB << 12) | pk_min(Mc[k], 0x0FFF0FFFu))));

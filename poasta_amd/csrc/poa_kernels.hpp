@@ -28,6 +28,7 @@
 
 #include "../../include/poasta_amd.h"
 #include "poa_graph.hpp"
+#include "poa_tb_derive.hpp"
 
 #ifndef POA_FWD_MIN_WAVES
 #define POA_FWD_MIN_WAVES 1
@@ -86,6 +87,7 @@ struct TbParams {
     uint32_t code_fmt;            // compact layout: 0 = one nibble per cell, 1 = bit-planes (poa_forward_px_kernel<0>, poa_forward_pxmw_kernel),
                                   // 2 = flags A, C in bits 14, 15 of the stored M value, B, D as bit-planes (poa_forward_px_kernel<1>)
                                   // 3 = flags B, D, A, C in bits 12..15 of the stored M value, no flag words (poa_forward_px_kernel<2>)
+                                  // 4 = flags A, C in bits 14, 15 of the stored M value, B and D not stored: derived (poa_forward_px_kernel<3>)
     const uint32_t* row_depth;    // relative encoding: stored value = score - e * (row_depth[row] - column); nullptr: absolute
     const uint32_t* d_slot;       // compact layout: slot of a row's kept D row (FlatGraph::d_slot / pred_dslot)
     const uint32_t* pred_dslot;
@@ -160,6 +162,11 @@ template <> struct PlaneIO<uint16_t> {
 // Traceback: the reference's score-based rule (scoring/gap_affine.rs:550-657, :804-915) applied to
 // the dense planes.  Every test of a step is evaluated so that the certificate "exactly one
 // candidate, no phantom below target" can be decided.  One thread per query.
+// code_fmt 2 and 4: a stored M value carries two flags — bit 14: I == M, bit 15: D == M — over a 14-bit score (0x3FFF = INF);
+// code_fmt 4 stores nothing else per cell: the two gap-state flags are derived where a step needs them (poa_tb_derive.hpp)
+constexpr uint32_t MF_MASK = 0x3FFFu;
+__device__ __forceinline__ uint32_t mf_value(uint32_t raw) { const uint32_t v = raw & MF_MASK; return v == MF_MASK ? INF : v; }
+
 template <typename T>
 struct TbCtx {
     const RowMeta* rows;
@@ -168,7 +175,7 @@ struct TbCtx {
     const T* I;
     const T* D;
     const uint32_t* codes;  // compact layout: 4 flag bits per cell at the I plane's place
-    uint32_t code_fmt;      // 0: nibble per cell, 1: bit-planes, 2: A, C in the M value + B, D bit-planes
+    uint32_t code_fmt;      // TbParams::code_fmt
     uint32_t tiled;         // 1: the table of the replayed search (u32, ex_cell_index layout) at M
     uint32_t n_rows;
     const uint8_t* q;
@@ -177,6 +184,19 @@ struct TbCtx {
     const uint32_t* row_depth;  // relative encoding (TbParams::row_depth) or nullptr
     const uint32_t* d_slot;     // compact layout: c.D holds only the kept D rows, row r at slot d_slot[r]
     const uint32_t* pred_dslot;
+    // what poa_tb_derive.hpp reads (code_fmt 4 only: u16 cells, absolute encoding)
+    __device__ __forceinline__ void cell(uint32_t row, uint32_t j, uint32_t& v, uint32_t& a, uint32_t& cf) const {
+        const uint32_t raw = (uint32_t)M[(uint64_t)row * pitch + j];
+        v = mf_value(raw); a = (raw >> 14) & 1u; cf = (raw >> 15) & 1u;
+    }
+    __device__ __forceinline__ uint32_t m(uint32_t row, uint32_t j) const { return mf_value((uint32_t)M[(uint64_t)row * pitch + j]); }
+    __device__ __forceinline__ uint32_t d_kept(uint32_t row, uint32_t j) const {
+        return PlaneIO<T>::get(D + (uint64_t)(d_slot ? d_slot[row] : row) * pitch + j);
+    }
+    __device__ __forceinline__ uint32_t pred(uint32_t k) const { return pred_rows[k]; }
+    __device__ __forceinline__ uint32_t pred_d(uint32_t k, uint32_t j) const {
+        return PlaneIO<T>::get(D + (uint64_t)(pred_dslot ? pred_dslot[k] : pred_rows[k]) * pitch + j);
+    }
 };
 
 struct TbStep {
@@ -199,14 +219,11 @@ __device__ inline bool tb_open_i(const TbCtx<T>& c, const RowMeta& m, uint32_t j
     return (uint32_t)m.child_sym != (uint32_t)c.q[j];
 }
 
-// code_fmt 2: a stored M value carries two flags — bit 14: I == M, bit 15: D == M — over a 14-bit score (0x3FFF = INF)
-constexpr uint32_t MF_MASK = 0x3FFFu;
 // code_fmt 3: four flags — bit 12: I[j] == I[j-1] + e, bit 13: D == PD + e, bit 14: I == M, bit 15: D == M — over a 12-bit score
 constexpr uint32_t MF4_MASK = 0x0FFFu;
 __device__ __forceinline__ uint32_t mf4_value(uint32_t raw) { const uint32_t v = raw & MF4_MASK; return v == MF4_MASK ? INF : v; }
 // dwords of [B, D] flag bit-planes per row: one per lane that owns columns of the row (a short row has fewer than 64)
 __host__ __device__ __forceinline__ uint32_t mf_code_stride(uint32_t pitch) { return pitch / 8 < 64u ? pitch / 8 : 64u; }
-__device__ __forceinline__ uint32_t mf_value(uint32_t raw) { const uint32_t v = raw & MF_MASK; return v == MF_MASK ? INF : v; }
 // the score of cell (row, j) of the M plane, whatever the format
 template <typename T>
 __device__ __forceinline__ uint32_t pl_tiled(const TbCtx<T>& c, uint32_t row, uint32_t j, uint32_t st) {
@@ -220,7 +237,7 @@ __device__ __forceinline__ uint32_t tb_abs(const TbCtx<T>& c, uint32_t v, uint32
 template <typename T>
 __device__ __forceinline__ uint32_t plM(const TbCtx<T>& c, uint32_t row, uint32_t j) {
     if (c.tiled) return pl_tiled(c, row, j, 0);
-    if (c.code_fmt == 2) return mf_value((uint32_t)c.M[(uint64_t)row * c.pitch + j]);
+    if (c.code_fmt == 2 || c.code_fmt == 4) return mf_value((uint32_t)c.M[(uint64_t)row * c.pitch + j]);
     if (c.code_fmt == 3) return mf4_value((uint32_t)c.M[(uint64_t)row * c.pitch + j]);
     if (c.row_depth) {
         const uint32_t depth = c.row_depth[row];  // independent of the plane load: one round trip for both
@@ -344,7 +361,7 @@ __device__ inline TbStep tb_step(const TbCtx<T>& c, uint32_t row, uint32_t j, ui
         }
         if (COMPACT && (m.flags & ROW_CHAIN)) {
             // single predecessor right above: D[row][j] == D[row-1][j] + e is code bit 3
-            if (tb_code(c, row, j) & 8u) cand(row - 1, j, 1);
+            if (c.code_fmt == 4 ? tbd_d_extends(c, row, j, cs) : (tb_code(c, row, j) & 8u) != 0) cand(row - 1, j, 1);
         } else {
             for (uint32_t pe0 = 0; pe0 < m.pred_count; pe0 += 4) {
                 uint32_t prs[4], vals[4], slots[4];
@@ -369,7 +386,7 @@ __device__ inline TbStep tb_step(const TbCtx<T>& c, uint32_t row, uint32_t j, ui
             const uint32_t pm = plM(c, row, j - 1);
             if (pm == t_open) cand(row, j - 1, 0);
             else if (!tb_open_i(c, m, j - 1) && pm < t_open) bad = true;
-            const bool ext = COMPACT ? (tb_code(c, row, j) & 2u) != 0 : plI(c, row, j - 1) == t_ext;
+            const bool ext = COMPACT ? (c.code_fmt == 4 ? tbd_i_extends(c, m, row, j, cs) : (tb_code(c, row, j) & 2u) != 0) : plI(c, row, j - 1) == t_ext;
             if (ext) {
                 const bool only = (n_cand == 0);
                 cand(row, j - 1, 0);  // sic: the reference returns Match here (gap_affine.rs:649)
