@@ -54,6 +54,14 @@ extern "C" {
 #define POA_MODE_EXACT 1u   /* dense pass, then a replay of the reference's own A* search (same pop order, greedy
                                extension and pruning) for EVERY query: alignments bit-identical incl. tie-breaks */
 #define POA_MODE_HYBRID 2u  /* dense pass, then the exact replay only for queries whose dense flags are non-zero */
+#define POA_MODE_SCORE 3u   /* forward sweep only: score[] as in dense mode, no alignment.  Only the rows some later row still
+                               reads are kept (poa_graph_sweep_slots), so a query needs n_slots x pitch cells of M and D instead
+                               of rows x pitch.  pairs may be NULL and pair_capacity 0; pair_off[0..n] is all zero.  flags[i]
+                               carries only the bits dense mode derives from the input alone, POA_FLAG_EMPTY_GRAPH and
+                               POA_FLAG_SHORT_QUERY; the path-dependent bits (AMBIGUOUS, START_QUIRK, TRUNCATED, REF_PANIC)
+                               are not evaluated and stay clear.  Global only: with POA_SPAN_ENDS_FREE every entry point
+                               returns POA_ERR_UNSUPPORTED.  heuristic and pruning are ignored.  A resident batch must be
+                               created for it (poa_batch_create_ex) and runs in no other mode. */
 #define POA_HEURISTIC_DIJKSTRA 0u /* AffineDijkstra   (src/aligner/config.rs:49)  */
 #define POA_HEURISTIC_MINGAP 1u   /* AffineMinGapCost (src/aligner/config.rs:104), the default of both reference CLIs */
 
@@ -208,6 +216,10 @@ int poa_graph_update(poa_graph_t* g, uint32_t n_nodes_with_start_end, uint32_t s
                      const uint32_t* succ_off, const uint32_t* succ, const uint32_t* pred_off, const uint32_t* pred);
 
 uint32_t poa_graph_rows(const poa_graph_t* g);           /* == n */
+/* slots of the score-only sweep: slot[n] by ROW (POA_NONE: the row is never read back); *n_slots = rows alive at once.
+ * A row has a slot iff some successor is not the chain row directly below it; it is live from its own row to its last
+ * reader.  Host-side table, recomputed by poa_graph_update; needs no device. */
+int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot /* may be NULL */, uint32_t* n_slots);
 /* row (topological rank used for the score planes) of every node; rank[n] */
 int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank);
 
@@ -251,6 +263,8 @@ int poa_align_batch_2piece(const poa_graph_t* g, const poa_costs2_t* costs, uint
  * its backtrace (gap_affine_2piece.rs:639-794, :944-1043); flags: POA_FLAG_REF_PANIC, POA_FLAG_TRUNCATED,
  * POA_FLAG_EXACT_OVERFLOW (queue pool: raise cfg->queue_entries_per_cell).  search_counters (may be NULL): 4 words per query —
  * num_queued, num_visited, num_pruned (AstarResult, astar.rs:228) and the queue entries that were live at once. */
+/* Mode SCORE: the scores poa_align_batch_2piece returns, by the score-only sweep under the one-piece costs
+ * open' = open1 + extend1 - extend2, extend' = extend2; no pairs, flags as under POA_MODE_SCORE. */
 int poa_align_batch_2piece_ex(const poa_graph_t* g, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t n_queries,
                               const uint8_t* qseq, const uint64_t* qoff, uint32_t* score,
                               poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
@@ -271,6 +285,16 @@ void poa_release_cache(void);
  * poa_batch_fetch synchronises the stream and copies results to the host. */
 int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq,
                      const uint64_t* qoff, uint64_t workspace_bytes, poa_batch_t** out);
+/* same for a batch that will run in cfg->mode (cfg NULL or any mode but POA_MODE_SCORE == poa_batch_create).  A batch created
+ * for POA_MODE_SCORE holds max(n_slots, 1) x pitch 4-byte cells of M and of D per query (+ 256 bytes of padding) instead of
+ * full planes, is chunked by that footprint (a batch that fits runs as one chunk) and has no pair buffers.  Besides the slots
+ * it holds, only when some query is longer than 1024 columns, the carries between strips: 16 bytes per graph row and query
+ * in flight (not part of poa_batch_workspace_bytes).  The one-shot calls create and destroy such a batch per call.  Running it in
+ * another mode, or a batch of poa_batch_create in POA_MODE_SCORE, returns POA_ERR_INVALID_ARG. */
+int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq,
+                        const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out);
+/* bytes of the plane workspace the batch holds */
+int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes);
 int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream);
 /* same with a mode: cfg NULL == dense */
 int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);

@@ -345,6 +345,36 @@ public:
         return out;
     }
 
+    // scores only (POA_MODE_SCORE): the forward sweep over the rows still alive, no score planes, no traceback.  score = what
+    // align_batch returns in Mode::Dense; alignment empty; flags limited to POA_FLAG_EMPTY_GRAPH | POA_FLAG_SHORT_QUERY.
+    std::vector<AstarResult> score_batch(const graphs::POAGraph& g, const std::vector<std::string>& seqs, poa_stats_t* stats = nullptr) const {
+        const uint32_t n = (uint32_t)seqs.size();
+        std::vector<uint64_t> qoff(n + 1, 0);
+        std::string qseq;
+        for (uint32_t i = 0; i < n; ++i) { qseq += seqs[i]; qoff[i + 1] = qseq.size(); }
+        std::vector<uint32_t> score(n), flags(n);
+        std::vector<uint64_t> pair_off(n + 1, 0);
+        poa_config_t cfg{};
+        cfg.mode = POA_MODE_SCORE; cfg.heuristic = Config::heuristic;
+        if (aln_type_.ends_free) cfg.span = POA_SPAN_ENDS_FREE;   // (the library answers POA_ERR_UNSUPPORTED)
+        int rc;
+        if constexpr (Config::two_piece) {
+            poa_costs2_t c{};
+            c.mismatch = config_.costs.mismatch(); c.gap_open1 = config_.costs.gap_open(); c.gap_extend1 = config_.costs.gap_extend();
+            c.gap_open2 = config_.costs.gap_open2(); c.gap_extend2 = config_.costs.gap_extend2();
+            rc = poa_align_batch_2piece_ex(g.device_graph(), &c, &cfg, n, (const uint8_t*)qseq.data(), qoff.data(), score.data(), nullptr,
+                                           pair_off.data(), 0, flags.data(), stats, nullptr, device_);
+        } else {
+            const poa_costs_t c{config_.costs.mismatch(), config_.costs.gap_open(), config_.costs.gap_extend(), 0};
+            rc = poa_align_batch_ex(g.device_graph(), &c, &cfg, n, (const uint8_t*)qseq.data(), qoff.data(), score.data(), nullptr,
+                                    pair_off.data(), 0, flags.data(), stats, device_);
+        }
+        if (rc != POA_OK) throw PoastaError(std::string("poa_align_batch (score-only): ") + poa_last_error());
+        std::vector<AstarResult> out(n);
+        for (uint32_t i = 0; i < n; ++i) { out[i].score = score[i]; out[i].flags = flags[i]; }
+        return out;
+    }
+
 private:
     Config config_;
     AlignmentType aln_type_;

@@ -21,7 +21,8 @@ FLAG_AMBIGUOUS, FLAG_START_QUIRK, FLAG_REF_PANIC, FLAG_SHORT_QUERY, FLAG_TRUNCAT
 EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_create", "poa_graph_destroy",
            "poa_graph_rows", "poa_graph_node_rows", "poa_graph_update", "poa_align_batch", "poa_align_batch_ex", "poa_align_batch_2piece", "poa_align_batch_2piece_ex", "poa_planes_2piece", "poa_release_cache", "poa_batch_create", "poa_batch_run",
            "poa_batch_run_ex",
-           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_fetch_planes", "poa_batch_destroy"]
+           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_fetch_planes", "poa_batch_destroy",
+           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes"]
 
 
 class PoaCosts2(C.Structure):
@@ -73,7 +74,7 @@ BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED = 0, 1, 2
 SPAN_GLOBAL, SPAN_ENDS_FREE = 0, 1
 
 
-MODE_DENSE, MODE_EXACT, MODE_HYBRID = 0, 1, 2
+MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE = 0, 1, 2, 3
 HEURISTIC_DIJKSTRA, HEURISTIC_MINGAP = 0, 1
 FLAG_EXACT_OVERFLOW = 0x40
 CFG_FULL_PLANES = 1
@@ -145,6 +146,12 @@ def lib():
     L.poa_batch_run_ex.argtypes = [vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp]
     L.poa_batch_create.restype = C.c_int
     L.poa_batch_create.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint64, C.POINTER(vp)]
+    L.poa_graph_sweep_slots.restype = C.c_int
+    L.poa_graph_sweep_slots.argtypes = [vp, vp, vp]
+    L.poa_batch_create_ex.restype = C.c_int
+    L.poa_batch_create_ex.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.POINTER(PoaConfig), C.c_uint64, C.POINTER(vp)]
+    L.poa_batch_workspace_bytes.restype = C.c_int
+    L.poa_batch_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.poa_batch_run.restype = C.c_int
     L.poa_batch_run.argtypes = [vp, C.POINTER(PoaCosts), vp]
     L.poa_batch_fetch.restype = C.c_int

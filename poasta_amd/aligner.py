@@ -153,13 +153,14 @@ class AffineDijkstra(AffineMinGapCost):
     heuristic = _lib.HEURISTIC_DIJKSTRA
 
 
-MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE_HYBRID}
+MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE_HYBRID, "score": _lib.MODE_SCORE}
 
 
 def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, queue_entries_per_cell=0.0, full_planes=False,
                 aln_type=AlignmentType.Global, **tune):
     """poa_config_t: `mode` "dense" | "exact" (replay the reference's A* for every query: bit-identical
-    tie-breaks) | "hybrid" (replay only the queries the dense pass could not certify); `aln_type` Global or EndsFree(...)."""
+    tie-breaks) | "hybrid" (replay only the queries the dense pass could not certify) | "score" (forward sweep only: dense
+    mode's scores, no alignment, memory for the live rows only); `aln_type` Global or EndsFree(...)."""
     cfg = _lib.PoaConfig(MODES[mode] if isinstance(mode, str) else int(mode), int(heuristic), 1 if pruning else 0,
                          float(queue_entries_per_cell), _lib.CFG_FULL_PLANES if full_planes else 0)
     if isinstance(aln_type, EndsFree):
@@ -243,6 +244,13 @@ class DeviceGraph:
         _lib.check(_lib.lib().poa_graph_node_rows(self.handle, _p(r)))
         return r
 
+    def sweep_slots(self):
+        """(slot, n_slots) of the score-only sweep: slot[row] (POA_NONE: never read back), rows alive at once."""
+        slot = np.zeros(max(self.graph.n, 1), np.uint32)
+        n = C.c_uint32(0)
+        _lib.check(_lib.lib().poa_graph_sweep_slots(self.handle, _p(slot), C.byref(n)))
+        return slot[:self.graph.n], int(n.value)
+
     def __del__(self):
         try:
             if self.handle:
@@ -268,14 +276,20 @@ def _device_graph(graph):
 class ResidentBatch:
     """Queries + results resident in HBM (`poa_batch_*`): create once, run many times."""
 
-    def __init__(self, graph, qseq, qoff, device=0, workspace_bytes=0):
+    def __init__(self, graph, qseq, qoff, device=0, workspace_bytes=0, config=None):
+        """config: the poa_config_t the batch will run with — needed for mode "score", whose batch holds slots instead of
+        planes (poa_batch_create_ex) and runs in no other mode."""
         self.dg = _device_graph(graph)
         self.qseq = np.ascontiguousarray(qseq, np.uint8)
         self.qoff = np.ascontiguousarray(qoff, np.uint64)
         self.n = len(self.qoff) - 1
         h = C.c_void_p()
-        _lib.check(_lib.lib().poa_batch_create(self.dg.handle, device, self.n, _p(self.qseq), _p(self.qoff),
-                                               int(workspace_bytes), C.byref(h)))
+        if config is None:
+            _lib.check(_lib.lib().poa_batch_create(self.dg.handle, device, self.n, _p(self.qseq), _p(self.qoff),
+                                                   int(workspace_bytes), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().poa_batch_create_ex(self.dg.handle, device, self.n, _p(self.qseq), _p(self.qoff),
+                                                      C.byref(config), int(workspace_bytes), C.byref(h)))
         self.handle = h
         self.pair_capacity = int(self.qoff[-1]) + self.n * self.dg.graph.n
 
@@ -330,6 +344,12 @@ class ResidentBatch:
         st = _lib.PoaStats()
         _lib.check(_lib.lib().poa_batch_stats(self.handle, C.byref(st)))
         return st.as_dict()
+
+    def workspace_bytes(self):
+        """Bytes of the plane workspace the batch holds."""
+        v = C.c_uint64(0)
+        _lib.check(_lib.lib().poa_batch_workspace_bytes(self.handle, C.byref(v)))
+        return int(v.value)
 
     def search_counters(self):
         """AstarResult::{num_queued, num_visited, num_pruned} + wave-search steps, one row per query (exact / hybrid runs)."""
@@ -398,6 +418,29 @@ class PoastaAligner:
         c = self.config.costs._c()
         _lib.check(_lib.lib().poa_planes_2piece(dg.handle, C.byref(c), _p(s), len(s), *[_p(a) for a in out], self.device))
         return out
+
+    def score_batch(self, ref_graph, seqs=None, qseq=None, qoff=None):
+        """Scores only (mode "score"): (score, flags) as numpy arrays — dense mode's scores, flags limited to what follows
+        from the input alone (EMPTY_GRAPH, SHORT_QUERY).  No score planes are stored, no traceback runs."""
+        dg = _device_graph(ref_graph)
+        if seqs is not None:
+            qseq, qoff = pack_queries(seqs)
+        qseq = np.ascontiguousarray(qseq, np.uint8)
+        qoff = np.ascontiguousarray(qoff, np.uint64)
+        n = len(qoff) - 1
+        score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        pair_off = np.zeros(n + 1, np.uint64)
+        st = _lib.PoaStats()
+        c = self.config.costs._c()
+        cfg = make_config("score", self.config.heuristic)
+        if getattr(self.config, "two_piece", False):
+            _lib.check(_lib.lib().poa_align_batch_2piece_ex(dg.handle, C.byref(c), C.byref(cfg), n, _p(qseq), _p(qoff), _p(score),
+                                                            None, _p(pair_off), 0, _p(flags), C.byref(st), None, self.device))
+        else:
+            _lib.check(_lib.lib().poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, _p(qseq), _p(qoff), _p(score),
+                                                     None, _p(pair_off), 0, _p(flags), C.byref(st), self.device))
+        self.last_stats = st.as_dict()
+        return score, flags
 
     # -- batch shape (lasagna.rs:246-268) ------------------------------------------------------
     def align_batch(self, ref_graph, seqs=None, qseq=None, qoff=None, want_pairs=True, pruning=True):

@@ -32,6 +32,8 @@ struct TuneView {
 #include "poa_forward_packed.hpp"
 #include "poa_forward_px.hpp"
 #include "poa_twopiece.hpp"
+#include "poa_sweep_rows.hpp"
+#include "poa_forward_sweep.hpp"
 
 using namespace poa_amd;
 
@@ -121,7 +123,7 @@ struct PlaneWorkspace {
     uint32_t* p = nullptr;
     size_t bytes = 0;
     int device = -1;
-    bool acquire(int dev, size_t need, std::string& err);
+    bool acquire(int dev, size_t need, std::string& err, bool exact = false);
     void release();
     ~PlaneWorkspace() { release(); }
 };
@@ -132,17 +134,19 @@ struct WsCache {
     size_t bytes[16] = {};
 } g_ws_cache;
 }  // namespace
-bool PlaneWorkspace::acquire(int dev, size_t need, std::string& err) {
+// exact: a parked block is taken only if it has exactly the size asked for (score-only batches: what the batch holds is what
+// its slots need, poa_batch_workspace_bytes), and a parked block of another size stays parked for the next dense batch
+bool PlaneWorkspace::acquire(int dev, size_t need, std::string& err, bool exact) {
     release();
     device = dev;
     if (dev >= 0 && dev < 16) {
         std::lock_guard<std::mutex> lk(g_ws_cache.mu);
-        if (g_ws_cache.p[dev] && g_ws_cache.bytes[dev] >= need) {
+        if (g_ws_cache.p[dev] && (exact ? g_ws_cache.bytes[dev] == need : g_ws_cache.bytes[dev] >= need)) {
             p = (uint32_t*)g_ws_cache.p[dev]; bytes = g_ws_cache.bytes[dev];
             g_ws_cache.p[dev] = nullptr; g_ws_cache.bytes[dev] = 0;
             return true;
         }
-        if (g_ws_cache.p[dev]) {  // too small: give it back before asking for a bigger one
+        if (g_ws_cache.p[dev] && !exact) {  // too small: give it back before asking for a bigger one
             (void)hipFree(g_ws_cache.p[dev]);
             g_ws_cache.p[dev] = nullptr; g_ws_cache.bytes[dev] = 0;
         }
@@ -168,6 +172,7 @@ void PlaneWorkspace::release() {
 
 struct poa_graph {
     FlatGraph g;
+    SweepRows sweep;        // row liveness / slots of the score-only sweep (poa_sweep_rows.hpp), rebuilt with g
     std::mutex bubble_mu;   // the bubble index (exact / hybrid mode only) is built on first use; batches on other threads may share the handle
 };
 
@@ -228,6 +233,12 @@ struct poa_batch {
     bool exact_ready = false;
     bool prof_on = false;              // the last run asked for the replay kernel's cycle counts (POA_TUNE_WS_PROF)
     uint32_t last_mode = 0;
+    // score-only batch (poa_batch_create_ex with POA_MODE_SCORE): the workspace holds n_sweep_slots rows of M and D per query,
+    // d_dslot / d_pred_dslot hold SweepRows::slot / pred_slot, no pair buffers exist
+    bool sweep = false;
+    uint32_t sweep_slots = 1;          // max(n_sweep_slots, 1)
+    uint64_t sweep_slotted = 0;        // rows per query that are stored at all
+    uint64_t sweep_bytes_written = 0;  // slot bytes the last score-only run stored (poa_stats_t.plane_bytes)
 
     // one event set per run since the last stats call: [begin, (fwd_end, tb_end) per chunk..., end]
     std::vector<std::vector<hipEvent_t>> runs;
@@ -257,7 +268,7 @@ static int check_pipeline_error(poa_batch* b) {
 static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     const uint32_t n = b->n_queries;
     const uint32_t keep_flagged = stats->n_flagged;
-    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = b->plane_bytes_total;
+    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = b->sweep ? b->sweep_bytes_written : b->plane_bytes_total;
     stats->n_queries = n; stats->n_chunks = (uint32_t)b->cur().chunks.size();
     stats->n_flagged = keep_flagged;
     stats->ms_h2d = b->ms_h2d; stats->ms_d2h = 0.f;
@@ -287,6 +298,7 @@ static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     }
     stats->n_runs = (uint32_t)b->runs.size();
     stats->n_forward_launches = launches;
+    if (b->sweep) tb = 0.f;   // nothing but the sweep runs
     stats->ms_forward = fwd; stats->ms_traceback = tb; stats->ms_exact = ex; stats->ms_total = total;
     for (auto& r : b->runs) b->free_sets.push_back(std::move(r));
     b->runs.clear();
@@ -308,7 +320,7 @@ static bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch) {
 
 extern "C" {
 
-const char* poa_version(void) { return "poasta_amd 0.1 (gfx950)"; }
+const char* poa_version(void) { return "poasta_amd 0.2 (gfx950)"; }
 const char* poa_last_error(void) { return g_err.c_str(); }
 
 int poa_device_count(void) {
@@ -331,6 +343,11 @@ int poa_graph_create(uint32_t n, uint32_t start, uint32_t end, const uint8_t* sy
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_create: host allocation failed");
     }
     if (rc != POA_OK) return fail(rc, err);
+    try {
+        build_sweep_rows(h->g, h->sweep);
+    } catch (const std::bad_alloc&) {
+        return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_create: host allocation failed");
+    }
     *out = h.release();
     return POA_OK;
 }
@@ -343,14 +360,24 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     std::string err;
     int rc;
     FlatGraph ng;
+    SweepRows nsw;
     try {
         rc = build_flat_graph(n, start, end, symbol, succ_off, succ, pred_off, pred, ng, err);
+        if (rc == POA_OK) build_sweep_rows(ng, nsw);
     } catch (const std::bad_alloc&) {
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_update: host allocation failed");
     }
     if (rc != POA_OK) return fail(rc, err);   // (the handle keeps the graph it had)
     std::lock_guard<std::mutex> lk(g->bubble_mu);
     g->g = std::move(ng);
+    g->sweep = std::move(nsw);
+    return POA_OK;
+}
+
+int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot, uint32_t* n_slots) {
+    if (!g || !n_slots) return fail(POA_ERR_INVALID_ARG, "poa_graph_sweep_slots: null argument");
+    if (slot && !g->sweep.slot.empty()) std::memcpy(slot, g->sweep.slot.data(), g->sweep.slot.size() * sizeof(uint32_t));
+    *n_slots = g->sweep.n_slots;
     return POA_OK;
 }
 
@@ -360,8 +387,31 @@ int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank) {
     return POA_OK;
 }
 
+static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out);
+
 int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                      uint64_t workspace_bytes, poa_batch_t** out) {
+    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, false, out);
+}
+
+int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
+                        const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out) {
+    if (cfg && cfg->mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_batch_create_ex: unknown mode");
+    const bool sweep = cfg && cfg->mode == POA_MODE_SCORE;
+    if (sweep && cfg->span == POA_SPAN_ENDS_FREE)
+        return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
+    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out);
+}
+
+int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
+    if (!b || !bytes) return fail(POA_ERR_INVALID_ARG, "poa_batch_workspace_bytes: null argument");
+    *bytes = b->d_planes.bytes;
+    return POA_OK;
+}
+
+static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out) {
     if (!out) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: out is null");
     *out = nullptr;
     if (!g || !qoff || (n_queries && qoff[n_queries] && !qseq))
@@ -380,6 +430,9 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
     const FlatGraph& fg = g->g;
     b->graph = g; b->device = device; b->n_queries = n_queries;
     const uint32_t rows = fg.n;
+    b->sweep = sweep;
+    b->sweep_slots = std::max<uint32_t>(g->sweep.n_slots, 1u);
+    b->sweep_slotted = g->sweep.n_slotted;
     try {
         b->h_qoff.assign(qoff, qoff + n_queries + 1);
         b->h_pitch.resize(n_queries);
@@ -393,9 +446,10 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
         max_len = std::max(max_len, L);
         const uint32_t pitch = (uint32_t)(((L + 1 + 63) / 64) * 64);
         b->h_pitch[i] = pitch;
-        q_plane_elems[i] = 3ull * rows * pitch;
+        // score-only: n_sweep_slots rows of M and of D (4-byte cells: what the widest layout needs; u16 runs use half of it)
+        q_plane_elems[i] = sweep ? 2ull * b->sweep_slots * pitch : 3ull * rows * pitch;
         b->h_scratch_off[i] = scratch_total;
-        scratch_total += L + rows;
+        if (!sweep) scratch_total += L + rows;   // (no pairs, no traceback scratch)
         b->max_len = std::max<uint64_t>(b->max_len, L);
         b->total_bases += L;
         b->total_cells += (uint64_t)rows * (L + 1);
@@ -406,12 +460,17 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
     // workspace: as many queries' planes as fit; chunks reuse it.
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t fixed = scratch_total * 16 + (uint64_t)n_queries * 64 + qoff[n_queries] + (64ull << 20);
+    // score-only: the carries between strips (two parities x two words per row and query in flight, poa_forward_sweep.hpp) exist
+    // only when some query is longer than one 1024-column strip; they are part of what the batch holds besides the slots
+    const bool sweep_carry = sweep && max_len + 1 > 1024;
+    const uint64_t fixed = scratch_total * 16 + (uint64_t)n_queries * 64 + qoff[n_queries] + (64ull << 20) +
+                           (sweep_carry ? 16ull * n_queries * rows : 0);
     uint64_t ws = workspace_bytes;
     if (ws == 0) {
         const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
         ws = std::min<uint64_t>(b->plane_bytes_total, avail);
     }
+    if (sweep) ws = std::min<uint64_t>(ws, b->plane_bytes_total);   // a score-only batch holds its slots, never more (workspace_bytes is a cap)
     uint64_t biggest = 0;
     for (uint32_t i = 0; i < n_queries; ++i) biggest = std::max(biggest, q_plane_elems[i] * 4);
     if (ws < biggest) {
@@ -460,7 +519,7 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
         for (auto& c : pl.chunks) pl.max_chunk = std::max(pl.max_chunk, c.count);
     };
     make_plan(b->plan[0], 4, false);
-    b->plan16_same = b->plan[0].chunks.size() <= 1;
+    b->plan16_same = sweep || b->plan[0].chunks.size() <= 1;
     if (!b->plan16_same) { make_plan(b->plan[1], 2, false); make_plan(b->plan[2], 2, true); }
     const uint32_t max_chunk_any = std::max(b->plan[0].max_chunk, std::max(b->plan[1].max_chunk, b->plan[2].max_chunk));
     b->cols_per_lane = 16;
@@ -470,8 +529,8 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
     HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(fg.pred_rows.size(), 1)));
     HIP_TRY(b->d_pred_k.alloc(std::max<size_t>(fg.pred_k.size(), 1)));
     HIP_TRY(b->d_row_depth.alloc(std::max<size_t>(fg.row_depth.size(), 1)));
-    HIP_TRY(b->d_dslot.alloc(std::max<size_t>(fg.d_slot.size(), 1)));
-    HIP_TRY(b->d_pred_dslot.alloc(std::max<size_t>(fg.pred_dslot.size(), 1)));
+    HIP_TRY(b->d_dslot.alloc(std::max<size_t>(sweep ? g->sweep.slot.size() : fg.d_slot.size(), 1)));
+    HIP_TRY(b->d_pred_dslot.alloc(std::max<size_t>(sweep ? g->sweep.pred_slot.size() : fg.pred_dslot.size(), 1)));
     HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n_queries], 1)));
     HIP_TRY(b->d_qoff.alloc((size_t)n_queries + 1));
     HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n_queries, 1)));
@@ -483,12 +542,12 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
     HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n_queries, 1)));
     HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
     HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>(2ull * max_chunk_any * rows, 1)));
+    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep ? (sweep_carry ? 4ull : 0ull) : 2ull) * max_chunk_any * rows, 1)));
     HIP_TRY(b->d_pipeline_error.alloc(1));
     HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
     if (n_queries) {
         std::string werr;
-        if (!b->d_planes.acquire(device, ws + 256, werr)) return fail(POA_ERR_OUT_OF_MEMORY, "score-plane workspace: " + werr);
+        if (!b->d_planes.acquire(device, ws + 256, werr, sweep)) return fail(POA_ERR_OUT_OF_MEMORY, "score-plane workspace: " + werr);
     }
 
     hipEvent_t e0, e1;
@@ -502,10 +561,13 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
         HIP_TRY(hipMemcpy(b->d_pred_k.p, fg.pred_k.data(), fg.pred_k.size() * 4, hipMemcpyHostToDevice));
     if (!fg.row_depth.empty())
         HIP_TRY(hipMemcpy(b->d_row_depth.p, fg.row_depth.data(), fg.row_depth.size() * 4, hipMemcpyHostToDevice));
-    if (!fg.d_slot.empty())
-        HIP_TRY(hipMemcpy(b->d_dslot.p, fg.d_slot.data(), fg.d_slot.size() * 4, hipMemcpyHostToDevice));
-    if (!fg.pred_dslot.empty())
-        HIP_TRY(hipMemcpy(b->d_pred_dslot.p, fg.pred_dslot.data(), fg.pred_dslot.size() * 4, hipMemcpyHostToDevice));
+    const std::vector<uint32_t>& h_slot = sweep ? g->sweep.slot : fg.d_slot;
+    const std::vector<uint32_t>& h_pred_slot = sweep ? g->sweep.pred_slot : fg.pred_dslot;
+    if (!h_slot.empty())
+        HIP_TRY(hipMemcpy(b->d_dslot.p, h_slot.data(), h_slot.size() * 4, hipMemcpyHostToDevice));
+    if (!h_pred_slot.empty())
+        HIP_TRY(hipMemcpy(b->d_pred_dslot.p, h_pred_slot.data(), h_pred_slot.size() * 4, hipMemcpyHostToDevice));
+    if (sweep) HIP_TRY(hipMemset(b->d_pair_off.p, 0, ((size_t)n_queries + 1) * 8));
     if (qoff[n_queries]) HIP_TRY(hipMemcpy(b->d_qseq.p, qseq, qoff[n_queries], hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_qoff.p, qoff, ((size_t)n_queries + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_scratch_off.p, b->h_scratch_off.data(), ((size_t)n_queries + 1) * 8, hipMemcpyHostToDevice));
@@ -615,6 +677,85 @@ static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_confi
     return POA_OK;
 }
 
+// Score-only run of a batch created for it: one sweep launch per chunk, nothing else.  Costs are 32-bit here: the two-piece
+// reduction (poa_align_batch_2piece_ex) opens a gap at open1 + extend1 - extend2, which need not fit poa_costs_t.
+static int run_sweep(poa_batch* b, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const TuneView& T, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(b->device));
+    const poa_graph* gh = b->graph;
+    const FlatGraph& fg = gh->g;
+    b->last_mode = POA_MODE_SCORE;
+    b->last_stream = stream;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
+    // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the end cell depends on is exact in them
+    const uint64_t ub = (b->max_len ? (uint64_t)cost_o + (uint64_t)cost_e * b->max_len : 0) +
+                        (fg.min_path_nodes ? (uint64_t)cost_o + (uint64_t)cost_e * fg.min_path_nodes : 0);
+    bool narrow = ub <= 65534;
+    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    bool want_px = true;
+    if (const int* xv = T.ptr(POA_TUNE_PX)) want_px = (*xv) != 0;
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = 0;
+    const poa_batch::Plan& PL = b->cur();
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * PL.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    b->sweep_bytes_written = 0;
+    size_t ev = 1;
+    for (const auto& ch : PL.chunks) {
+        SweepParams sp;
+        sp.rows = b->d_rows.p; sp.pred_rows = b->d_pred_rows.p; sp.slot = b->d_dslot.p; sp.pred_slot = b->d_pred_dslot.p;
+        sp.n_rows = fg.n; sp.n_slots = b->sweep_slots;
+        sp.first_query = ch.first; sp.n_queries = ch.count;
+        sp.qseq = b->d_qseq.p; sp.qoff = b->d_qoff.p; sp.pitch = b->d_pitch.p; sp.plane_off = PL.d_off.p;
+        sp.planes = b->d_planes.p; sp.carry = b->d_carry.p;
+        sp.cost_x = cost_x; sp.cost_oe = cost_o + cost_e; sp.cost_e = cost_e;
+        sp.score = b->d_score.p; sp.flags = b->d_flags.p;
+        uint32_t max_pitch = 0;
+        uint64_t pitch_sum = 0;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) { max_pitch = std::max(max_pitch, b->h_pitch[i]); pitch_sum += b->h_pitch[i]; }
+        const uint32_t blocks = (ch.count + 3) / 4;
+        // The one-strip packed kernel keeps a slot row in its register layout, 1024 two-byte cells whatever the pitch: it is
+        // taken where the chunk is one strip wide and those rows fit what the chunk was given (8 bytes per slot and column).
+        const bool px = narrow && want_px && max_pitch > 512 && max_pitch <= 1024 && pitch_sum >= 512ull * ch.count;
+        // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
+        b->sweep_bytes_written += 2ull * b->sweep_slotted * (px ? 2048ull * ch.count : pitch_sum * (narrow ? 2 : 4));
+        if (px) hipLaunchKernelGGL(poa_sweep_px_kernel, dim3(blocks), dim3(256), 0, stream, sp);
+        else if (narrow) {
+            if (max_pitch <= 512) hipLaunchKernelGGL((poa_sweep_kernel<1, uint16_t>), dim3(blocks), dim3(256), 0, stream, sp);
+            else hipLaunchKernelGGL((poa_sweep_kernel<2, uint16_t>), dim3(blocks), dim3(256), 0, stream, sp);
+        } else {
+            if (max_pitch <= 256) hipLaunchKernelGGL((poa_sweep_kernel<1, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
+            else if (max_pitch <= 512) hipLaunchKernelGGL((poa_sweep_kernel<2, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
+            else hipLaunchKernelGGL((poa_sweep_kernel<4, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+    }
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
 int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream_v) { return poa_batch_run_ex(b, costs, nullptr, stream_v); }
 
 int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
@@ -622,9 +763,15 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     const TuneView T(cfg);   // what this call overrides, read once
     b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
     uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
-    if (mode > POA_MODE_HYBRID) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
+    if (mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown alignment span");
     const bool ends_free = cfg && cfg->span == POA_SPAN_ENDS_FREE;
+    if (mode == POA_MODE_SCORE) {
+        if (ends_free) return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
+        if (!b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: POA_MODE_SCORE needs a batch created by poa_batch_create_ex with that mode");
+        return run_sweep(b, costs->mismatch, costs->gap_open, costs->gap_extend, T, (hipStream_t)stream_v);
+    }
+    if (b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: the batch was created for POA_MODE_SCORE (it holds no score planes)");
     if (ends_free) {
         if (cfg->qry_free_end.kind > POA_BOUND_EXCLUDED || cfg->graph_free_begin.kind > POA_BOUND_EXCLUDED ||
             cfg->graph_free_end.kind > POA_BOUND_EXCLUDED || cfg->qry_free_begin.kind > POA_BOUND_EXCLUDED)
@@ -1125,7 +1272,7 @@ int poa_batch_fetch(poa_batch_t* b, uint32_t* score, poa_aln_pair_t* pairs, uint
             for (uint32_t i = 0; i < n; ++i) nf += fl[i] != 0;
             stats->n_flagged = nf;
         }
-        if (stats && b->last_mode != POA_MODE_DENSE) {
+        if (stats && (b->last_mode == POA_MODE_EXACT || b->last_mode == POA_MODE_HYBRID)) {
             std::vector<uint32_t> stt(n);
             HIP_TRY(hipMemcpy(stt.data(), b->d_ex_status.p, (size_t)n * 4, hipMemcpyDeviceToHost));
             uint32_t ne = 0;
@@ -1160,7 +1307,7 @@ int poa_batch_stats(poa_batch_t* b, poa_stats_t* stats) {
 
 int poa_batch_fetch_search_counters(poa_batch_t* b, uint32_t* out) {
     if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: null argument");
-    if (!b->ran || b->last_mode == POA_MODE_DENSE || !b->d_ex_counters.p)
+    if (!b->ran || b->last_mode == POA_MODE_DENSE || b->last_mode == POA_MODE_SCORE || !b->d_ex_counters.p)
         return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: the last run was not an exact / hybrid run");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->last_stream));
@@ -1206,6 +1353,7 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
     if (!b || !m || !i || !d) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes: null argument");
     if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes: bad query / not run");
     if (b->compact) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: the last run used the compact layout; run with POA_CFG_FULL_PLANES");
+    if (b->sweep) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: a score-only batch keeps no score planes");
     if (b->last_mode != POA_MODE_DENSE) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: after an exact / hybrid run the workspace holds the replayed search's tiled table");
     const auto& last = b->cur().chunks.back();
     if (query < last.first || query >= last.first + last.count)
@@ -1239,6 +1387,23 @@ void poa_batch_destroy(poa_batch_t* b) {
     delete b;
 }
 
+// one-shot score-only call: a batch sized from the slot footprint, one run, scores and flags back; pair_off all zero.
+// First version: it creates and destroys a whole resident batch per call (device tables, events, a workspace that is reused
+// from the parked one only at exactly the same size), a fixed cost that has not been measured against the kernel's few
+// milliseconds; a host that screens many small batches keeps a batch per shape (poa_batch_create_ex) or batches more reads.
+static int sweep_one_shot(const poa_graph_t* g, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const poa_config_t* cfg,
+                          uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, uint64_t* pair_off,
+                          uint32_t* flags, poa_stats_t* stats, int device) {
+    const TuneView T(cfg);
+    poa_batch_t* b = nullptr;
+    int rc = batch_create_impl(g, device, n_queries, qseq, qoff, 0, true, &b);
+    if (rc != POA_OK) return rc;
+    rc = run_sweep(b, cost_x, cost_o, cost_e, T, nullptr);
+    if (rc == POA_OK) rc = poa_batch_fetch(b, score, nullptr, pair_off, 0, flags, stats);
+    poa_batch_destroy(b);
+    return rc;
+}
+
 int poa_align_batch(const poa_graph_t* g, const poa_costs_t* costs, uint32_t n_queries, const uint8_t* qseq,
                     const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off,
                     uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
@@ -1262,6 +1427,11 @@ int poa_align_batch_ex(const poa_graph_t* g, const poa_costs_t* costs, const poa
         if (pair_off) pair_off[n_queries] = 0;
         if (stats) { stats->n_queries = n_queries; stats->n_flagged = n_queries; }
         return POA_OK;
+    }
+    if (cfg && cfg->mode == POA_MODE_SCORE) {
+        if (cfg->span == POA_SPAN_ENDS_FREE)
+            return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
+        return sweep_one_shot(g, costs->mismatch, costs->gap_open, costs->gap_extend, cfg, n_queries, qseq, qoff, score, pair_off, flags, stats, device);
     }
     // size the workspace for the layout this run will use (2-byte elements when the dense pass can run in u16)
     uint64_t ws_hint = 0;
@@ -1338,8 +1508,11 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
     // mode: DENSE = the dense Global pass; EXACT / HYBRID = the replay of the reference's search for EVERY query (under this
     // model a dense flag of 0 certifies the alignment only where the reference's search is optimal, and it need not be:
     // DESIGN.md §6a — so there is no cheaper hybrid)
-    const bool exact = cfg && cfg->mode != POA_MODE_DENSE;
-    if (cfg && cfg->mode > POA_MODE_HYBRID) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
+    const bool score_only = cfg && cfg->mode == POA_MODE_SCORE;
+    const bool exact = cfg && cfg->mode != POA_MODE_DENSE && !score_only;
+    if (cfg && cfg->mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
+    if (score_only && cfg->span == POA_SPAN_ENDS_FREE)
+        return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown alignment span");
     const bool ends_free = cfg && cfg->span == POA_SPAN_ENDS_FREE;
     if (ends_free && !exact) return fail(POA_ERR_UNSUPPORTED, "two-piece model: ends-free alignment needs the exact replay (mode EXACT)");
@@ -1366,6 +1539,13 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
         }
         if (stats) { stats->n_queries = n_queries; stats->n_flagged = n_queries; }
         return POA_OK;
+    }
+    if (score_only) {
+        // the two-piece optimum is the one-piece optimum under open' = open1 + extend1 - extend2, extend' = extend2
+        // (a gap of length k costs open1 + extend1 + (k - 1) * extend2 at its cheapest): the same sweep, wider cost fields
+        if (pair_off) std::memset(pair_off, 0, ((size_t)n_queries + 1) * sizeof(uint64_t));
+        return sweep_one_shot(g, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
+                              n_queries, qseq, qoff, score, pair_off, flags, stats, device);
     }
     const uint32_t pitch = (uint32_t)((max_len + 64) & ~63ull);
     const uint64_t per_query = 5ull * fg.n * pitch;   // plane elements
