@@ -62,6 +62,14 @@ extern "C" {
                                are not evaluated and stay clear.  Global only: with POA_SPAN_ENDS_FREE every entry point
                                returns POA_ERR_UNSUPPORTED.  heuristic and pruning are ignored.  A resident batch must be
                                created for it (poa_batch_create_ex) and runs in no other mode. */
+#define POA_MODE_CHECKPOINT 4u /* dense mode's results — score[], pairs, pair_off, flags, bit for bit — from a slot-sized workspace:
+                               the rows are cut into segments (poa_graph_checkpoint_plan); a forward sweep keeps, besides its live
+                               rows, a snapshot of the rows each later segment still reads, and a second pass recomputes one segment
+                               at a time into a window and walks the traceback through it, last segment first.  A query holds
+                               rows_per_query x pitch cells instead of 3 x rows x pitch, at the price of a second forward pass.
+                               One-piece model, Global only: POA_SPAN_ENDS_FREE and poa_align_batch_2piece_ex return
+                               POA_ERR_UNSUPPORTED, as does poa_batch_fetch_planes.  heuristic and pruning are ignored.  A resident
+                               batch must be created for it (poa_batch_create_ex) and runs in no other mode. */
 #define POA_HEURISTIC_DIJKSTRA 0u /* AffineDijkstra   (src/aligner/config.rs:49)  */
 #define POA_HEURISTIC_MINGAP 1u   /* AffineMinGapCost (src/aligner/config.rs:104), the default of both reference CLIs */
 
@@ -136,6 +144,7 @@ enum {
     POA_TUNE_TIMING,          /* poa_align_batch: host-side timing printed to stderr */
     POA_TUNE_WS_ADAPT,        /* wave replay: entries tested in the step after an expansion (0: always WS_LANES) */
     POA_TUNE_WS_REC,          /* 0: the wave replay's one-round-trip path reads the graph arrays instead of the per-row records */
+    POA_TUNE_CKPT_ROWS,       /* checkpointed mode: rows per segment (read when the batch is created; 0 / unset: the engine's choice) */
     POA_TUNE_COUNT = 32
 };
 
@@ -220,6 +229,14 @@ uint32_t poa_graph_rows(const poa_graph_t* g);           /* == n */
  * A row has a slot iff some successor is not the chain row directly below it; it is live from its own row to its last
  * reader.  Host-side table, recomputed by poa_graph_update; needs no device. */
 int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot /* may be NULL */, uint32_t* n_slots);
+/* segment plan of the checkpointed mode (POA_MODE_CHECKPOINT): the rows are cut into *n_segments segments of segment_rows rows
+ * (0: the engine's choice — the length that holds the fewest rows; a graph of a few rows is one segment), boundary[0] = 0 <
+ * ... < boundary[*n_segments] = rows.  The snapshot of a boundary b > 0 holds every row < b that has a sweep slot and a reader
+ * >= b, plus row b - 1 if row b takes it from registers in the sweep (its only predecessor).  *rows_per_query = plane rows (of
+ * `pitch` cells) a query holds: 2 x n_slots (the sweep's live rows, M and D) + 2 x the snapshot rows of all boundaries + 3 x
+ * the longest segment (the window: M, I, D).  Host-side table, recomputed by poa_graph_update; needs no device. */
+int poa_graph_checkpoint_plan(const poa_graph_t* g, uint32_t segment_rows /* 0: engine's choice */, uint32_t* n_segments,
+                              uint32_t* boundary /* may be NULL, [*n_segments + 1] */, uint32_t* rows_per_query);
 /* row (topological rank used for the score planes) of every node; rank[n] */
 int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank);
 
@@ -290,7 +307,12 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
  * full planes, is chunked by that footprint (a batch that fits runs as one chunk) and has no pair buffers.  Besides the slots
  * it holds, only when some query is longer than 1024 columns, the carries between strips: 16 bytes per graph row and query
  * in flight (not part of poa_batch_workspace_bytes).  The one-shot calls create and destroy such a batch per call.  Running it in
- * another mode, or a batch of poa_batch_create in POA_MODE_SCORE, returns POA_ERR_INVALID_ARG. */
+ * another mode, or a batch of poa_batch_create in POA_MODE_SCORE, returns POA_ERR_INVALID_ARG.
+ * A batch created for POA_MODE_CHECKPOINT holds rows_per_query x pitch 4-byte cells per query (poa_graph_checkpoint_plan at
+ * cfg->tune[POA_TUNE_CKPT_ROWS]; + 256 bytes of padding) and is chunked by that footprint; the cell width of a run follows
+ * from its costs, after the batch exists, so it is sized for u32 cells and a u16 run packs twice the queries into a chunk when
+ * the batch needs chunks at all.  Pair buffers as in dense mode, carries between strips as in score mode.  The same rule on
+ * modes: it runs in POA_MODE_CHECKPOINT only, and no other batch runs in that mode (POA_ERR_INVALID_ARG). */
 int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq,
                         const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out);
 /* bytes of the plane workspace the batch holds */

@@ -22,7 +22,7 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_graph_rows", "poa_graph_node_rows", "poa_graph_update", "poa_align_batch", "poa_align_batch_ex", "poa_align_batch_2piece", "poa_align_batch_2piece_ex", "poa_planes_2piece", "poa_release_cache", "poa_batch_create", "poa_batch_run",
            "poa_batch_run_ex",
            "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_fetch_planes", "poa_batch_destroy",
-           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes"]
+           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan"]
 
 
 class PoaCosts2(C.Structure):
@@ -48,7 +48,7 @@ class PoaConfig(C.Structure):
 # sweep set POA_<NAME> and this binding copies them into the config of every call (tune_from_env).
 TUNE_KEYS = ("PLANES", "COMPACT", "PACKED", "RELATIVE", "PX", "MF", "MW", "PXMW", "FWD_QUADS", "FUSE_TB", "TB_GROUP", "TB_DEPTH",
              "EXACT_IMPL", "EXACT_LANES", "EXACT_LDS", "WS_LANES", "WS_GROUP", "WS_WAVES", "WS_RING_GLOBAL", "WS_STATIC",
-             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC")
+             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC", "CKPT_ROWS")
 EXACT_IMPLS = {"lane": 1, "wave": 2, "flat": 3}
 
 
@@ -74,7 +74,7 @@ BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED = 0, 1, 2
 SPAN_GLOBAL, SPAN_ENDS_FREE = 0, 1
 
 
-MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE = 0, 1, 2, 3
+MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE, MODE_CHECKPOINT = 0, 1, 2, 3, 4
 HEURISTIC_DIJKSTRA, HEURISTIC_MINGAP = 0, 1
 FLAG_EXACT_OVERFLOW = 0x40
 CFG_FULL_PLANES = 1
@@ -148,6 +148,8 @@ def lib():
     L.poa_batch_create.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint64, C.POINTER(vp)]
     L.poa_graph_sweep_slots.restype = C.c_int
     L.poa_graph_sweep_slots.argtypes = [vp, vp, vp]
+    L.poa_graph_checkpoint_plan.restype = C.c_int
+    L.poa_graph_checkpoint_plan.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.poa_batch_create_ex.restype = C.c_int
     L.poa_batch_create_ex.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.POINTER(PoaConfig), C.c_uint64, C.POINTER(vp)]
     L.poa_batch_workspace_bytes.restype = C.c_int

@@ -153,14 +153,17 @@ class AffineDijkstra(AffineMinGapCost):
     heuristic = _lib.HEURISTIC_DIJKSTRA
 
 
-MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE_HYBRID, "score": _lib.MODE_SCORE}
+MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE_HYBRID, "score": _lib.MODE_SCORE,
+         "checkpoint": _lib.MODE_CHECKPOINT}
 
 
 def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, queue_entries_per_cell=0.0, full_planes=False,
                 aln_type=AlignmentType.Global, **tune):
     """poa_config_t: `mode` "dense" | "exact" (replay the reference's A* for every query: bit-identical
     tie-breaks) | "hybrid" (replay only the queries the dense pass could not certify) | "score" (forward sweep only: dense
-    mode's scores, no alignment, memory for the live rows only); `aln_type` Global or EndsFree(...)."""
+    mode's scores, no alignment, memory for the live rows only) | "checkpoint" (dense mode's results from a slot-sized
+    workspace: sweep with snapshots, then recompute-and-walk per segment; ckpt_rows=k overrides the segment length);
+    `aln_type` Global or EndsFree(...)."""
     cfg = _lib.PoaConfig(MODES[mode] if isinstance(mode, str) else int(mode), int(heuristic), 1 if pruning else 0,
                          float(queue_entries_per_cell), _lib.CFG_FULL_PLANES if full_planes else 0)
     if isinstance(aln_type, EndsFree):
@@ -251,6 +254,15 @@ class DeviceGraph:
         _lib.check(_lib.lib().poa_graph_sweep_slots(self.handle, _p(slot), C.byref(n)))
         return slot[:self.graph.n], int(n.value)
 
+    def checkpoint_plan(self, segment_rows=0):
+        """(boundary, rows_per_query) of the checkpointed mode: boundary[0] = 0 < ... < boundary[-1] = rows cut the rows into
+        segments of segment_rows rows (0: the engine's choice); rows_per_query = plane rows of `pitch` cells a query holds."""
+        n_seg, rpq = C.c_uint32(0), C.c_uint32(0)
+        _lib.check(_lib.lib().poa_graph_checkpoint_plan(self.handle, int(segment_rows), C.byref(n_seg), None, C.byref(rpq)))
+        boundary = np.zeros(n_seg.value + 1, np.uint32)
+        _lib.check(_lib.lib().poa_graph_checkpoint_plan(self.handle, int(segment_rows), C.byref(n_seg), _p(boundary), C.byref(rpq)))
+        return boundary, int(rpq.value)
+
     def __del__(self):
         try:
             if self.handle:
@@ -277,8 +289,8 @@ class ResidentBatch:
     """Queries + results resident in HBM (`poa_batch_*`): create once, run many times."""
 
     def __init__(self, graph, qseq, qoff, device=0, workspace_bytes=0, config=None):
-        """config: the poa_config_t the batch will run with — needed for mode "score", whose batch holds slots instead of
-        planes (poa_batch_create_ex) and runs in no other mode."""
+        """config: the poa_config_t the batch will run with — needed for modes "score" and "checkpoint", whose batches hold
+        slots (and snapshots and a segment window) instead of planes (poa_batch_create_ex) and run in no other mode."""
         self.dg = _device_graph(graph)
         self.qseq = np.ascontiguousarray(qseq, np.uint8)
         self.qoff = np.ascontiguousarray(qoff, np.uint64)

@@ -34,6 +34,7 @@ struct TuneView {
 #include "poa_twopiece.hpp"
 #include "poa_sweep_rows.hpp"
 #include "poa_forward_sweep.hpp"
+#include "poa_checkpoint.hpp"
 
 using namespace poa_amd;
 
@@ -173,6 +174,7 @@ void PlaneWorkspace::release() {
 struct poa_graph {
     FlatGraph g;
     SweepRows sweep;        // row liveness / slots of the score-only sweep (poa_sweep_rows.hpp), rebuilt with g
+    CheckpointPlan ckpt;    // segment plan of the checkpointed mode at the engine's own segment length, rebuilt with g
     std::mutex bubble_mu;   // the bubble index (exact / hybrid mode only) is built on first use; batches on other threads may share the handle
 };
 
@@ -239,6 +241,12 @@ struct poa_batch {
     uint32_t sweep_slots = 1;          // max(n_sweep_slots, 1)
     uint64_t sweep_slotted = 0;        // rows per query that are stored at all
     uint64_t sweep_bytes_written = 0;  // slot bytes the last score-only run stored (poa_stats_t.plane_bytes)
+    // checkpointed batch (poa_batch_create_ex with POA_MODE_CHECKPOINT): per query the sweep's slots, the snapshots and one
+    // segment window (poa_checkpoint.hpp); d_dslot / d_pred_dslot hold SweepRows::slot / pred_slot; pair buffers as in dense mode
+    bool ckpt = false;
+    CheckpointPlan ckpt_plan;          // the plan the batch was sized for (POA_TUNE_CKPT_ROWS at creation, else the graph's own)
+    uint32_t ckpt_slots = 0;
+    DevBuf<uint32_t> d_ck_snap_off, d_ck_snap_dst, d_ck_pred_src, d_ck_boundary;
 
     // one event set per run since the last stats call: [begin, (fwd_end, tb_end) per chunk..., end]
     std::vector<std::vector<hipEvent_t>> runs;
@@ -268,7 +276,7 @@ static int check_pipeline_error(poa_batch* b) {
 static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     const uint32_t n = b->n_queries;
     const uint32_t keep_flagged = stats->n_flagged;
-    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = b->sweep ? b->sweep_bytes_written : b->plane_bytes_total;
+    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = (b->sweep || b->ckpt) ? b->sweep_bytes_written : b->plane_bytes_total;
     stats->n_queries = n; stats->n_chunks = (uint32_t)b->cur().chunks.size();
     stats->n_flagged = keep_flagged;
     stats->ms_h2d = b->ms_h2d; stats->ms_d2h = 0.f;
@@ -345,6 +353,7 @@ int poa_graph_create(uint32_t n, uint32_t start, uint32_t end, const uint8_t* sy
     if (rc != POA_OK) return fail(rc, err);
     try {
         build_sweep_rows(h->g, h->sweep);
+        build_checkpoint_plan(h->g, h->sweep, 0, h->ckpt);
     } catch (const std::bad_alloc&) {
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_create: host allocation failed");
     }
@@ -361,9 +370,10 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     int rc;
     FlatGraph ng;
     SweepRows nsw;
+    CheckpointPlan nck;
     try {
         rc = build_flat_graph(n, start, end, symbol, succ_off, succ, pred_off, pred, ng, err);
-        if (rc == POA_OK) build_sweep_rows(ng, nsw);
+        if (rc == POA_OK) { build_sweep_rows(ng, nsw); build_checkpoint_plan(ng, nsw, 0, nck); }
     } catch (const std::bad_alloc&) {
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_update: host allocation failed");
     }
@@ -371,6 +381,7 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     std::lock_guard<std::mutex> lk(g->bubble_mu);
     g->g = std::move(ng);
     g->sweep = std::move(nsw);
+    g->ckpt = std::move(nck);
     return POA_OK;
 }
 
@@ -381,6 +392,22 @@ int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot, uint32_t* n_slot
     return POA_OK;
 }
 
+int poa_graph_checkpoint_plan(const poa_graph_t* g, uint32_t segment_rows, uint32_t* n_segments, uint32_t* boundary, uint32_t* rows_per_query) {
+    if (!g || !n_segments || !rows_per_query) return fail(POA_ERR_INVALID_ARG, "poa_graph_checkpoint_plan: null argument");
+    CheckpointPlan own;
+    const CheckpointPlan* pl = &g->ckpt;
+    if (segment_rows != 0 && segment_rows != g->ckpt.segment_rows) {
+        try {
+            build_checkpoint_plan(g->g, g->sweep, segment_rows, own);
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_checkpoint_plan: host allocation failed"); }
+        pl = &own;
+    }
+    *n_segments = pl->n_segments();
+    *rows_per_query = pl->rows_per_query;
+    if (boundary) std::memcpy(boundary, pl->boundary.data(), pl->boundary.size() * sizeof(uint32_t));
+    return POA_OK;
+}
+
 int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank) {
     if (!g || !rank) return fail(POA_ERR_INVALID_ARG, "poa_graph_node_rows: null argument");
     std::memcpy(rank, g->g.node_row.data(), g->g.n * sizeof(uint32_t));
@@ -388,7 +415,7 @@ int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank) {
 }
 
 static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
-                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out);
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt = false, uint32_t ckpt_rows = 0);
 
 int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                      uint64_t workspace_bytes, poa_batch_t** out) {
@@ -397,11 +424,16 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
 
 int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                         const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out) {
-    if (cfg && cfg->mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_batch_create_ex: unknown mode");
+    if (cfg && cfg->mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_create_ex: unknown mode");
     const bool sweep = cfg && cfg->mode == POA_MODE_SCORE;
     if (sweep && cfg->span == POA_SPAN_ENDS_FREE)
         return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
-    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out);
+    const bool ckpt = cfg && cfg->mode == POA_MODE_CHECKPOINT;
+    if (ckpt && cfg->span == POA_SPAN_ENDS_FREE)
+        return fail(POA_ERR_UNSUPPORTED, "checkpointed mode is Global: an ends-free result is defined by the reference's search");
+    uint32_t ckpt_rows = 0;
+    if (ckpt) { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) ckpt_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
+    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out, ckpt, ckpt_rows);
 }
 
 int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
@@ -411,7 +443,7 @@ int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
 }
 
 static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
-                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out) {
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt, uint32_t ckpt_rows) {
     if (!out) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: out is null");
     *out = nullptr;
     if (!g || !qoff || (n_queries && qoff[n_queries] && !qseq))
@@ -433,7 +465,13 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     b->sweep = sweep;
     b->sweep_slots = std::max<uint32_t>(g->sweep.n_slots, 1u);
     b->sweep_slotted = g->sweep.n_slotted;
+    b->ckpt = ckpt;
+    b->ckpt_slots = g->sweep.n_slots;
     try {
+        if (ckpt) {
+            if (ckpt_rows == 0 || ckpt_rows == g->ckpt.segment_rows) b->ckpt_plan = g->ckpt;
+            else build_checkpoint_plan(fg, g->sweep, ckpt_rows, b->ckpt_plan);
+        }
         b->h_qoff.assign(qoff, qoff + n_queries + 1);
         b->h_pitch.resize(n_queries);
         b->h_scratch_off.resize((size_t)n_queries + 1);
@@ -447,7 +485,8 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
         const uint32_t pitch = (uint32_t)(((L + 1 + 63) / 64) * 64);
         b->h_pitch[i] = pitch;
         // score-only: n_sweep_slots rows of M and of D (4-byte cells: what the widest layout needs; u16 runs use half of it)
-        q_plane_elems[i] = sweep ? 2ull * b->sweep_slots * pitch : 3ull * rows * pitch;
+        // checkpointed: slots + snapshots + one segment window (CheckpointPlan::rows_per_query rows), sized for 4-byte cells too
+        q_plane_elems[i] = sweep ? 2ull * b->sweep_slots * pitch : (ckpt ? (uint64_t)b->ckpt_plan.rows_per_query * pitch : 3ull * rows * pitch);
         b->h_scratch_off[i] = scratch_total;
         if (!sweep) scratch_total += L + rows;   // (no pairs, no traceback scratch)
         b->max_len = std::max<uint64_t>(b->max_len, L);
@@ -462,7 +501,7 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // score-only: the carries between strips (two parities x two words per row and query in flight, poa_forward_sweep.hpp) exist
     // only when some query is longer than one 1024-column strip; they are part of what the batch holds besides the slots
-    const bool sweep_carry = sweep && max_len + 1 > 1024;
+    const bool sweep_carry = (sweep || ckpt) && max_len + 1 > 1024;
     const uint64_t fixed = scratch_total * 16 + (uint64_t)n_queries * 64 + qoff[n_queries] + (64ull << 20) +
                            (sweep_carry ? 16ull * n_queries * rows : 0);
     uint64_t ws = workspace_bytes;
@@ -470,7 +509,7 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
         const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
         ws = std::min<uint64_t>(b->plane_bytes_total, avail);
     }
-    if (sweep) ws = std::min<uint64_t>(ws, b->plane_bytes_total);   // a score-only batch holds its slots, never more (workspace_bytes is a cap)
+    if (sweep || ckpt) ws = std::min<uint64_t>(ws, b->plane_bytes_total);   // such a batch holds its own footprint, never more (workspace_bytes is a cap)
     uint64_t biggest = 0;
     for (uint32_t i = 0; i < n_queries; ++i) biggest = std::max(biggest, q_plane_elems[i] * 4);
     if (ws < biggest) {
@@ -520,7 +559,8 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     };
     make_plan(b->plan[0], 4, false);
     b->plan16_same = sweep || b->plan[0].chunks.size() <= 1;
-    if (!b->plan16_same) { make_plan(b->plan[1], 2, false); make_plan(b->plan[2], 2, true); }
+    // (a checkpointed batch has no compact layout: its u16 runs take plan[1], and plan[2] is a copy of it)
+    if (!b->plan16_same) { make_plan(b->plan[1], 2, false); make_plan(b->plan[2], 2, !ckpt); }
     const uint32_t max_chunk_any = std::max(b->plan[0].max_chunk, std::max(b->plan[1].max_chunk, b->plan[2].max_chunk));
     b->cols_per_lane = 16;
 
@@ -529,8 +569,20 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(fg.pred_rows.size(), 1)));
     HIP_TRY(b->d_pred_k.alloc(std::max<size_t>(fg.pred_k.size(), 1)));
     HIP_TRY(b->d_row_depth.alloc(std::max<size_t>(fg.row_depth.size(), 1)));
-    HIP_TRY(b->d_dslot.alloc(std::max<size_t>(sweep ? g->sweep.slot.size() : fg.d_slot.size(), 1)));
-    HIP_TRY(b->d_pred_dslot.alloc(std::max<size_t>(sweep ? g->sweep.pred_slot.size() : fg.pred_dslot.size(), 1)));
+    const bool sweep_tables = sweep || ckpt;
+    HIP_TRY(b->d_dslot.alloc(std::max<size_t>(sweep_tables ? g->sweep.slot.size() : fg.d_slot.size(), 1)));
+    HIP_TRY(b->d_pred_dslot.alloc(std::max<size_t>(sweep_tables ? g->sweep.pred_slot.size() : fg.pred_dslot.size(), 1)));
+    if (ckpt) {
+        const CheckpointPlan& cp = b->ckpt_plan;
+        HIP_TRY(b->d_ck_snap_off.alloc(cp.snap_off.size()));
+        HIP_TRY(b->d_ck_snap_dst.alloc(std::max<size_t>(cp.snap_dst.size(), 1)));
+        HIP_TRY(b->d_ck_pred_src.alloc(std::max<size_t>(cp.pred_src.size(), 1)));
+        HIP_TRY(b->d_ck_boundary.alloc(cp.boundary.size()));
+        HIP_TRY(hipMemcpy(b->d_ck_snap_off.p, cp.snap_off.data(), cp.snap_off.size() * 4, hipMemcpyHostToDevice));
+        if (!cp.snap_dst.empty()) HIP_TRY(hipMemcpy(b->d_ck_snap_dst.p, cp.snap_dst.data(), cp.snap_dst.size() * 4, hipMemcpyHostToDevice));
+        if (!cp.pred_src.empty()) HIP_TRY(hipMemcpy(b->d_ck_pred_src.p, cp.pred_src.data(), cp.pred_src.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->d_ck_boundary.p, cp.boundary.data(), cp.boundary.size() * 4, hipMemcpyHostToDevice));
+    }
     HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n_queries], 1)));
     HIP_TRY(b->d_qoff.alloc((size_t)n_queries + 1));
     HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n_queries, 1)));
@@ -542,12 +594,12 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n_queries, 1)));
     HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
     HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep ? (sweep_carry ? 4ull : 0ull) : 2ull) * max_chunk_any * rows, 1)));
+    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep_tables ? (sweep_carry ? 4ull : 0ull) : 2ull) * max_chunk_any * rows, 1)));
     HIP_TRY(b->d_pipeline_error.alloc(1));
     HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
     if (n_queries) {
         std::string werr;
-        if (!b->d_planes.acquire(device, ws + 256, werr, sweep)) return fail(POA_ERR_OUT_OF_MEMORY, "score-plane workspace: " + werr);
+        if (!b->d_planes.acquire(device, ws + 256, werr, sweep_tables)) return fail(POA_ERR_OUT_OF_MEMORY, "score-plane workspace: " + werr);
     }
 
     hipEvent_t e0, e1;
@@ -561,8 +613,8 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
         HIP_TRY(hipMemcpy(b->d_pred_k.p, fg.pred_k.data(), fg.pred_k.size() * 4, hipMemcpyHostToDevice));
     if (!fg.row_depth.empty())
         HIP_TRY(hipMemcpy(b->d_row_depth.p, fg.row_depth.data(), fg.row_depth.size() * 4, hipMemcpyHostToDevice));
-    const std::vector<uint32_t>& h_slot = sweep ? g->sweep.slot : fg.d_slot;
-    const std::vector<uint32_t>& h_pred_slot = sweep ? g->sweep.pred_slot : fg.pred_dslot;
+    const std::vector<uint32_t>& h_slot = sweep_tables ? g->sweep.slot : fg.d_slot;
+    const std::vector<uint32_t>& h_pred_slot = sweep_tables ? g->sweep.pred_slot : fg.pred_dslot;
     if (!h_slot.empty())
         HIP_TRY(hipMemcpy(b->d_dslot.p, h_slot.data(), h_slot.size() * 4, hipMemcpyHostToDevice));
     if (!h_pred_slot.empty())
@@ -756,6 +808,96 @@ static int run_sweep(poa_batch* b, uint32_t cost_x, uint32_t cost_o, uint32_t co
     return POA_OK;
 }
 
+// Checkpointed run of a batch created for it: per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2);
+// scan and compaction of the pairs as in dense mode.
+static int run_ckpt(poa_batch* b, const poa_costs_t* costs, const TuneView& T, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(b->device));
+    const FlatGraph& fg = b->graph->g;
+    const CheckpointPlan& cp = b->ckpt_plan;
+    b->last_mode = POA_MODE_CHECKPOINT;
+    b->last_stream = stream;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
+    // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the result depends on is exact in them
+    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * b->max_len : 0) +
+                        (fg.min_path_nodes ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * fg.min_path_nodes : 0);
+    bool narrow = ub <= 65534;
+    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = (narrow && !b->plan16_same) ? 1 : 0;
+    const poa_batch::Plan& PL = b->cur();
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * PL.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    b->sweep_bytes_written = 0;
+    size_t ev = 1;
+    for (const auto& ch : PL.chunks) {
+        CkptParams kp;
+        kp.rows = b->d_rows.p; kp.pred_rows = b->d_pred_rows.p; kp.slot = b->d_dslot.p; kp.pred_slot = b->d_pred_dslot.p;
+        kp.snap_off = b->d_ck_snap_off.p; kp.snap_dst = b->d_ck_snap_dst.p; kp.pred_src = b->d_ck_pred_src.p; kp.boundary = b->d_ck_boundary.p;
+        kp.n_rows = fg.n; kp.n_slots = b->ckpt_slots; kp.n_snap = cp.n_snap_rows; kp.seg_rows = cp.max_segment; kp.n_segments = cp.n_segments();
+        kp.start_row = fg.start_row; kp.end_row = fg.end_row;
+        kp.first_query = ch.first; kp.n_queries = ch.count;
+        kp.qseq = b->d_qseq.p; kp.qoff = b->d_qoff.p; kp.pitch = b->d_pitch.p; kp.plane_off = PL.d_off.p;
+        kp.planes = b->d_planes.p; kp.carry = b->d_carry.p;
+        kp.cost_x = costs->mismatch; kp.cost_o = costs->gap_open; kp.cost_e = costs->gap_extend;
+        kp.scratch_off = b->d_scratch_off.p; kp.scratch = b->d_scratch.p;
+        kp.score = b->d_score.p; kp.flags = b->d_flags.p; kp.n_pairs = b->d_npairs.p;
+        uint32_t max_pitch = 0;
+        uint64_t pitch_sum = 0;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) { max_pitch = std::max(max_pitch, b->h_pitch[i]); pitch_sum += b->h_pitch[i]; }
+        // cells stored: pass 1 its slotted rows and the snapshots (M, D), pass 2 every row once (M, I, D) when the walk enters
+        // every segment, which a Global alignment does unless an edge skips one
+        b->sweep_bytes_written += (2ull * (b->sweep_slotted + cp.n_snap_rows) + 3ull * fg.n) * pitch_sum * (narrow ? 2 : 4);
+        const dim3 grid((ch.count + 3) / 4), block(256);
+#define LAUNCH_CKPT(KERNEL)                                                                              \
+    do {                                                                                                \
+        if (narrow) {                                                                                   \
+            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<1, uint16_t>), grid, block, 0, stream, kp); \
+            else hipLaunchKernelGGL((KERNEL<2, uint16_t>), grid, block, 0, stream, kp);                  \
+        } else {                                                                                        \
+            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<1, uint32_t>), grid, block, 0, stream, kp); \
+            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<2, uint32_t>), grid, block, 0, stream, kp); \
+            else hipLaunchKernelGGL((KERNEL<4, uint32_t>), grid, block, 0, stream, kp);                  \
+        }                                                                                               \
+    } while (0)
+        LAUNCH_CKPT(poa_ckpt_sweep_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        LAUNCH_CKPT(poa_ckpt_trace_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+#undef LAUNCH_CKPT
+    }
+    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
 int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream_v) { return poa_batch_run_ex(b, costs, nullptr, stream_v); }
 
 int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
@@ -763,15 +905,21 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     const TuneView T(cfg);   // what this call overrides, read once
     b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
     uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
-    if (mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
+    if (mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown alignment span");
     const bool ends_free = cfg && cfg->span == POA_SPAN_ENDS_FREE;
     if (mode == POA_MODE_SCORE) {
         if (ends_free) return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
-        if (!b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: POA_MODE_SCORE needs a batch created by poa_batch_create_ex with that mode");
+        if (!b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: POA_MODE_SCORE needs a batch created by poa_batch_create_ex with that mode");   // (a checkpointed batch included)
         return run_sweep(b, costs->mismatch, costs->gap_open, costs->gap_extend, T, (hipStream_t)stream_v);
     }
+    if (mode == POA_MODE_CHECKPOINT) {
+        if (ends_free) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode is Global: an ends-free result is defined by the reference's search");
+        if (!b->ckpt) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: POA_MODE_CHECKPOINT needs a batch created by poa_batch_create_ex with that mode");
+        return run_ckpt(b, costs, T, (hipStream_t)stream_v);
+    }
     if (b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: the batch was created for POA_MODE_SCORE (it holds no score planes)");
+    if (b->ckpt) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: the batch was created for POA_MODE_CHECKPOINT (it holds no full score planes)");
     if (ends_free) {
         if (cfg->qry_free_end.kind > POA_BOUND_EXCLUDED || cfg->graph_free_begin.kind > POA_BOUND_EXCLUDED ||
             cfg->graph_free_end.kind > POA_BOUND_EXCLUDED || cfg->qry_free_begin.kind > POA_BOUND_EXCLUDED)
@@ -1307,7 +1455,7 @@ int poa_batch_stats(poa_batch_t* b, poa_stats_t* stats) {
 
 int poa_batch_fetch_search_counters(poa_batch_t* b, uint32_t* out) {
     if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: null argument");
-    if (!b->ran || b->last_mode == POA_MODE_DENSE || b->last_mode == POA_MODE_SCORE || !b->d_ex_counters.p)
+    if (!b->ran || b->last_mode == POA_MODE_DENSE || b->last_mode == POA_MODE_SCORE || b->last_mode == POA_MODE_CHECKPOINT || !b->d_ex_counters.p)
         return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: the last run was not an exact / hybrid run");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->last_stream));
@@ -1354,6 +1502,7 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
     if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes: bad query / not run");
     if (b->compact) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: the last run used the compact layout; run with POA_CFG_FULL_PLANES");
     if (b->sweep) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: a score-only batch keeps no score planes");
+    if (b->ckpt) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: a checkpointed batch keeps snapshots and one segment window, no score planes");
     if (b->last_mode != POA_MODE_DENSE) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: after an exact / hybrid run the workspace holds the replayed search's tiled table");
     const auto& last = b->cur().chunks.back();
     if (query < last.first || query >= last.first + last.count)
@@ -1433,6 +1582,18 @@ int poa_align_batch_ex(const poa_graph_t* g, const poa_costs_t* costs, const poa
             return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
         return sweep_one_shot(g, costs->mismatch, costs->gap_open, costs->gap_extend, cfg, n_queries, qseq, qoff, score, pair_off, flags, stats, device);
     }
+    if (cfg && cfg->mode == POA_MODE_CHECKPOINT) {
+        // one-shot checkpointed call: a batch sized from the plan's footprint, one run, everything dense mode returns
+        if (cfg->span == POA_SPAN_ENDS_FREE)
+            return fail(POA_ERR_UNSUPPORTED, "checkpointed mode is Global: an ends-free result is defined by the reference's search");
+        poa_batch_t* cb = nullptr;
+        int crc = poa_batch_create_ex(g, device, n_queries, qseq, qoff, cfg, 0, &cb);
+        if (crc != POA_OK) return crc;
+        crc = poa_batch_run_ex(cb, costs, cfg, nullptr);
+        if (crc == POA_OK) crc = poa_batch_fetch(cb, score, pairs, pair_off, pair_capacity, flags, stats);
+        poa_batch_destroy(cb);
+        return crc;
+    }
     // size the workspace for the layout this run will use (2-byte elements when the dense pass can run in u16)
     uint64_t ws_hint = 0;
     {
@@ -1510,7 +1671,8 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
     // DESIGN.md §6a — so there is no cheaper hybrid)
     const bool score_only = cfg && cfg->mode == POA_MODE_SCORE;
     const bool exact = cfg && cfg->mode != POA_MODE_DENSE && !score_only;
-    if (cfg && cfg->mode > POA_MODE_SCORE) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
+    if (cfg && cfg->mode == POA_MODE_CHECKPOINT) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode: one-piece gap-affine model only");
+    if (cfg && cfg->mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
     if (score_only && cfg->span == POA_SPAN_ENDS_FREE)
         return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown alignment span");

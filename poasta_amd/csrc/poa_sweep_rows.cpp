@@ -45,4 +45,86 @@ void build_sweep_rows(const FlatGraph& g, SweepRows& out) {
     for (size_t k = 0; k < g.pred_rows.size(); ++k) out.pred_slot[k] = out.slot[g.pred_rows[k]];
 }
 
+// rows p < b of boundary b's snapshot that the slot table knows: slotted, read by some row >= b
+static inline bool snap_by_slot(const SweepRows& sw, uint32_t p, uint32_t b) {
+    return sw.slot[p] != SWEEP_NO_SLOT && sw.last_reader[p] >= b;
+}
+
+uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k) {
+    const uint32_t n = (uint32_t)g.rows.size();
+    if (n == 0) return 0;
+    if (k == 0 || k > n) k = n;
+    uint64_t snap = 0;
+    // a slotted row p lies in the snapshots of the boundaries b = i * k with p < b <= last_reader[p]
+    for (uint32_t p = 0; p < n; ++p)
+        if (sw.slot[p] != SWEEP_NO_SLOT) snap += sw.last_reader[p] / k - p / k;
+    for (uint32_t b = k; b < n; b += k)
+        if ((g.rows[b].flags & ROW_CHAIN) && !snap_by_slot(sw, b - 1, b)) snap++;
+    return 2ull * sw.n_slots + 2ull * snap + 3ull * k;
+}
+
+void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out) {
+    const uint32_t n = (uint32_t)g.rows.size();
+    out = CheckpointPlan();
+    out.snap_off.assign((size_t)n + 1, 0);
+    out.pred_src.assign(g.pred_rows.size(), 0);
+    out.boundary.assign(1, 0);
+    if (n == 0) return;
+    uint32_t k = segment_rows;
+    if (k == 0) {
+        // the sum 2 * (n_slots + 1) * S + 3 * rows / S is least at S = sqrt(1.5 * rows / (n_slots + 1)); the real snapshots are
+        // smaller than n_slots + 1 rows, so the neighbourhood of that S is searched with the real count
+        uint32_t s0 = 1;
+        while ((uint64_t)(s0 + 1) * (s0 + 1) * 2 * (sw.n_slots + 1) <= 3ull * n) ++s0;
+        k = n;
+        uint64_t best = checkpoint_rows_per_query(g, sw, n);   // one segment: full planes, the most the mode may ever hold
+        for (uint32_t s : {s0 / 2, (2 * s0) / 3, s0, s0 + s0 / 2, 2 * s0, 3 * s0}) {
+            if (s < 2 || s > n) continue;
+            const uint32_t kk = (n + s - 1) / s;
+            const uint64_t c = checkpoint_rows_per_query(g, sw, kk);
+            if (c < best) { best = c; k = kk; }
+        }
+    }
+    if (k > n) k = n;
+    out.segment_rows = k;
+    for (uint32_t b = k; b < n; b += k) out.boundary.push_back(b);
+    out.boundary.push_back(n);
+    out.max_segment = k;
+    // snapshots, boundary by boundary: position of every saved row, and per row the list of its copies
+    std::vector<std::vector<uint32_t>> dst(n);
+    std::vector<uint32_t> live;   // slotted rows < b that some row >= b may read
+    std::vector<uint32_t> pos(n, SWEEP_NO_SLOT);   // row -> snapshot row of the boundary being built
+    uint32_t next = 0, p_scan = 0;
+    for (size_t s = 1; s + 1 < out.boundary.size(); ++s) {
+        const uint32_t b = out.boundary[s], b_end = out.boundary[s + 1];
+        for (; p_scan < b; ++p_scan)
+            if (sw.slot[p_scan] != SWEEP_NO_SLOT) live.push_back(p_scan);
+        size_t w = 0;
+        for (size_t i = 0; i < live.size(); ++i)
+            if (sw.last_reader[live[i]] >= b) live[w++] = live[i];
+        live.resize(w);
+        std::vector<uint32_t> members(live);
+        if ((g.rows[b].flags & ROW_CHAIN) && !snap_by_slot(sw, b - 1, b)) members.push_back(b - 1);
+        for (uint32_t p : members) { pos[p] = next; dst[p].push_back(next); next++; }
+        for (uint32_t r = b; r < b_end; ++r) {
+            const RowMeta& m = g.rows[r];
+            for (uint32_t pe = 0; pe < m.pred_count; ++pe) {
+                const uint32_t p = g.pred_rows[m.pred_begin + pe];
+                out.pred_src[m.pred_begin + pe] = p >= b ? p - b : (CKPT_SNAP | pos[p]);
+            }
+        }
+        for (uint32_t p : members) pos[p] = SWEEP_NO_SLOT;
+    }
+    // first segment: every predecessor is in the window
+    for (uint32_t r = 0; r < out.boundary[1]; ++r) {
+        const RowMeta& m = g.rows[r];
+        for (uint32_t pe = 0; pe < m.pred_count; ++pe) out.pred_src[m.pred_begin + pe] = g.pred_rows[m.pred_begin + pe];
+    }
+    out.n_snap_rows = next;
+    for (uint32_t r = 0; r < n; ++r) out.snap_off[r + 1] = out.snap_off[r] + (uint32_t)dst[r].size();
+    out.snap_dst.reserve(next);
+    for (uint32_t r = 0; r < n; ++r) out.snap_dst.insert(out.snap_dst.end(), dst[r].begin(), dst[r].end());
+    out.rows_per_query = (uint32_t)(2ull * sw.n_slots + 2ull * next + 3ull * k);
+}
+
 }  // namespace poa_amd

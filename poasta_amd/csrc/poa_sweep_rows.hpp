@@ -29,4 +29,36 @@ struct SweepRows {
 
 void build_sweep_rows(const FlatGraph& g, SweepRows& out);
 
+// Segment plan of the checkpointed mode (POA_MODE_CHECKPOINT, poa_checkpoint.hpp).  Host code, no device needed.
+//
+// The row order is cut into segments [boundary[s], boundary[s + 1]) of segment_rows rows (the last one may be shorter).  The
+// SNAPSHOT of a boundary b > 0 is what rows >= b may still read of rows < b: every row p < b that has a sweep slot and
+// last_reader[p] >= b, plus row b - 1 if row b is a ROW_CHAIN row (the sweep hands it its predecessor in registers, so the
+// slot table does not know that reader).  Only M and D are saved: I never leaves its row.  Snapshot rows are numbered through
+// all boundaries, in boundary order; a query holds n_snap_rows rows of M and of D for them.
+//
+// Pass 1 (the sweep) stores a row into every snapshot it belongs to as it computes it: snap_off / snap_dst list those
+// snapshot rows per graph row.  Pass 2 recomputes one segment at a time into a window of max_segment rows of M, I and D and
+// reads a predecessor either from the window or from the snapshot of the segment's first boundary: pred_src says which, per
+// predecessor edge (the walk goes through the same table, so it never needs a row -> location lookup).
+constexpr uint32_t CKPT_SNAP = 0x80000000u;   // pred_src: the low bits are a snapshot row; else a row of the window
+
+struct CheckpointPlan {
+    uint32_t segment_rows = 0;         // rows per segment (the last may hold fewer)
+    uint32_t max_segment = 0;          // rows of the longest segment: the window
+    uint32_t n_snap_rows = 0;          // snapshot rows, all boundaries together
+    uint32_t rows_per_query = 0;       // 2 * n_slots + 2 * n_snap_rows + 3 * max_segment plane rows of `pitch` cells
+    std::vector<uint32_t> boundary;    // [n_segments + 1]: 0 ... rows
+    std::vector<uint32_t> snap_off;    // [n + 1] CSR by row into snap_dst
+    std::vector<uint32_t> snap_dst;    // snapshot rows a row is stored to in pass 1
+    std::vector<uint32_t> pred_src;    // [pred_rows.size()] pass 2: window row (pred - segment start), or CKPT_SNAP | snapshot row
+    uint32_t n_segments() const { return boundary.empty() ? 0u : (uint32_t)boundary.size() - 1u; }
+};
+
+// plane rows a query holds with segments of k rows (what the default plan minimises)
+uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k);
+// segment_rows 0: the engine's choice — about sqrt(1.5 * rows / (n_slots + 1)) segments, the candidate around it that
+// holds the fewest rows, and never more than one segment of all rows would
+void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out);
+
 }  // namespace poa_amd

@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
         }
         if (pos.size() < 2) throw PoastaError("need reads.fa");
         auto reads = read_sequences(pos[1]);
-        aligner::Mode m = mode == "exact" ? aligner::Mode::Exact : (mode == "hybrid" ? aligner::Mode::Hybrid : aligner::Mode::Dense);
+        aligner::Mode m = mode == "exact" ? aligner::Mode::Exact : (mode == "hybrid" ? aligner::Mode::Hybrid : (mode == "checkpoint" ? aligner::Mode::Checkpoint : aligner::Mode::Dense));
         // GapAffine::new(mismatch, extend, open) — lasagna.rs:193-197; Global is hard-coded there (:256)
         aligner::GapAffine scoring((uint8_t)mismatch, (uint8_t)extend, (uint8_t)open);
         aligner::PoastaAligner<aligner::AffineMinGapCost> al(aligner::AffineMinGapCost(scoring), aligner::AlignmentType::Global, device, m);
