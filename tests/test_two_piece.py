@@ -185,7 +185,8 @@ def test_gpu_two_piece_planes_scores_alignments(engine, oracle):
 @pytest.mark.gpu
 def test_gpu_two_piece_config2_sample(engine, oracle):
     """configs[1] shape under the CLI's two-piece example costs (-g 6,24 -e 2,1): scores and alignments equal the dense
-    restatement on a sample; chunks of the workspace are exercised by the batch size."""
+    restatement on a sample.  48 queries of about 10 MB of u16 planes each are far below the plane budget, so this is ONE chunk;
+    the chunk loop (first_query > 0) is covered by tests/test_two_piece_shapes.py::test_gpu_two_piece_chunk_loop."""
     g, (qseq, qoff) = W.config2(n_queries=48)
     al = engine.PoastaAligner(engine.Affine2PieceDijkstra(engine.GapAffine2Piece(4, 2, 6, 1, 24)))
     res = al.align_batch(g, qseq=qseq, qoff=qoff)
