@@ -320,6 +320,24 @@ int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes);
 int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream);
 /* same with a mode: cfg NULL == dense */
 int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);
+/* Two-piece affine model on a resident batch: what poa_align_batch_2piece computes — the same scores, flags and pairs, bit for
+ * bit — launched on `stream` without synchronising, results in the batch's own device buffers, so poa_batch_fetch,
+ * poa_batch_stats and poa_batch_device_results serve it as they serve poa_batch_run_ex, and one batch may alternate the two.
+ *   cfg NULL or POA_MODE_DENSE   the dense two-piece pass with its traceback and certificate; a batch of poa_batch_create.
+ *                                Cells are u16 when [open1 + extend1 * longest query] + [open1 + extend1 * shortest path] <= 65534
+ *                                and costs->wide_planes is 0, else u32.  Every query holds five planes of its OWN pitch; five u16
+ *                                planes fit the region the batch planned for it, five u32 planes get a plan of their own on the
+ *                                first such run (and, only if the longest query's do not fit, a larger workspace:
+ *                                poa_batch_workspace_bytes then grows).  No allocation, copy or host synchronisation after the
+ *                                first run of a width.
+ *   POA_MODE_SCORE               the score-only sweep under open' = open1 + extend1 - extend2, extend' = extend2; a batch created
+ *                                for POA_MODE_SCORE.
+ *   POA_MODE_EXACT / HYBRID / CHECKPOINT, POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED (the replay keeps a workspace of its own:
+ *                                poa_align_batch_2piece_ex; checkpointed mode is one-piece only).
+ * A batch created for another mode than the run's: POA_ERR_INVALID_ARG; extend1 < extend2: POA_ERR_INVALID_ARG.
+ * poa_stats_t.plane_bytes = cells x 5 x cell bytes.  Afterwards poa_batch_last_layout reports POA_LAYOUT_U16 or 0,
+ * poa_batch_fetch_planes returns POA_ERR_UNSUPPORTED and poa_batch_fetch_search_counters POA_ERR_INVALID_ARG. */
+int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream);
 int poa_batch_fetch(poa_batch_t* b, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off,
                     uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats);
 /* synchronise the stream and return the HIP-event timings accumulated over every poa_batch_run
@@ -343,6 +361,9 @@ int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);
+/* the five planes M, I1, D1, I2, D2 of query i after a dense poa_batch_run_2piece, rows x (len + 1) each — valid under the rule
+ * of poa_batch_fetch_planes: the query's chunk was the last one run, and the last run was a dense two-piece run */
+int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2);
 void poa_batch_destroy(poa_batch_t* b);
 
 #ifdef __cplusplus

@@ -384,6 +384,61 @@ private:
     float queue_entries_per_cell_;
 };
 
+// Queries and results resident in HBM (poa_batch_*): create once, run many times — stream-ordered, no host synchronisation
+// until fetch.  run() takes the one-piece costs (poa_batch_run_ex) or the two-piece costs (poa_batch_run_2piece: the dense
+// two-piece pass, Global); one batch may alternate them.
+class ResidentBatch {
+public:
+    ResidentBatch(const graphs::POAGraph& g, const std::vector<std::string>& seqs, int device = 0, uint64_t workspace_bytes = 0)
+        : n_((uint32_t)seqs.size()) {
+        std::vector<uint64_t> qoff(n_ + 1, 0);
+        std::string qseq;
+        for (uint32_t i = 0; i < n_; ++i) { qseq += seqs[i]; qoff[i + 1] = qseq.size(); }
+        cap_ = qseq.size() + (uint64_t)n_ * g.node_count_with_start_and_end() + 1;
+        if (poa_batch_create(g.device_graph(), device, n_, (const uint8_t*)qseq.data(), qoff.data(), workspace_bytes, &b_) != POA_OK)
+            throw PoastaError(std::string("poa_batch_create: ") + poa_last_error());
+    }
+    ResidentBatch(const ResidentBatch&) = delete;
+    ResidentBatch& operator=(const ResidentBatch&) = delete;
+    ~ResidentBatch() { poa_batch_destroy(b_); }
+
+    void run(const GapAffine& costs, void* stream = nullptr, const poa_config_t* cfg = nullptr) {
+        const poa_costs_t c{costs.mismatch(), costs.gap_open(), costs.gap_extend(), 0};
+        if (poa_batch_run_ex(b_, &c, cfg, stream) != POA_OK) throw PoastaError(std::string("poa_batch_run_ex: ") + poa_last_error());
+    }
+    void run(const GapAffine2Piece& costs, void* stream = nullptr, const poa_config_t* cfg = nullptr) {
+        poa_costs2_t c{};
+        c.mismatch = costs.mismatch(); c.gap_open1 = costs.gap_open(); c.gap_extend1 = costs.gap_extend();
+        c.gap_open2 = costs.gap_open2(); c.gap_extend2 = costs.gap_extend2();
+        if (poa_batch_run_2piece(b_, &c, cfg, stream) != POA_OK) throw PoastaError(std::string("poa_batch_run_2piece: ") + poa_last_error());
+    }
+    // synchronises the stream of the last run and copies its results to the host
+    std::vector<AstarResult> fetch(poa_stats_t* stats = nullptr) {
+        std::vector<uint32_t> score(n_), flags(n_);
+        std::vector<uint64_t> pair_off(n_ + 1, 0);
+        std::vector<poa_aln_pair_t> pairs(cap_);
+        if (poa_batch_fetch(b_, score.data(), pairs.data(), pair_off.data(), cap_, flags.data(), stats) != POA_OK)
+            throw PoastaError(std::string("poa_batch_fetch: ") + poa_last_error());
+        std::vector<AstarResult> out(n_);
+        for (uint32_t i = 0; i < n_; ++i) {
+            out[i].score = score[i]; out[i].flags = flags[i];
+            for (uint64_t k = pair_off[i]; k < pair_off[i + 1]; ++k) {
+                AlignedPair ap;
+                if (pairs[k].rpos != POA_NONE) ap.rpos = pairs[k].rpos;
+                if (pairs[k].qpos != POA_NONE) ap.qpos = pairs[k].qpos;
+                out[i].alignment.push_back(ap);
+            }
+        }
+        return out;
+    }
+    poa_batch_t* handle() const { return b_; }
+
+private:
+    poa_batch_t* b_ = nullptr;
+    uint32_t n_;
+    uint64_t cap_ = 0;
+};
+
 }  // namespace aligner
 
 // =====================================================================================================

@@ -306,7 +306,13 @@ class ResidentBatch:
         self.pair_capacity = int(self.qoff[-1]) + self.n * self.dg.graph.n
 
     def run(self, costs, stream=None, config=None):
+        """Launch on `stream` without synchronising.  costs: GapAffine (poa_batch_run_ex) or GapAffine2Piece
+        (poa_batch_run_2piece: the dense two-piece pass, or the score-only sweep on a batch created for mode "score")."""
         c = costs._c()
+        if isinstance(costs, GapAffine2Piece):
+            _lib.check(_lib.lib().poa_batch_run_2piece(self.handle, C.byref(c), C.byref(config) if config is not None else None,
+                                                       C.c_void_p(stream or 0)))
+            return
         if config is None:
             config = _lib.tune_from_env()   # (a dense-mode config carrying the overrides, if any are set)
         if config is None:
@@ -386,6 +392,14 @@ class ResidentBatch:
         m, i, d = (np.zeros((rows, cols), np.uint32) for _ in range(3))
         _lib.check(_lib.lib().poa_batch_fetch_planes(self.handle, query, _p(m), _p(i), _p(d)))
         return m, i, d
+
+    def planes_2piece(self, query):
+        """M, I1, D1, I2, D2 of one query after a dense two-piece run, rows = topological rank (its chunk must be the last one run)."""
+        rows = self.dg.graph.n
+        cols = int(self.qoff[query + 1] - self.qoff[query]) + 1
+        out = [np.zeros((rows, cols), np.uint32) for _ in range(5)]
+        _lib.check(_lib.lib().poa_batch_fetch_planes_2piece(self.handle, query, *[_p(a) for a in out]))
+        return out
 
     def close(self):
         if getattr(self, "handle", None):

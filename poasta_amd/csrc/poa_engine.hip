@@ -196,7 +196,11 @@ struct poa_batch {
         uint32_t max_chunk = 0;
         DevBuf<uint64_t> d_off;
     };
-    Plan plan[3];
+    // plan[3]: 4-byte elements, five full planes (u32 run of the two-piece model, poa_batch_run_2piece) — built on first use;
+    // the five u16 planes of a two-piece run fit a query's region of plan[0] (2.5 of its 3 x rows x pitch elements)
+    Plan plan[4];
+    uint64_t plan_ws = 0;            // bytes of workspace the plans were cut for
+    bool two_piece = false;          // the last run was a dense two-piece run (five planes in the workspace)
     bool plan16_same = true;         // plan[1], plan[2] not built: everything fits in one chunk anyway
     int active_plan = 0;             // plan of the last run
     const Plan& cur() const { return plan[active_plan]; }
@@ -276,7 +280,7 @@ static int check_pipeline_error(poa_batch* b) {
 static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     const uint32_t n = b->n_queries;
     const uint32_t keep_flagged = stats->n_flagged;
-    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = (b->sweep || b->ckpt) ? b->sweep_bytes_written : b->plane_bytes_total;
+    stats->cells = b->total_cells; stats->bases = b->total_bases; stats->plane_bytes = (b->sweep || b->ckpt) ? b->sweep_bytes_written : (b->two_piece ? b->total_cells * 5 * (b->narrow ? 2 : 4) : b->plane_bytes_total);
     stats->n_queries = n; stats->n_chunks = (uint32_t)b->cur().chunks.size();
     stats->n_flagged = keep_flagged;
     stats->ms_h2d = b->ms_h2d; stats->ms_d2h = 0.f;
@@ -324,6 +328,45 @@ static uint32_t mw_waves(uint32_t strips) {
 static bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch) {
     if (const int* v = T.ptr(POA_TUNE_PXMW)) return (*v) != 0;
     return (uint64_t)count * ((max_pitch + 1023) / 1024) >= 1024;
+}
+
+// Greedy chunking of the queries over `ws` bytes of workspace (elems_of(i) elements of elem_bytes each), with the chunks evened
+// out: the forward kernels that take a workgroup per query finish with their most loaded CU, so 2 000 queries that fit 527 at
+// a time run as 4 x 500, not 3 x 527 + 419 (measured on configs[4]: 434 -> 320 ms).
+template <typename ElemsOf>
+static void build_chunk_plan(poa_batch::Plan& pl, uint32_t n_queries, uint64_t ws, uint64_t elem_bytes, ElemsOf elems_of) {
+    auto need_of = [&](uint32_t i) { return (uint64_t)elems_of(i) * elem_bytes; };
+    auto greedy = [&](uint64_t budget, std::vector<poa_batch::Chunk>& chunks, std::vector<uint64_t>& off) {
+        chunks.clear();
+        off.assign(n_queries, 0);
+        uint32_t first = 0;
+        uint64_t used = 0;
+        for (uint32_t i = 0; i < n_queries; ++i) {
+            const uint64_t need = need_of(i);
+            if (used + need > budget && i > first) {
+                chunks.push_back({first, i - first});
+                first = i; used = 0;
+            }
+            off[i] = used / elem_bytes;
+            used += need;
+        }
+        if (n_queries > first) chunks.push_back({first, n_queries - first});
+    };
+    greedy(ws, pl.chunks, pl.off);
+    if (pl.chunks.size() > 1) {
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < n_queries; ++i) total += need_of(i);
+        const uint64_t target = (total + pl.chunks.size() - 1) / pl.chunks.size();
+        std::vector<poa_batch::Chunk> c2;
+        std::vector<uint64_t> o2;
+        for (double slack : {1.0, 1.02, 1.05, 1.1}) {
+            const uint64_t budget = std::min<uint64_t>(ws, (uint64_t)((double)target * slack));
+            greedy(budget, c2, o2);
+            if (c2.size() == pl.chunks.size()) { pl.chunks = c2; pl.off = o2; break; }
+        }
+    }
+    pl.max_chunk = 0;
+    for (auto& c : pl.chunks) pl.max_chunk = std::max(pl.max_chunk, c.count);
 }
 
 extern "C" {
@@ -519,44 +562,13 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
             ws = biggest;
         }
     }
-    // Greedy chunking, once per layout — with the chunks evened out: the forward kernels that take a workgroup per query
-    // finish with their most loaded CU, so 2 000 queries that fit 527 at a time run as 4 x 500, not 3 x 527 + 419
-    // (measured on configs[4]: 434 -> 320 ms).
+    // chunking, once per layout (build_chunk_plan)
     auto make_plan = [&](poa_batch::Plan& pl, uint64_t elem_bytes, bool compact_size) {
-        auto need_of = [&](uint32_t i) {
-            return (compact_size ? compact_plane_elems(rows, b->h_pitch[i], fg.n_store_d) : q_plane_elems[i]) * elem_bytes;
-        };
-        auto greedy = [&](uint64_t budget, std::vector<poa_batch::Chunk>& chunks, std::vector<uint64_t>& off) {
-            chunks.clear();
-            off.assign(n_queries, 0);
-            uint32_t first = 0;
-            uint64_t used = 0;
-            for (uint32_t i = 0; i < n_queries; ++i) {
-                const uint64_t need = need_of(i);
-                if (used + need > budget && i > first) {
-                    chunks.push_back({first, i - first});
-                    first = i; used = 0;
-                }
-                off[i] = used / elem_bytes;
-                used += need;
-            }
-            if (n_queries > first) chunks.push_back({first, n_queries - first});
-        };
-        greedy(ws, pl.chunks, pl.off);
-        if (pl.chunks.size() > 1) {
-            uint64_t total = 0;
-            for (uint32_t i = 0; i < n_queries; ++i) total += need_of(i);
-            const uint64_t target = (total + pl.chunks.size() - 1) / pl.chunks.size();
-            std::vector<poa_batch::Chunk> c2;
-            std::vector<uint64_t> o2;
-            for (double slack : {1.0, 1.02, 1.05, 1.1}) {
-                const uint64_t budget = std::min<uint64_t>(ws, (uint64_t)((double)target * slack));
-                greedy(budget, c2, o2);
-                if (c2.size() == pl.chunks.size()) { pl.chunks = c2; pl.off = o2; break; }
-            }
-        }
-        for (auto& c : pl.chunks) pl.max_chunk = std::max(pl.max_chunk, c.count);
+        build_chunk_plan(pl, n_queries, ws, elem_bytes, [&](uint32_t i) {
+            return compact_size ? compact_plane_elems(rows, b->h_pitch[i], fg.n_store_d) : q_plane_elems[i];
+        });
     };
+    b->plan_ws = ws;
     make_plan(b->plan[0], 4, false);
     b->plan16_same = sweep || b->plan[0].chunks.size() <= 1;
     // (a checkpointed batch has no compact layout: its u16 runs take plan[1], and plan[2] is a copy of it)
@@ -736,6 +748,7 @@ static int run_sweep(poa_batch* b, uint32_t cost_x, uint32_t cost_o, uint32_t co
     const poa_graph* gh = b->graph;
     const FlatGraph& fg = gh->g;
     b->last_mode = POA_MODE_SCORE;
+    b->two_piece = false;
     b->last_stream = stream;
     if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
     // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the end cell depends on is exact in them
@@ -815,6 +828,7 @@ static int run_ckpt(poa_batch* b, const poa_costs_t* costs, const TuneView& T, h
     const FlatGraph& fg = b->graph->g;
     const CheckpointPlan& cp = b->ckpt_plan;
     b->last_mode = POA_MODE_CHECKPOINT;
+    b->two_piece = false;
     b->last_stream = stream;
     if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
     // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the result depends on is exact in them
@@ -935,6 +949,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         if (rc != POA_OK) return rc;
     }
     b->last_mode = mode;
+    b->two_piece = false;
     b->last_stream = stream;
     if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
     // u16 planes whenever every value that can matter fits.  u16 arithmetic saturates at 0xFFFF = INF, so every stored
@@ -1504,6 +1519,7 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
     if (b->sweep) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: a score-only batch keeps no score planes");
     if (b->ckpt) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: a checkpointed batch keeps snapshots and one segment window, no score planes");
     if (b->last_mode != POA_MODE_DENSE) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: after an exact / hybrid run the workspace holds the replayed search's tiled table");
+    if (b->two_piece) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes: the last run was a two-piece run; its five planes come from poa_batch_fetch_planes_2piece");
     const auto& last = b->cur().chunks.back();
     if (query < last.first || query >= last.first + last.count)
         return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes: the query's planes were overwritten by a later chunk");
@@ -1522,6 +1538,156 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
         std::vector<uint16_t> tmp((size_t)rows * cols);
         const uint16_t* base = reinterpret_cast<const uint16_t*>(b->d_planes.p) + b->cur().off[query];
         for (int k = 0; k < 3; ++k) {
+            HIP_TRY(hipMemcpy2D(tmp.data(), (size_t)cols * 2, base + k * RP, (size_t)pitch * 2, (size_t)cols * 2, rows, hipMemcpyDeviceToHost));
+            for (size_t t = 0; t < tmp.size(); ++t) dst[k][t] = tmp[t] == 0xFFFFu ? 0xFFFFFFFFu : tmp[t];
+        }
+    }
+    return POA_OK;
+}
+
+// ---- two-piece model on a resident batch (kernels: poa_twopiece.hpp with TwoPieceBatchParams) ------------------------------------
+// The u32 plan of the two-piece pass, cut on the first u32 run: five planes of 4-byte cells per query.  The batch's workspace
+// was sized for three; it is replaced by a larger one only if the longest query's five planes do not fit it.
+static int prepare_two_piece_u32(poa_batch* b) {
+    const uint32_t rows = b->graph->g.n, n = b->n_queries;
+    uint64_t biggest = 0;
+    for (uint32_t i = 0; i < n; ++i) biggest = std::max<uint64_t>(biggest, 5ull * rows * b->h_pitch[i] * 4);
+    const uint64_t ws = std::max(b->plan_ws, biggest);
+    if (b->d_planes.bytes < ws + 256) {
+        if (b->ran) HIP_TRY(hipStreamSynchronize(b->last_stream));   // (an earlier run may still read the workspace given up here)
+        const size_t held = b->d_planes.bytes;
+        std::string werr;
+        if (!b->d_planes.acquire(b->device, ws + 256, werr)) {
+            std::string again;
+            (void)b->d_planes.acquire(b->device, held, again);
+            return fail(POA_ERR_OUT_OF_MEMORY, "two-piece u32 planes of the largest query: " + werr);
+        }
+    }
+    poa_batch::Plan& pl = b->plan[3];
+    try {
+        build_chunk_plan(pl, n, ws, 4, [&](uint32_t i) { return 5ull * rows * b->h_pitch[i]; });
+    } catch (const std::bad_alloc&) { pl.chunks.clear(); return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    if (pl.d_off.alloc(n) != hipSuccess) { pl.chunks.clear(); return fail(POA_ERR_OUT_OF_MEMORY, "two-piece u32 plan: device allocation failed"); }
+    if (hipMemcpy(pl.d_off.p, pl.off.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { pl.chunks.clear(); return fail(POA_ERR_HIP, "two-piece u32 plan: upload failed"); }
+    return POA_OK;
+}
+
+int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
+    if (!b || !costs) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: null argument");
+    const uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
+    if (mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: unknown mode");
+    if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: unknown alignment span");
+    if (mode == POA_MODE_EXACT || mode == POA_MODE_HYBRID)
+        return fail(POA_ERR_UNSUPPORTED, "poa_batch_run_2piece: the replay of the reference's two-piece search keeps a workspace of its own (poa_align_batch_2piece_ex)");
+    if (mode == POA_MODE_CHECKPOINT) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode: one-piece gap-affine model only");
+    if (cfg && cfg->span == POA_SPAN_ENDS_FREE)
+        return fail(POA_ERR_UNSUPPORTED, "two-piece model: ends-free alignment needs the exact replay (poa_align_batch_2piece_ex, mode EXACT)");
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    const TuneView T(cfg);
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (mode == POA_MODE_SCORE) {
+        if (!b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: POA_MODE_SCORE needs a batch created by poa_batch_create_ex with that mode");
+        // the two-piece optimum is the one-piece optimum under open' = open1 + extend1 - extend2, extend' = extend2
+        return run_sweep(b, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, T, stream);
+    }
+    if (b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: the batch was created for POA_MODE_SCORE (it holds no score planes)");
+    if (b->ckpt) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: the batch was created for POA_MODE_CHECKPOINT (it holds no full score planes)");
+    HIP_TRY(hipSetDevice(b->device));
+    const FlatGraph& fg = b->graph->g;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
+    // cell width: the rule of run_two_piece (the first piece's costs bound the optimum; wide_planes forces u32)
+    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * b->max_len : 0) +
+                        (fg.min_path_nodes ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * fg.min_path_nodes : 0);
+    const bool narrow = ub <= 65534 && !costs->wide_planes;
+    if (!narrow && b->n_queries && b->plan[3].chunks.empty()) {
+        const int rc = prepare_two_piece_u32(b);
+        if (rc != POA_OK) return rc;
+    }
+    b->last_mode = POA_MODE_DENSE;
+    b->two_piece = true;
+    b->last_stream = stream;
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    // u16: five 2-byte planes inside the query's region of the 4-byte plan (2.5 of its 3 x rows x pitch elements)
+    b->active_plan = narrow ? 0 : 3;
+    const poa_batch::Plan& PL = b->cur();
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * PL.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    TwoPieceBatchParams P;
+    P.rows = b->d_rows.p; P.pred_rows = b->d_pred_rows.p; P.n_rows = fg.n; P.start_row = fg.start_row; P.end_row = fg.end_row;
+    P.qseq = b->d_qseq.p; P.qoff = b->d_qoff.p; P.pitch = 0; P.planes = b->d_planes.p;
+    P.x = costs->mismatch; P.o1 = costs->gap_open1; P.e1 = costs->gap_extend1; P.e2 = costs->gap_extend2;
+    P.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
+    P.score = b->d_score.p; P.flags = b->d_flags.p; P.n_pairs = b->d_npairs.p;
+    P.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p); P.scratch_stride = 0;
+    P.exact_pass = 0; P.ex_status = nullptr; P.ex_end = nullptr;
+    P.q_pitch = b->d_pitch.p; P.plane_off = PL.d_off.p; P.off_scale = narrow ? 2u : 1u; P.scratch_off = b->d_scratch_off.p;
+    size_t ev = 1;
+    for (const auto& ch : PL.chunks) {
+        P.first_query = ch.first; P.n_queries = ch.count;
+        // one wave per query, previous row in registers for up to 1024 columns: the launch shapes of run_two_piece
+        if (narrow) hipLaunchKernelGGL((poa2_forward_kernel<uint16_t, 2, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL((poa2_forward_kernel<uint32_t, 4, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (narrow) hipLaunchKernelGGL((poa2_traceback_kernel<uint16_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL((poa2_traceback_kernel<uint32_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+    }
+    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
+int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2) {
+    if (!b || !m || !i1 || !d1 || !i2 || !d2) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: null argument");
+    if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: bad query / not run");
+    if (!b->two_piece) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the last run was not a dense two-piece run");
+    const auto& last = b->cur().chunks.back();
+    if (query < last.first || query >= last.first + last.count)
+        return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the query's planes were overwritten by a later chunk");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const uint32_t rows = b->graph->g.n, pitch = b->h_pitch[query];
+    const uint32_t cols = (uint32_t)(b->h_qoff[query + 1] - b->h_qoff[query]) + 1;
+    const uint64_t RP = (uint64_t)rows * pitch;
+    uint32_t* dst[5] = {m, i1, d1, i2, d2};
+    if (!b->narrow) {
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t* src = b->d_planes.p + b->cur().off[query] + k * RP;
+            HIP_TRY(hipMemcpy2D(dst[k], (size_t)cols * 4, src, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost));
+        }
+    } else {
+        std::vector<uint16_t> tmp((size_t)rows * cols);
+        const uint16_t* base = reinterpret_cast<const uint16_t*>(b->d_planes.p) + 2 * b->cur().off[query];   // (the 4-byte plan's offset)
+        for (int k = 0; k < 5; ++k) {
             HIP_TRY(hipMemcpy2D(tmp.data(), (size_t)cols * 2, base + k * RP, (size_t)pitch * 2, (size_t)cols * 2, rows, hipMemcpyDeviceToHost));
             for (size_t t = 0; t < tmp.size(); ++t) dst[k][t] = tmp[t] == 0xFFFFu ? 0xFFFFFFFFu : tmp[t];
         }

@@ -44,6 +44,40 @@ struct TwoPieceParams {
     const uint32_t* ex_end;            // [2 * total] (row, offset) the search stopped at
 };
 
+// Resident batch (poa_batch_run_2piece): every query has its own pitch, its planes at plane_off[qi] of the batch's workspace and
+// its pairs at scratch_off[qi] of the batch's scratch, as the one-piece kernels take them (FwdParams / TbParams); `pitch` and
+// `scratch_stride` of the base are not read.
+struct TwoPieceBatchParams : TwoPieceParams {
+    const uint32_t* q_pitch;       // [total] columns per plane row (multiple of 64)
+    const uint64_t* plane_off;     // [total] offset of the query's five planes, in units of off_scale plane elements
+    uint32_t off_scale;            // plane elements per unit of plane_off (2: u16 planes under the batch's 4-byte plan)
+    const uint64_t* scratch_off;   // [total + 1] per-query region in `scratch` (capacity len + n_rows), written back to front
+};
+
+// where a query's planes and pairs live: fixed stride per slot of the chunk (one-shot call) / per query (resident batch)
+__device__ __forceinline__ uint32_t tp_pitch(const TwoPieceParams& P, uint32_t) { return P.pitch; }
+__device__ __forceinline__ uint32_t tp_pitch(const TwoPieceBatchParams& P, uint32_t qi) { return P.q_pitch[qi]; }
+template <typename T>
+__device__ __forceinline__ T* tp_planes(const TwoPieceParams& P, uint32_t slot, uint32_t, uint64_t plane) {
+    return reinterpret_cast<T*>(P.planes) + (uint64_t)slot * 5 * plane;
+}
+template <typename T>
+__device__ __forceinline__ T* tp_planes(const TwoPieceBatchParams& P, uint32_t, uint32_t qi, uint64_t) {
+    return reinterpret_cast<T*>(P.planes) + P.plane_off[qi] * P.off_scale;
+}
+__device__ __forceinline__ poa_aln_pair_t* tp_out(const TwoPieceParams& P, uint32_t slot, uint32_t, uint32_t& cap) {
+    cap = P.scratch_stride;
+    return P.scratch + (uint64_t)slot * P.scratch_stride;
+}
+__device__ __forceinline__ poa_aln_pair_t* tp_out(const TwoPieceBatchParams& P, uint32_t, uint32_t qi, uint32_t& cap) {
+    cap = (uint32_t)(P.scratch_off[qi + 1] - P.scratch_off[qi]);
+    return P.scratch + P.scratch_off[qi];
+}
+// pairs reported: the one-shot call keeps the walk's own count (its host side refuses one beyond the stride), a resident
+// batch clamps to the region as poa_traceback_kernel does (scan and compaction read n_pairs unchecked)
+__device__ __forceinline__ uint32_t tp_n_pairs(const TwoPieceParams&, uint32_t n_out, uint32_t) { return n_out; }
+__device__ __forceinline__ uint32_t tp_n_pairs(const TwoPieceBatchParams&, uint32_t n_out, uint32_t cap) { return n_out < cap ? n_out : cap; }
+
 // Replay of the reference's two-piece search (Affine2PieceMinGapCost / Affine2PieceDijkstra with or without pruning,
 // config.rs:160-272; astar.rs:124-226 over gap_affine_2piece.rs): the search object of poa_exact.hpp instantiated with
 // EX_AS_TWO_PIECE — the generic code, five plain u32 planes (the layout the traceback below reads), linked-list queue with
@@ -109,8 +143,8 @@ __device__ __forceinline__ uint32_t tp_scan(uint32_t v, uint32_t step, uint32_t 
 // the bytes of a kernel that lives on its stores; arithmetic is u32 in registers either way (PlaneIO widens 0xFFFF to INF).
 // NP: passes whose previous row stays in registers (rows of up to NP * 64 * K columns): a chain row — one predecessor, the
 // previous row — then reads nothing back from the planes (6 of the 16 bytes of traffic per cell with u16 planes).
-template <typename T, int NP>
-__global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
+template <typename T, int NP, typename PP = TwoPieceParams>
+__global__ __launch_bounds__(64) void poa2_forward_kernel(PP P) {
     using IO = PlaneIO<T>;
     constexpr int K = IO::K;
     constexpr uint32_t PW = 64 * K;   // columns per pass
@@ -120,8 +154,9 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* q = P.qseq + qbeg;
-    const uint64_t plane = (uint64_t)P.n_rows * P.pitch;
-    T* M = reinterpret_cast<T*>(P.planes) + (uint64_t)slot * 5 * plane;
+    const uint32_t pitch = tp_pitch(P, qi);   // (resident batch: the query's own — a pass may end inside its padding, never past it)
+    const uint64_t plane = (uint64_t)P.n_rows * pitch;
+    T* M = tp_planes<T>(P, slot, qi, plane);
     T* I1 = M + plane; T* D1 = I1 + plane; T* I2 = D1 + plane; T* D2 = I2 + plane;
     const uint32_t n_pass = (L + 1 + PW - 1) / PW;   // pitch is a multiple of 64: a pass may end inside the row's padding
     constexpr int NPA = NP > 0 ? NP : 1;
@@ -130,13 +165,13 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
     for (uint32_t r = 0; r < P.n_rows; ++r) {
         const RowMeta rm = P.rows[r];
         const bool is_end = r == P.end_row, is_start = r == P.start_row;
-        const uint64_t ro = (uint64_t)r * P.pitch;
+        const uint64_t ro = (uint64_t)r * pitch;
         uint32_t c1 = INF, c2 = INF;   // I1 / I2 entering the first column of the pass
         uint32_t cpm = INF;             // min over predecessors of M[p][first column of the pass - 1]
         const bool from_regs = keep && r > 0 && (rm.flags & ROW_CHAIN);
         auto do_pass = [&](const uint32_t ps, uint32_t (&kM)[K], uint32_t (&kD1)[K], uint32_t (&kD2)[K]) {
             const uint32_t j = ps * PW + K * lane;    // my first column
-            const bool in = j < P.pitch;              // (whole 16-byte groups lie inside or outside the plane row)
+            const bool in = j < pitch;              // (whole 16-byte groups lie inside or outside the plane row)
             uint32_t qs[K], qm;                       // q[j + k] (0 past the end: never a symbol), q[j - 1]
 #pragma unroll
             for (int k = 0; k < K; ++k) qs[k] = (j + k < L) ? (uint32_t)q[j + k] : 0u;
@@ -149,7 +184,7 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
                 for (int k = 0; k < K; ++k) { pm[k] = kM[k]; pd[k] = kD1[k]; pd2[k] = kD2[k]; }
             } else if (in)
                 for (uint32_t e = 0; e < rm.pred_count; ++e) {
-                    const uint64_t po = (uint64_t)P.pred_rows[rm.pred_begin + e] * P.pitch + j;
+                    const uint64_t po = (uint64_t)P.pred_rows[rm.pred_begin + e] * pitch + j;
                     uint32_t a[K], b[K], c[K];
                     IO::load(M + po, a); IO::load(D1 + po, b); IO::load(D2 + po, c);
 #pragma unroll
@@ -241,30 +276,32 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next rows read this one back (same wave)
     }
-    if (lane == 0) P.score[qi] = IO::get(M + (uint64_t)P.end_row * P.pitch + L);
+    if (lane == 0) P.score[qi] = IO::get(M + (uint64_t)P.end_row * pitch + L);
 }
 
 // One lane per query: the reference's two-piece backtrace on the five planes, every test of a step evaluated so that the
 // certificate (exactly one candidate, no phantom below the target of an open test) can be decided.
-template <typename T>
-__global__ __launch_bounds__(64) void poa2_traceback_kernel(TwoPieceParams P) {
+template <typename T, typename PP = TwoPieceParams>
+__global__ __launch_bounds__(64) void poa2_traceback_kernel(PP P) {
     const uint32_t slot = blockIdx.x * 64 + threadIdx.x;
     if (slot >= P.n_queries) return;
     const uint32_t qi = P.first_query + slot;
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* q = P.qseq + qbeg;
-    const uint64_t plane = (uint64_t)P.n_rows * P.pitch;
-    const T* base = reinterpret_cast<const T*>(P.planes) + (uint64_t)slot * 5 * plane;
+    const uint32_t pitch = tp_pitch(P, qi);
+    const uint64_t plane = (uint64_t)P.n_rows * pitch;
+    const T* base = tp_planes<T>(P, slot, qi, plane);
     enum : uint32_t { SM = 0, SI = 1, SD = 2, SI2 = 3, SD2 = 4 };   // plane order
     // dense pass: five planes; replayed search (u32): [row][offset][state] (ExactSearchT::cix)
     auto S = [&](uint32_t row, uint32_t j, uint32_t st) {
-        return P.exact_pass ? PlaneIO<T>::get(base + ((uint64_t)row * P.pitch + j) * 5u + st) : PlaneIO<T>::get(base + st * plane + (uint64_t)row * P.pitch + j);
+        return P.exact_pass ? PlaneIO<T>::get(base + ((uint64_t)row * pitch + j) * 5u + st) : PlaneIO<T>::get(base + st * plane + (uint64_t)row * pitch + j);
     };
     const uint32_t INF = 0xFFFFFFFFu;
-    poa_aln_pair_t* out = P.scratch + (uint64_t)slot * P.scratch_stride;
+    uint32_t cap;
+    poa_aln_pair_t* out = tp_out(P, slot, qi, cap);
     uint32_t n_out = 0, fl = 0;
-    auto emit = [&](uint32_t rpos, uint32_t qpos) { if (n_out < P.scratch_stride) out[P.scratch_stride - 1 - n_out] = poa_aln_pair_t{rpos, qpos}; n_out++; };
+    auto emit = [&](uint32_t rpos, uint32_t qpos) { if (n_out < cap) out[cap - 1 - n_out] = poa_aln_pair_t{rpos, qpos}; n_out++; };
     auto sym_eq = [&](uint32_t row, uint8_t c) { return row == P.end_row || P.rows[row].sym == c; };
     // the cell the walk starts from: (end row, L) in the dense Global pass; where the replayed search stopped otherwise
     uint32_t tb_row = P.end_row, tb_off = L;
@@ -386,7 +423,7 @@ __global__ __launch_bounds__(64) void poa2_traceback_kernel(TwoPieceParams P) {
     }
     // (a replayed table IS the reference's: its backtrace takes the first candidate, nothing to certify)
     P.flags[qi] = P.exact_pass ? (fl & (POA_FLAG_REF_PANIC | POA_FLAG_TRUNCATED)) : fl;
-    P.n_pairs[qi] = n_out;
+    P.n_pairs[qi] = tp_n_pairs(P, n_out, cap);
 }
 
 }  // namespace poa_amd

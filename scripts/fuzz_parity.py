@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised differential run (GPU box): the HIP path against the oracle on random graphs, costs and query lengths —
-dense mode vs the oracle's dense restatement (scores, alignments, flags), exact mode vs the oracle's A*.
+dense mode vs the oracle's dense restatement (scores, alignments, flags), exact mode vs the oracle's A*, the two-piece model on
+a resident batch (poa_batch_run_2piece) vs the oracle's two-piece dense pass and the one-shot call.
 Test infrastructure; prints one JSON line; non-zero exit on the first difference."""
 import argparse, json, os, sys, time
 import numpy as np
@@ -17,7 +18,7 @@ ap.add_argument("--seconds", type=float, default=240.0)
 ap.add_argument("--verbose", action="store_true")
 args = ap.parse_args()
 t0 = time.time()
-n_dense = n_exact = n_exact2 = n_cases = 0
+n_dense = n_exact = n_exact2 = n_res2 = n_cases = 0
 for seed in range(args.first, args.first + args.seeds):
     if time.time() - t0 > args.seconds:
         break
@@ -109,6 +110,37 @@ for seed in range(args.first, args.first + args.seeds):
                                   oracle=[int(D["score"][i]), int(D["flags"][i])])))
             sys.exit(1)
         n_dense += 1
+    if span is None and kind != 7:
+        # two-piece model on a resident batch: random second piece, cell width and workspace (a small one cuts chunks), two runs
+        # of one batch (u32 planes, then the width the costs give) with a one-piece run between them
+        e2r, o2r = int(rng.integers(0, e + 1)), int(rng.integers(0, 30))
+        c2 = E.GapAffine2Piece(m, e, o, e2r, o2r)
+        big = 12 * g.n * max((len(q) + 64) // 64 * 64 for q in qs)
+        rb = E.ResidentBatch(g, qseq, qoff, workspace_bytes=0 if seed % 3 == 0 else int(big * float(rng.uniform(1.0, 3.0))))
+        with O.two_piece(o2r, e2r):
+            D2 = og.dense_batch(qseq, qoff, oc, threads=8)
+        shot = E.PoastaAligner(E.Affine2PieceDijkstra(c2)).align_batch(g, qseq=qseq, qoff=qoff)
+        for wide in (True, False):
+            os.environ["POA_PLANES"] = "32" if wide else ""
+            rb.run(c2)
+            os.environ.pop("POA_PLANES")
+            r = rb.fetch()
+            nq = len(qs)
+            ok = (np.array_equal(r.score, D2["score"]) and np.array_equal(r.flags, D2["flags"]) and np.array_equal(r.score, shot.score)
+                  and np.array_equal(r.flags, shot.flags) and np.array_equal(r.pair_off, shot.pair_off)
+                  and np.array_equal(r.pairs[:int(r.pair_off[nq])], shot.pairs[:int(shot.pair_off[nq])])
+                  and all(r.raw_alignment(i) == O.batch_alignment(D2, i) for i in range(nq)))
+            if not ok:
+                print(json.dumps(dict(fail="two-piece resident", seed=seed, kind=kind, costs=costs + (o2r, e2r), wide=wide, chunks=r.stats["n_chunks"])))
+                sys.exit(1)
+            n_res2 += nq
+            if wide:
+                rb.run(E.GapAffine(m, e, o))
+                r1 = rb.fetch()
+                if not (np.array_equal(r1.score, res.score) and np.array_equal(r1.pairs[:int(r1.pair_off[nq])], res.pairs[:int(res.pair_off[nq])])):
+                    print(json.dumps(dict(fail="one-piece run between two-piece runs", seed=seed, kind=kind, costs=costs)))
+                    sys.exit(1)
+        rb.close()
     if g.n * max(len(q) for q in qs) < 400000 and kind != 5:
         heur, prune = (O.H_MINGAP, True) if seed % 3 else (O.H_DIJKSTRA, seed % 2 == 0)
         cfgc = E.AffineMinGapCost if heur == O.H_MINGAP else E.AffineDijkstra
@@ -176,4 +208,4 @@ for seed in range(args.first, args.first + args.seeds):
     n_cases += 1
     if n_cases % 100 == 0:  # keeps a long run visibly alive
         print(json.dumps(dict(progress=n_cases, seconds=round(time.time() - t0, 1))), flush=True)
-print(json.dumps(dict(ok=True, graphs=n_cases, dense_queries=n_dense, exact_queries=n_exact, two_piece_exact_queries=n_exact2, seconds=round(time.time() - t0, 1))))
+print(json.dumps(dict(ok=True, graphs=n_cases, dense_queries=n_dense, exact_queries=n_exact, two_piece_exact_queries=n_exact2, two_piece_resident_queries=n_res2, seconds=round(time.time() - t0, 1))))
