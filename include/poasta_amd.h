@@ -70,6 +70,13 @@ extern "C" {
                                One-piece model, Global only: POA_SPAN_ENDS_FREE and poa_align_batch_2piece_ex return
                                POA_ERR_UNSUPPORTED, as does poa_batch_fetch_planes.  heuristic and pruning are ignored.  A resident
                                batch must be created for it (poa_batch_create_ex) and runs in no other mode. */
+#define POA_MODE_CHECKPOINT2 5u /* the same for the two-piece model: poa_align_batch_2piece's score[], pairs, pair_off and flags, bit
+                               for bit, from a slot-sized workspace (poa_graph_checkpoint_plan2: M, D1 and D2 in slots and snapshots,
+                               five planes in the window).  A mode of its own because a batch's footprint is fixed when it is
+                               created, before any costs are seen.  Two-piece entry points only (poa_align_batch_2piece_ex,
+                               poa_batch_run_2piece on a batch created for it): the one-piece entry points return
+                               POA_ERR_UNSUPPORTED.  Global only (POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED); heuristic and pruning
+                               are ignored. */
 #define POA_HEURISTIC_DIJKSTRA 0u /* AffineDijkstra   (src/aligner/config.rs:49)  */
 #define POA_HEURISTIC_MINGAP 1u   /* AffineMinGapCost (src/aligner/config.rs:104), the default of both reference CLIs */
 
@@ -237,6 +244,12 @@ int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot /* may be NULL */
  * the longest segment (the window: M, I, D).  Host-side table, recomputed by poa_graph_update; needs no device. */
 int poa_graph_checkpoint_plan(const poa_graph_t* g, uint32_t segment_rows /* 0: engine's choice */, uint32_t* n_segments,
                               uint32_t* boundary /* may be NULL, [*n_segments + 1] */, uint32_t* rows_per_query);
+/* the same plan for the two-piece model (POA_MODE_CHECKPOINT2): same contract, same boundaries rule and snapshot membership;
+ * *rows_per_query = 3 x n_slots (M, D1, D2) + 3 x the snapshot rows of all boundaries + 5 x the longest segment (the window:
+ * M, I1, D1, I2, D2).  segment_rows 0 is the length that minimises THIS sum (the window weighs 5 instead of 3, so it differs
+ * from the one-piece choice), never more than one segment of all rows costs. */
+int poa_graph_checkpoint_plan2(const poa_graph_t* g, uint32_t segment_rows /* 0: engine's choice */, uint32_t* n_segments,
+                               uint32_t* boundary /* may be NULL, [*n_segments + 1] */, uint32_t* rows_per_query);
 /* row (topological rank used for the score planes) of every node; rank[n] */
 int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank);
 
@@ -281,7 +294,9 @@ int poa_align_batch_2piece(const poa_graph_t* g, const poa_costs2_t* costs, uint
  * POA_FLAG_EXACT_OVERFLOW (queue pool: raise cfg->queue_entries_per_cell).  search_counters (may be NULL): 4 words per query —
  * num_queued, num_visited, num_pruned (AstarResult, astar.rs:228) and the queue entries that were live at once. */
 /* Mode SCORE: the scores poa_align_batch_2piece returns, by the score-only sweep under the one-piece costs
- * open' = open1 + extend1 - extend2, extend' = extend2; no pairs, flags as under POA_MODE_SCORE. */
+ * open' = open1 + extend1 - extend2, extend' = extend2; no pairs, flags as under POA_MODE_SCORE.
+ * Mode CHECKPOINT2: everything poa_align_batch_2piece returns, from a batch of the checkpointed footprint created, run,
+ * fetched and destroyed inside the call. */
 int poa_align_batch_2piece_ex(const poa_graph_t* g, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t n_queries,
                               const uint8_t* qseq, const uint64_t* qoff, uint32_t* score,
                               poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
@@ -312,7 +327,10 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
  * cfg->tune[POA_TUNE_CKPT_ROWS]; + 256 bytes of padding) and is chunked by that footprint; the cell width of a run follows
  * from its costs, after the batch exists, so it is sized for u32 cells and a u16 run packs twice the queries into a chunk when
  * the batch needs chunks at all.  Pair buffers as in dense mode, carries between strips as in score mode.  The same rule on
- * modes: it runs in POA_MODE_CHECKPOINT only, and no other batch runs in that mode (POA_ERR_INVALID_ARG). */
+ * modes: it runs in POA_MODE_CHECKPOINT only, and no other batch runs in that mode (POA_ERR_INVALID_ARG).
+ * A batch created for POA_MODE_CHECKPOINT2 is the same with the two-piece plan (poa_graph_checkpoint_plan2: three slotted and
+ * snapshot planes, five window planes) and 24 bytes of carries per graph row and query in flight; it runs in that mode through
+ * poa_batch_run_2piece only.  POA_SPAN_ENDS_FREE at creation: POA_ERR_UNSUPPORTED. */
 int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq,
                         const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out);
 /* bytes of the plane workspace the batch holds */
@@ -334,6 +352,15 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
  *                                for POA_MODE_SCORE.
  *   POA_MODE_EXACT / HYBRID / CHECKPOINT, POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED (the replay keeps a workspace of its own:
  *                                poa_align_batch_2piece_ex; checkpointed mode is one-piece only).
+ *   POA_MODE_CHECKPOINT2         poa_align_batch_2piece's results from a slot-sized workspace: per chunk a two-piece sweep that
+ *                                keeps slots and snapshots of M, D1 and D2 (pass 1), then, last segment first, the recompute of a
+ *                                segment's five planes into the window and the walk through it (pass 2); a batch created for
+ *                                POA_MODE_CHECKPOINT2.  Cell width by the rule above; the batch is sized for u32, so a u16 run
+ *                                packs twice the queries per chunk.  poa_stats_t.plane_bytes = the bytes written when the walk enters
+ *                                every segment (at most that: a segment an edge skips is not recomputed).
+ *                                poa_batch_fetch_planes and poa_batch_fetch_planes_2piece return POA_ERR_UNSUPPORTED afterwards.
+ *                                Such a batch in any other mode, or through poa_batch_run / poa_batch_run_ex, and any other
+ *                                batch in this mode: POA_ERR_INVALID_ARG.
  * A batch created for another mode than the run's: POA_ERR_INVALID_ARG; extend1 < extend2: POA_ERR_INVALID_ARG.
  * poa_stats_t.plane_bytes = cells x 5 x cell bytes.  Afterwards poa_batch_last_layout reports POA_LAYOUT_U16 or 0,
  * poa_batch_fetch_planes returns POA_ERR_UNSUPPORTED and poa_batch_fetch_search_counters POA_ERR_INVALID_ARG. */

@@ -278,7 +278,9 @@ struct AstarResult {  // astar.rs:81-90 (+ the exactness certificate of the dens
 };
 
 // Checkpoint: Dense's results from a slot-sized workspace (POA_MODE_CHECKPOINT: one-piece model, Global; else the call throws)
-enum class Mode : uint32_t { Dense = POA_MODE_DENSE, Exact = POA_MODE_EXACT, Hybrid = POA_MODE_HYBRID, Checkpoint = POA_MODE_CHECKPOINT };
+// Checkpoint2: the same for a two-piece config (POA_MODE_CHECKPOINT2; with a one-piece config the call throws)
+enum class Mode : uint32_t { Dense = POA_MODE_DENSE, Exact = POA_MODE_EXACT, Hybrid = POA_MODE_HYBRID, Checkpoint = POA_MODE_CHECKPOINT,
+                             Checkpoint2 = POA_MODE_CHECKPOINT2 };
 
 template <typename Config>
 class PoastaAligner {
@@ -322,7 +324,7 @@ public:
             poa_costs2_t c{};
             c.mismatch = config_.costs.mismatch(); c.gap_open1 = config_.costs.gap_open(); c.gap_extend1 = config_.costs.gap_extend();
             c.gap_open2 = config_.costs.gap_open2(); c.gap_extend2 = config_.costs.gap_extend2();
-            if (mode_ != Mode::Checkpoint && (mode_ != Mode::Dense || aln_type_.ends_free)) { cfg.mode = POA_MODE_EXACT; counters.resize(4 * (size_t)n); }
+            if (mode_ != Mode::Checkpoint && mode_ != Mode::Checkpoint2 && (mode_ != Mode::Dense || aln_type_.ends_free)) { cfg.mode = POA_MODE_EXACT; counters.resize(4 * (size_t)n); }
             rc = poa_align_batch_2piece_ex(g.device_graph(), &c, &cfg, n, (const uint8_t*)qseq.data(), qoff.data(), score.data(), pairs.data(),
                                            pair_off.data(), cap, flags.data(), stats, counters.empty() ? nullptr : counters.data(), device_);
         } else {

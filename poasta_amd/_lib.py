@@ -23,7 +23,7 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_batch_run_ex",
            "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_fetch_planes", "poa_batch_destroy",
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
-           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan"]
+           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2"]
 
 
 class PoaCosts2(C.Structure):
@@ -75,7 +75,7 @@ BOUND_UNBOUNDED, BOUND_INCLUDED, BOUND_EXCLUDED = 0, 1, 2
 SPAN_GLOBAL, SPAN_ENDS_FREE = 0, 1
 
 
-MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE, MODE_CHECKPOINT = 0, 1, 2, 3, 4
+MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE, MODE_CHECKPOINT, MODE_CHECKPOINT2 = 0, 1, 2, 3, 4, 5
 HEURISTIC_DIJKSTRA, HEURISTIC_MINGAP = 0, 1
 FLAG_EXACT_OVERFLOW = 0x40
 CFG_FULL_PLANES = 1
@@ -151,6 +151,8 @@ def lib():
     L.poa_graph_sweep_slots.argtypes = [vp, vp, vp]
     L.poa_graph_checkpoint_plan.restype = C.c_int
     L.poa_graph_checkpoint_plan.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    L.poa_graph_checkpoint_plan2.restype = C.c_int
+    L.poa_graph_checkpoint_plan2.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.poa_batch_create_ex.restype = C.c_int
     L.poa_batch_create_ex.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.POINTER(PoaConfig), C.c_uint64, C.POINTER(vp)]
     L.poa_batch_workspace_bytes.restype = C.c_int

@@ -154,7 +154,7 @@ class AffineDijkstra(AffineMinGapCost):
 
 
 MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE_HYBRID, "score": _lib.MODE_SCORE,
-         "checkpoint": _lib.MODE_CHECKPOINT}
+         "checkpoint": _lib.MODE_CHECKPOINT, "checkpoint2": _lib.MODE_CHECKPOINT2}
 
 
 def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, queue_entries_per_cell=0.0, full_planes=False,
@@ -162,7 +162,8 @@ def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, que
     """poa_config_t: `mode` "dense" | "exact" (replay the reference's A* for every query: bit-identical
     tie-breaks) | "hybrid" (replay only the queries the dense pass could not certify) | "score" (forward sweep only: dense
     mode's scores, no alignment, memory for the live rows only) | "checkpoint" (dense mode's results from a slot-sized
-    workspace: sweep with snapshots, then recompute-and-walk per segment; ckpt_rows=k overrides the segment length);
+    workspace: sweep with snapshots, then recompute-and-walk per segment; ckpt_rows=k overrides the segment length) |
+    "checkpoint2" (the same for the two-piece model: the dense two-piece pass's results, two-piece entry points only);
     `aln_type` Global or EndsFree(...)."""
     cfg = _lib.PoaConfig(MODES[mode] if isinstance(mode, str) else int(mode), int(heuristic), 1 if pruning else 0,
                          float(queue_entries_per_cell), _lib.CFG_FULL_PLANES if full_planes else 0)
@@ -254,13 +255,15 @@ class DeviceGraph:
         _lib.check(_lib.lib().poa_graph_sweep_slots(self.handle, _p(slot), C.byref(n)))
         return slot[:self.graph.n], int(n.value)
 
-    def checkpoint_plan(self, segment_rows=0):
+    def checkpoint_plan(self, segment_rows=0, two_piece=False):
         """(boundary, rows_per_query) of the checkpointed mode: boundary[0] = 0 < ... < boundary[-1] = rows cut the rows into
-        segments of segment_rows rows (0: the engine's choice); rows_per_query = plane rows of `pitch` cells a query holds."""
+        segments of segment_rows rows (0: the engine's choice); rows_per_query = plane rows of `pitch` cells a query holds.
+        two_piece: the plan of mode "checkpoint2" (three kept planes, five window planes; its own default segment length)."""
+        plan = _lib.lib().poa_graph_checkpoint_plan2 if two_piece else _lib.lib().poa_graph_checkpoint_plan
         n_seg, rpq = C.c_uint32(0), C.c_uint32(0)
-        _lib.check(_lib.lib().poa_graph_checkpoint_plan(self.handle, int(segment_rows), C.byref(n_seg), None, C.byref(rpq)))
+        _lib.check(plan(self.handle, int(segment_rows), C.byref(n_seg), None, C.byref(rpq)))
         boundary = np.zeros(n_seg.value + 1, np.uint32)
-        _lib.check(_lib.lib().poa_graph_checkpoint_plan(self.handle, int(segment_rows), C.byref(n_seg), _p(boundary), C.byref(rpq)))
+        _lib.check(plan(self.handle, int(segment_rows), C.byref(n_seg), _p(boundary), C.byref(rpq)))
         return boundary, int(rpq.value)
 
     def __del__(self):
@@ -289,8 +292,8 @@ class ResidentBatch:
     """Queries + results resident in HBM (`poa_batch_*`): create once, run many times."""
 
     def __init__(self, graph, qseq, qoff, device=0, workspace_bytes=0, config=None):
-        """config: the poa_config_t the batch will run with — needed for modes "score" and "checkpoint", whose batches hold
-        slots (and snapshots and a segment window) instead of planes (poa_batch_create_ex) and run in no other mode."""
+        """config: the poa_config_t the batch will run with — needed for modes "score", "checkpoint" and "checkpoint2", whose
+        batches hold slots (and snapshots and a segment window) instead of planes (poa_batch_create_ex) and run in no other mode."""
         self.dg = _device_graph(graph)
         self.qseq = np.ascontiguousarray(qseq, np.uint8)
         self.qoff = np.ascontiguousarray(qoff, np.uint64)
@@ -307,7 +310,8 @@ class ResidentBatch:
 
     def run(self, costs, stream=None, config=None):
         """Launch on `stream` without synchronising.  costs: GapAffine (poa_batch_run_ex) or GapAffine2Piece
-        (poa_batch_run_2piece: the dense two-piece pass, or the score-only sweep on a batch created for mode "score")."""
+        (poa_batch_run_2piece: the dense two-piece pass, the score-only sweep on a batch created for mode "score", or the
+        checkpointed two-piece passes on a batch created for mode "checkpoint2" — pass that config to the run as well)."""
         c = costs._c()
         if isinstance(costs, GapAffine2Piece):
             _lib.check(_lib.lib().poa_batch_run_2piece(self.handle, C.byref(c), C.byref(config) if config is not None else None,

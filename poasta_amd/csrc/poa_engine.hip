@@ -35,6 +35,7 @@ struct TuneView {
 #include "poa_sweep_rows.hpp"
 #include "poa_forward_sweep.hpp"
 #include "poa_checkpoint.hpp"
+#include "poa_checkpoint2.hpp"
 
 using namespace poa_amd;
 
@@ -175,6 +176,7 @@ struct poa_graph {
     FlatGraph g;
     SweepRows sweep;        // row liveness / slots of the score-only sweep (poa_sweep_rows.hpp), rebuilt with g
     CheckpointPlan ckpt;    // segment plan of the checkpointed mode at the engine's own segment length, rebuilt with g
+    CheckpointPlan ckpt2;   // the same for the two-piece model (POA_MODE_CHECKPOINT2: three kept planes, five window planes)
     std::mutex bubble_mu;   // the bubble index (exact / hybrid mode only) is built on first use; batches on other threads may share the handle
 };
 
@@ -250,6 +252,7 @@ struct poa_batch {
     bool ckpt = false;
     CheckpointPlan ckpt_plan;          // the plan the batch was sized for (POA_TUNE_CKPT_ROWS at creation, else the graph's own)
     uint32_t ckpt_slots = 0;
+    bool ckpt2 = false;                // a checkpointed batch of the two-piece model (POA_MODE_CHECKPOINT2, poa_checkpoint2.hpp): `ckpt` is set too
     DevBuf<uint32_t> d_ck_snap_off, d_ck_snap_dst, d_ck_pred_src, d_ck_boundary;
 
     // one event set per run since the last stats call: [begin, (fwd_end, tb_end) per chunk..., end]
@@ -397,6 +400,7 @@ int poa_graph_create(uint32_t n, uint32_t start, uint32_t end, const uint8_t* sy
     try {
         build_sweep_rows(h->g, h->sweep);
         build_checkpoint_plan(h->g, h->sweep, 0, h->ckpt);
+        build_checkpoint_plan(h->g, h->sweep, 0, h->ckpt2, true);
     } catch (const std::bad_alloc&) {
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_create: host allocation failed");
     }
@@ -413,10 +417,10 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     int rc;
     FlatGraph ng;
     SweepRows nsw;
-    CheckpointPlan nck;
+    CheckpointPlan nck, nck2;
     try {
         rc = build_flat_graph(n, start, end, symbol, succ_off, succ, pred_off, pred, ng, err);
-        if (rc == POA_OK) { build_sweep_rows(ng, nsw); build_checkpoint_plan(ng, nsw, 0, nck); }
+        if (rc == POA_OK) { build_sweep_rows(ng, nsw); build_checkpoint_plan(ng, nsw, 0, nck); build_checkpoint_plan(ng, nsw, 0, nck2, true); }
     } catch (const std::bad_alloc&) {
         return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_update: host allocation failed");
     }
@@ -425,6 +429,7 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     g->g = std::move(ng);
     g->sweep = std::move(nsw);
     g->ckpt = std::move(nck);
+    g->ckpt2 = std::move(nck2);
     return POA_OK;
 }
 
@@ -435,20 +440,29 @@ int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot, uint32_t* n_slot
     return POA_OK;
 }
 
-int poa_graph_checkpoint_plan(const poa_graph_t* g, uint32_t segment_rows, uint32_t* n_segments, uint32_t* boundary, uint32_t* rows_per_query) {
-    if (!g || !n_segments || !rows_per_query) return fail(POA_ERR_INVALID_ARG, "poa_graph_checkpoint_plan: null argument");
+static int checkpoint_plan_out(const poa_graph_t* g, bool two_piece, uint32_t segment_rows, uint32_t* n_segments, uint32_t* boundary, uint32_t* rows_per_query) {
+    const std::string who = two_piece ? "poa_graph_checkpoint_plan2" : "poa_graph_checkpoint_plan";
+    if (!g || !n_segments || !rows_per_query) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
     CheckpointPlan own;
-    const CheckpointPlan* pl = &g->ckpt;
-    if (segment_rows != 0 && segment_rows != g->ckpt.segment_rows) {
+    const CheckpointPlan* pl = two_piece ? &g->ckpt2 : &g->ckpt;
+    if (segment_rows != 0 && segment_rows != pl->segment_rows) {
         try {
-            build_checkpoint_plan(g->g, g->sweep, segment_rows, own);
-        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_checkpoint_plan: host allocation failed"); }
+            build_checkpoint_plan(g->g, g->sweep, segment_rows, own, two_piece);
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
         pl = &own;
     }
     *n_segments = pl->n_segments();
     *rows_per_query = pl->rows_per_query;
     if (boundary) std::memcpy(boundary, pl->boundary.data(), pl->boundary.size() * sizeof(uint32_t));
     return POA_OK;
+}
+
+int poa_graph_checkpoint_plan(const poa_graph_t* g, uint32_t segment_rows, uint32_t* n_segments, uint32_t* boundary, uint32_t* rows_per_query) {
+    return checkpoint_plan_out(g, false, segment_rows, n_segments, boundary, rows_per_query);
+}
+
+int poa_graph_checkpoint_plan2(const poa_graph_t* g, uint32_t segment_rows, uint32_t* n_segments, uint32_t* boundary, uint32_t* rows_per_query) {
+    return checkpoint_plan_out(g, true, segment_rows, n_segments, boundary, rows_per_query);
 }
 
 int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank) {
@@ -458,7 +472,7 @@ int poa_graph_node_rows(const poa_graph_t* g, uint32_t* rank) {
 }
 
 static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
-                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt = false, uint32_t ckpt_rows = 0);
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt = false, uint32_t ckpt_rows = 0, bool ckpt2 = false);
 
 int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                      uint64_t workspace_bytes, poa_batch_t** out) {
@@ -467,16 +481,17 @@ int poa_batch_create(const poa_graph_t* g, int device, uint32_t n_queries, const
 
 int poa_batch_create_ex(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                         const poa_config_t* cfg, uint64_t workspace_bytes, poa_batch_t** out) {
-    if (cfg && cfg->mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_create_ex: unknown mode");
+    if (cfg && cfg->mode > POA_MODE_CHECKPOINT2) return fail(POA_ERR_INVALID_ARG, "poa_batch_create_ex: unknown mode");
     const bool sweep = cfg && cfg->mode == POA_MODE_SCORE;
     if (sweep && cfg->span == POA_SPAN_ENDS_FREE)
         return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
-    const bool ckpt = cfg && cfg->mode == POA_MODE_CHECKPOINT;
+    const bool ckpt2 = cfg && cfg->mode == POA_MODE_CHECKPOINT2;   // the two-piece model's checkpointed batch: its own footprint
+    const bool ckpt = ckpt2 || (cfg && cfg->mode == POA_MODE_CHECKPOINT);
     if (ckpt && cfg->span == POA_SPAN_ENDS_FREE)
         return fail(POA_ERR_UNSUPPORTED, "checkpointed mode is Global: an ends-free result is defined by the reference's search");
     uint32_t ckpt_rows = 0;
     if (ckpt) { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) ckpt_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
-    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out, ckpt, ckpt_rows);
+    return batch_create_impl(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out, ckpt, ckpt_rows, ckpt2);
 }
 
 int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
@@ -486,7 +501,7 @@ int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
 }
 
 static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
-                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt, uint32_t ckpt_rows) {
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt, uint32_t ckpt_rows, bool ckpt2) {
     if (!out) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: out is null");
     *out = nullptr;
     if (!g || !qoff || (n_queries && qoff[n_queries] && !qseq))
@@ -509,11 +524,13 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     b->sweep_slots = std::max<uint32_t>(g->sweep.n_slots, 1u);
     b->sweep_slotted = g->sweep.n_slotted;
     b->ckpt = ckpt;
+    b->ckpt2 = ckpt2;
     b->ckpt_slots = g->sweep.n_slots;
     try {
         if (ckpt) {
-            if (ckpt_rows == 0 || ckpt_rows == g->ckpt.segment_rows) b->ckpt_plan = g->ckpt;
-            else build_checkpoint_plan(fg, g->sweep, ckpt_rows, b->ckpt_plan);
+            const CheckpointPlan& own = ckpt2 ? g->ckpt2 : g->ckpt;
+            if (ckpt_rows == 0 || ckpt_rows == own.segment_rows) b->ckpt_plan = own;
+            else build_checkpoint_plan(fg, g->sweep, ckpt_rows, b->ckpt_plan, ckpt2);
         }
         b->h_qoff.assign(qoff, qoff + n_queries + 1);
         b->h_pitch.resize(n_queries);
@@ -544,9 +561,11 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // score-only: the carries between strips (two parities x two words per row and query in flight, poa_forward_sweep.hpp) exist
     // only when some query is longer than one 1024-column strip; they are part of what the batch holds besides the slots
+    // (the two-piece checkpointed passes carry three words per row and parity: poa_checkpoint2.hpp)
     const bool sweep_carry = (sweep || ckpt) && max_len + 1 > 1024;
+    const uint64_t carry_words = ckpt2 ? 6 : 4;
     const uint64_t fixed = scratch_total * 16 + (uint64_t)n_queries * 64 + qoff[n_queries] + (64ull << 20) +
-                           (sweep_carry ? 16ull * n_queries * rows : 0);
+                           (sweep_carry ? 4ull * carry_words * n_queries * rows : 0);
     uint64_t ws = workspace_bytes;
     if (ws == 0) {
         const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
@@ -606,7 +625,7 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n_queries, 1)));
     HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
     HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep_tables ? (sweep_carry ? 4ull : 0ull) : 2ull) * max_chunk_any * rows, 1)));
+    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep_tables ? (sweep_carry ? carry_words : 0ull) : 2ull) * max_chunk_any * rows, 1)));
     HIP_TRY(b->d_pipeline_error.alloc(1));
     HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
     if (n_queries) {
@@ -919,7 +938,12 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     const TuneView T(cfg);   // what this call overrides, read once
     b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
     uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
-    if (mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
+    if (mode == POA_MODE_CHECKPOINT2) {
+        if (b->ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: a POA_MODE_CHECKPOINT2 batch runs through poa_batch_run_2piece only");
+        return fail(POA_ERR_UNSUPPORTED, "POA_MODE_CHECKPOINT2 is the two-piece model's checkpointed mode: poa_batch_run_2piece / poa_align_batch_2piece_ex");
+    }
+    if (mode > POA_MODE_CHECKPOINT2) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown mode");
+    if (b->ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: the batch was created for POA_MODE_CHECKPOINT2 (it runs in that mode through poa_batch_run_2piece only)");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: unknown alignment span");
     const bool ends_free = cfg && cfg->span == POA_SPAN_ENDS_FREE;
     if (mode == POA_MODE_SCORE) {
@@ -1470,7 +1494,7 @@ int poa_batch_stats(poa_batch_t* b, poa_stats_t* stats) {
 
 int poa_batch_fetch_search_counters(poa_batch_t* b, uint32_t* out) {
     if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: null argument");
-    if (!b->ran || b->last_mode == POA_MODE_DENSE || b->last_mode == POA_MODE_SCORE || b->last_mode == POA_MODE_CHECKPOINT || !b->d_ex_counters.p)
+    if (!b->ran || b->last_mode == POA_MODE_DENSE || b->last_mode == POA_MODE_SCORE || b->last_mode == POA_MODE_CHECKPOINT || b->last_mode == POA_MODE_CHECKPOINT2 || !b->d_ex_counters.p)
         return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_search_counters: the last run was not an exact / hybrid run");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->last_stream));
@@ -1572,11 +1596,96 @@ static int prepare_two_piece_u32(poa_batch* b) {
     return POA_OK;
 }
 
+// Checkpointed run of a two-piece batch created for it (POA_MODE_CHECKPOINT2): per chunk the two-piece sweep with snapshots
+// (pass 1), then recompute-and-walk over five window planes (pass 2); scan and compaction of the pairs as in dense mode.
+static int run_ckpt2(poa_batch* b, const poa_costs2_t* costs, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(b->device));
+    const FlatGraph& fg = b->graph->g;
+    const CheckpointPlan& cp = b->ckpt_plan;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
+    if (b->n_queries && cp.n_segments() == 0) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: the graph has no rows");
+    b->last_mode = POA_MODE_CHECKPOINT2;
+    b->two_piece = false;   // (no full planes to fetch)
+    b->last_stream = stream;
+    // cell width: the rule of the dense two-piece run (the first piece's costs bound the optimum; wide_planes forces u32)
+    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * b->max_len : 0) +
+                        (fg.min_path_nodes ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * fg.min_path_nodes : 0);
+    const bool narrow = ub <= 65534 && !costs->wide_planes;
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = (narrow && !b->plan16_same) ? 1 : 0;   // the batch is sized for u32: a u16 run packs twice the queries per chunk
+    const poa_batch::Plan& PL = b->cur();
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * PL.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    b->sweep_bytes_written = 0;
+    Ckpt2Params kp;
+    kp.rows = b->d_rows.p; kp.pred_rows = b->d_pred_rows.p; kp.slot = b->d_dslot.p; kp.pred_slot = b->d_pred_dslot.p;
+    kp.snap_off = b->d_ck_snap_off.p; kp.snap_dst = b->d_ck_snap_dst.p; kp.pred_src = b->d_ck_pred_src.p; kp.boundary = b->d_ck_boundary.p;
+    kp.n_rows = fg.n; kp.n_slots = b->ckpt_slots; kp.n_snap = cp.n_snap_rows; kp.seg_rows = cp.max_segment; kp.n_segments = cp.n_segments();
+    kp.start_row = fg.start_row; kp.end_row = fg.end_row;
+    kp.qseq = b->d_qseq.p; kp.qoff = b->d_qoff.p; kp.pitch = b->d_pitch.p; kp.plane_off = PL.d_off.p;
+    kp.planes = b->d_planes.p; kp.carry = b->d_carry.p;
+    kp.x = costs->mismatch; kp.o1 = costs->gap_open1; kp.e1 = costs->gap_extend1; kp.e2 = costs->gap_extend2;
+    kp.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
+    kp.scratch_off = b->d_scratch_off.p; kp.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p);
+    kp.score = b->d_score.p; kp.flags = b->d_flags.p; kp.n_pairs = b->d_npairs.p;
+    size_t ev = 1;
+    for (const auto& ch : PL.chunks) {
+        kp.first_query = ch.first; kp.n_queries = ch.count;
+        uint64_t pitch_sum = 0;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) pitch_sum += b->h_pitch[i];
+        // cells stored: pass 1 its slotted rows and the snapshots (M, D1, D2), pass 2 every row once (five planes) when the walk
+        // enters every segment, which a Global alignment does unless an edge skips one
+        b->sweep_bytes_written += (3ull * (b->sweep_slotted + cp.n_snap_rows) + 5ull * fg.n) * pitch_sum * (narrow ? 2 : 4);
+        // one wave per query; a strip of 1024 columns (u16: two passes of 512, u32: four of 256) keeps the previous row in registers
+        if (narrow) hipLaunchKernelGGL((poa2_ckpt_sweep_kernel<uint16_t, 2>), dim3(ch.count), dim3(64), 0, stream, kp);
+        else hipLaunchKernelGGL((poa2_ckpt_sweep_kernel<uint32_t, 4>), dim3(ch.count), dim3(64), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (narrow) hipLaunchKernelGGL((poa2_ckpt_trace_kernel<uint16_t, 2>), dim3(ch.count), dim3(64), 0, stream, kp);
+        else hipLaunchKernelGGL((poa2_ckpt_trace_kernel<uint32_t, 4>), dim3(ch.count), dim3(64), 0, stream, kp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+    }
+    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
 int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!b || !costs) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: null argument");
     const uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
-    if (mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: unknown mode");
+    if (mode > POA_MODE_CHECKPOINT2) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: unknown mode");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: unknown alignment span");
+    // a CHECKPOINT2 batch runs in that mode only, and no other batch runs in it
+    if (b->ckpt2 != (mode == POA_MODE_CHECKPOINT2))
+        return fail(POA_ERR_INVALID_ARG, b->ckpt2 ? "poa_batch_run_2piece: the batch was created for POA_MODE_CHECKPOINT2 (it holds no full score planes and runs in that mode only)"
+                                                  : "poa_batch_run_2piece: POA_MODE_CHECKPOINT2 needs a batch created by poa_batch_create_ex with that mode (a batch created for another mode than the run's)");
     if (mode == POA_MODE_EXACT || mode == POA_MODE_HYBRID)
         return fail(POA_ERR_UNSUPPORTED, "poa_batch_run_2piece: the replay of the reference's two-piece search keeps a workspace of its own (poa_align_batch_2piece_ex)");
     if (mode == POA_MODE_CHECKPOINT) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode: one-piece gap-affine model only");
@@ -1586,6 +1695,7 @@ int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_co
         return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
     const TuneView T(cfg);
     hipStream_t stream = (hipStream_t)stream_v;
+    if (mode == POA_MODE_CHECKPOINT2) return run_ckpt2(b, costs, stream);
     if (mode == POA_MODE_SCORE) {
         if (!b->sweep) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: POA_MODE_SCORE needs a batch created by poa_batch_create_ex with that mode");
         // the two-piece optimum is the one-piece optimum under open' = open1 + extend1 - extend2, extend' = extend2
@@ -1669,6 +1779,7 @@ int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_co
 int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2) {
     if (!b || !m || !i1 || !d1 || !i2 || !d2) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: null argument");
     if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: bad query / not run");
+    if (b->ckpt2) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes_2piece: a checkpointed batch keeps snapshots and one segment window, no score planes");
     if (!b->two_piece) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the last run was not a dense two-piece run");
     const auto& last = b->cur().chunks.back();
     if (query < last.first || query >= last.first + last.count)
@@ -1729,6 +1840,8 @@ int poa_align_batch_ex(const poa_graph_t* g, const poa_costs_t* costs, const poa
                        const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off,
                        uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
     if (!g || !costs || !qoff) return fail(POA_ERR_INVALID_ARG, "poa_align_batch: null argument");
+    if (cfg && cfg->mode == POA_MODE_CHECKPOINT2)
+        return fail(POA_ERR_UNSUPPORTED, "POA_MODE_CHECKPOINT2 is the two-piece model's checkpointed mode: poa_align_batch_2piece_ex / poa_batch_run_2piece");
     const TuneView T(cfg);
     if (stats) std::memset(stats, 0, sizeof(*stats));
     // PoastaAligner::align, empty-graph shortcut (src/aligner/mod.rs:124-142): score 4*len, no pairs
@@ -1836,9 +1949,12 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
     // model a dense flag of 0 certifies the alignment only where the reference's search is optimal, and it need not be:
     // DESIGN.md §6a — so there is no cheaper hybrid)
     const bool score_only = cfg && cfg->mode == POA_MODE_SCORE;
-    const bool exact = cfg && cfg->mode != POA_MODE_DENSE && !score_only;
+    const bool exact = cfg && cfg->mode != POA_MODE_DENSE && !score_only && cfg->mode != POA_MODE_CHECKPOINT2;
     if (cfg && cfg->mode == POA_MODE_CHECKPOINT) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode: one-piece gap-affine model only");
-    if (cfg && cfg->mode > POA_MODE_CHECKPOINT) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
+    if (cfg && cfg->mode > POA_MODE_CHECKPOINT2) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown mode");
+    const bool ckpt2 = cfg && cfg->mode == POA_MODE_CHECKPOINT2;
+    if (ckpt2 && cfg->span == POA_SPAN_ENDS_FREE)
+        return fail(POA_ERR_UNSUPPORTED, "checkpointed mode is Global: an ends-free result is defined by the reference's search");
     if (score_only && cfg->span == POA_SPAN_ENDS_FREE)
         return fail(POA_ERR_UNSUPPORTED, "score-only mode is Global: an ends-free result is defined by the reference's search");
     if (cfg && cfg->span > POA_SPAN_ENDS_FREE) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece_ex: unknown alignment span");
@@ -1874,6 +1990,16 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
         if (pair_off) std::memset(pair_off, 0, ((size_t)n_queries + 1) * sizeof(uint64_t));
         return sweep_one_shot(g, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
                               n_queries, qseq, qoff, score, pair_off, flags, stats, device);
+    }
+    if (ckpt2) {
+        // one-shot checkpointed call: a batch sized from the plan's footprint, one run, everything the dense pass returns
+        poa_batch_t* cb = nullptr;
+        int crc = poa_batch_create_ex(g, device, n_queries, qseq, qoff, cfg, 0, &cb);
+        if (crc != POA_OK) return crc;
+        crc = poa_batch_run_2piece(cb, costs, cfg, nullptr);
+        if (crc == POA_OK) crc = poa_batch_fetch(cb, score, pairs, pair_off, pair_capacity, flags, stats);
+        poa_batch_destroy(cb);
+        return crc;
     }
     const uint32_t pitch = (uint32_t)((max_len + 64) & ~63ull);
     const uint64_t per_query = 5ull * fg.n * pitch;   // plane elements

@@ -50,7 +50,7 @@ static inline bool snap_by_slot(const SweepRows& sw, uint32_t p, uint32_t b) {
     return sw.slot[p] != SWEEP_NO_SLOT && sw.last_reader[p] >= b;
 }
 
-uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k) {
+uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k, bool two_piece) {
     const uint32_t n = (uint32_t)g.rows.size();
     if (n == 0) return 0;
     if (k == 0 || k > n) k = n;
@@ -60,10 +60,12 @@ uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint
         if (sw.slot[p] != SWEEP_NO_SLOT) snap += sw.last_reader[p] / k - p / k;
     for (uint32_t b = k; b < n; b += k)
         if ((g.rows[b].flags & ROW_CHAIN) && !snap_by_slot(sw, b - 1, b)) snap++;
-    return 2ull * sw.n_slots + 2ull * snap + 3ull * k;
+    const CheckpointWeights w = checkpoint_weights(two_piece);
+    return (uint64_t)w.kept * sw.n_slots + (uint64_t)w.kept * snap + (uint64_t)w.window * k;
 }
 
-void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out) {
+void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out, bool two_piece) {
+    const CheckpointWeights wt = checkpoint_weights(two_piece);
     const uint32_t n = (uint32_t)g.rows.size();
     out = CheckpointPlan();
     out.snap_off.assign((size_t)n + 1, 0);
@@ -72,16 +74,17 @@ void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t seg
     if (n == 0) return;
     uint32_t k = segment_rows;
     if (k == 0) {
-        // the sum 2 * (n_slots + 1) * S + 3 * rows / S is least at S = sqrt(1.5 * rows / (n_slots + 1)); the real snapshots are
-        // smaller than n_slots + 1 rows, so the neighbourhood of that S is searched with the real count
+        // the sum kept * (n_slots + 1) * S + window * rows / S (2 and 3 planes in the one-piece model, 3 and 5 in the two-piece
+        // one) is least at S = sqrt(window * rows / (kept * (n_slots + 1))); the real snapshots are smaller than n_slots + 1
+        // rows, so the neighbourhood of that S is searched with the real count
         uint32_t s0 = 1;
-        while ((uint64_t)(s0 + 1) * (s0 + 1) * 2 * (sw.n_slots + 1) <= 3ull * n) ++s0;
+        while ((uint64_t)(s0 + 1) * (s0 + 1) * wt.kept * (sw.n_slots + 1) <= (uint64_t)wt.window * n) ++s0;
         k = n;
-        uint64_t best = checkpoint_rows_per_query(g, sw, n);   // one segment: full planes, the most the mode may ever hold
+        uint64_t best = checkpoint_rows_per_query(g, sw, n, two_piece);   // one segment: full planes, the most the mode may ever hold
         for (uint32_t s : {s0 / 2, (2 * s0) / 3, s0, s0 + s0 / 2, 2 * s0, 3 * s0}) {
             if (s < 2 || s > n) continue;
             const uint32_t kk = (n + s - 1) / s;
-            const uint64_t c = checkpoint_rows_per_query(g, sw, kk);
+            const uint64_t c = checkpoint_rows_per_query(g, sw, kk, two_piece);
             if (c < best) { best = c; k = kk; }
         }
     }
@@ -124,7 +127,7 @@ void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t seg
     for (uint32_t r = 0; r < n; ++r) out.snap_off[r + 1] = out.snap_off[r] + (uint32_t)dst[r].size();
     out.snap_dst.reserve(next);
     for (uint32_t r = 0; r < n; ++r) out.snap_dst.insert(out.snap_dst.end(), dst[r].begin(), dst[r].end());
-    out.rows_per_query = (uint32_t)(2ull * sw.n_slots + 2ull * next + 3ull * k);
+    out.rows_per_query = (uint32_t)((uint64_t)wt.kept * sw.n_slots + (uint64_t)wt.kept * next + (uint64_t)wt.window * k);
 }
 
 }  // namespace poa_amd

@@ -47,7 +47,7 @@ struct CheckpointPlan {
     uint32_t segment_rows = 0;         // rows per segment (the last may hold fewer)
     uint32_t max_segment = 0;          // rows of the longest segment: the window
     uint32_t n_snap_rows = 0;          // snapshot rows, all boundaries together
-    uint32_t rows_per_query = 0;       // 2 * n_slots + 2 * n_snap_rows + 3 * max_segment plane rows of `pitch` cells
+    uint32_t rows_per_query = 0;       // 2 * n_slots + 2 * n_snap_rows + 3 * max_segment plane rows of `pitch` cells (two-piece: 3, 3 and 5)
     std::vector<uint32_t> boundary;    // [n_segments + 1]: 0 ... rows
     std::vector<uint32_t> snap_off;    // [n + 1] CSR by row into snap_dst
     std::vector<uint32_t> snap_dst;    // snapshot rows a row is stored to in pass 1
@@ -55,10 +55,17 @@ struct CheckpointPlan {
     uint32_t n_segments() const { return boundary.empty() ? 0u : (uint32_t)boundary.size() - 1u; }
 };
 
+// Planes a query holds per kept row (slot or snapshot) and per window row.  One-piece model: M and D are kept, the window
+// holds M, I and D.  Two-piece model (POA_MODE_CHECKPOINT2, poa_checkpoint2.hpp): M, D1 and D2 are kept (D2 leaves its row as
+// D1 does, I1 and I2 never do), the window holds all five.  Boundaries and snapshot membership are the same for both; the
+// default segment length differs because the window weighs more.
+struct CheckpointWeights { uint32_t kept, window; };
+inline CheckpointWeights checkpoint_weights(bool two_piece) { return two_piece ? CheckpointWeights{3, 5} : CheckpointWeights{2, 3}; }
+
 // plane rows a query holds with segments of k rows (what the default plan minimises)
-uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k);
-// segment_rows 0: the engine's choice — about sqrt(1.5 * rows / (n_slots + 1)) segments, the candidate around it that
-// holds the fewest rows, and never more than one segment of all rows would
-void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out);
+uint64_t checkpoint_rows_per_query(const FlatGraph& g, const SweepRows& sw, uint32_t k, bool two_piece = false);
+// segment_rows 0: the engine's choice — about sqrt(window * rows / (kept * (n_slots + 1))) segments, the candidate around it
+// that holds the fewest rows, and never more than one segment of all rows would
+void build_checkpoint_plan(const FlatGraph& g, const SweepRows& sw, uint32_t segment_rows, CheckpointPlan& out, bool two_piece = false);
 
 }  // namespace poa_amd
