@@ -393,6 +393,58 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
 int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2);
 void poa_batch_destroy(poa_batch_t* b);
 
+/* ---- multi-graph batch: the queries of many graphs in one checkpointed run ---------------- */
+/* For hosts that bring hundreds of small graphs with a few reads each (window consensus, amplicon families): one launch per
+ * pass covers every query of every graph, one wavefront per query, each wave reading its own graph's tables.
+ *   graphs[n_graphs]          graph handles; the same handle may be listed more than once (its tables are uploaded once)
+ *   graph_qoff[n_graphs + 1]  queries are grouped by graph: graph g owns the queries [graph_qoff[g], graph_qoff[g + 1]), a range
+ *                             may be empty.  graph_qoff[0] must be 0 and the array non-decreasing; graph_qoff[n_graphs] IS the
+ *                             query count n of the batch, so qseq / qoff[n + 1] must hold that many queries (a caller that
+ *                             knows its count another way checks the two against each other before the call, as the Python
+ *                             binding does)
+ *   cfg                       NULL or mode POA_MODE_CHECKPOINT, the only mode: the results are dense mode's score, pairs,
+ *                             pair_off and flags of every query against its own graph, bit for bit (poa_align_batch_ex in that
+ *                             mode, graph by graph).  Every other mode, and POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED.
+ *                             tune[POA_TUNE_CKPT_ROWS] (read at creation / by poa_multi_footprint) applies to every graph,
+ *                             tune[POA_TUNE_PLANES] to a run.
+ * Results are in query order; pairs[].rpos is the node index in THAT query's graph; pair_off runs over all queries; capacity
+ * sum(len_i + n_nodes(graph_i)) always suffices.  Queries against a graph without real nodes get POA_FLAG_EMPTY_GRAPH, score
+ * 4 * len and no pairs, as poa_align_batch_ex gives them.  POA_ERR_INVALID_ARG: graph_qoff[0] != 0, graph_qoff not
+ * non-decreasing, a NULL graph or array.
+ * Memory: a query holds rows_per_query(its graph) x pitch 4-byte cells + 256 bytes (poa_graph_checkpoint_plan of its graph alone;
+ * pitch = len + 1 rounded up to 64).  poa_multi_footprint returns the sum over all queries (the batch as one chunk) and its
+ * largest term, on the host, without a device.  poa_multi_create takes workspace_bytes as a cap (0: the whole batch, or what
+ * free device memory allows; a cap below the largest query is raised to it) and cuts the queries into chunks greedily in query
+ * order — a chunk ends in front of the first query that no longer fits, inside a graph's range or between two graphs.  The
+ * batch is sized for u32 cells; a u16 run uses the same chunks and half of every region.  The cell width of a run is u16 only
+ * if EVERY graph that has queries allows it — [open + extend x its longest query] + [open + extend x its shortest path] <=
+ * 65534 — and tune[POA_TUNE_PLANES] is not 32; else u32 for the whole run.  Both are exact: results do not depend on it.
+ * Carries between strips (queries of more than 1024 columns only): 16 bytes per graph row of such a query in flight.
+ * poa_multi_run launches on `stream` (a hipStream_t, NULL = default stream) without synchronising, and may be called again
+ * with other costs; poa_multi_fetch / _stats / _device_results behave as their poa_batch_* namesakes, with poa_stats_t summed
+ * over all graphs (cells = sum rows(graph_i) x (len_i + 1)).  poa_graph_update on a member graph after poa_multi_create: the
+ * batch keeps the tables it copied and must not be run again.  A poa_multi_t belongs to one thread at a time. */
+typedef struct poa_multi poa_multi_t;
+/* host only, no device: bytes of plane workspace for the whole batch as one chunk, and of its largest query */
+int poa_multi_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
+                        const uint64_t* qoff, const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes);
+int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device,
+                     const uint8_t* qseq, const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes,
+                     poa_multi_t** out);
+int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);
+int poa_multi_fetch(poa_multi_t* m, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
+                    uint32_t* flags, poa_stats_t* stats);
+int poa_multi_stats(poa_multi_t* m, poa_stats_t* stats);
+int poa_multi_device_results(poa_multi_t* m, void** score, void** flags, void** pair_off, void** pairs);
+/* bytes of the plane workspace the batch holds: its largest chunk */
+int poa_multi_workspace_bytes(poa_multi_t* m, uint64_t* bytes);
+void poa_multi_destroy(poa_multi_t* m);
+/* one-shot: create, run, fetch, destroy */
+int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
+                    const poa_costs_t* costs, const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff,
+                    uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags,
+                    poa_stats_t* stats, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,9 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_batch_run_ex",
            "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_fetch_planes", "poa_batch_destroy",
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
-           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2"]
+           "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
+           "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
+           "poa_multi_workspace_bytes", "poa_multi_destroy", "poa_align_multi"]
 
 
 class PoaCosts2(C.Structure):
@@ -177,6 +179,26 @@ def lib():
     L.poa_batch_fetch_planes_2piece.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]
     L.poa_batch_destroy.argtypes = [vp]
     L.poa_batch_destroy.restype = None
+    # multi-graph batch: graphs is an array of n_graphs handles (c_void_p * n_graphs)
+    L.poa_multi_footprint.restype = C.c_int
+    L.poa_multi_footprint.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.poa_multi_create.restype = C.c_int
+    L.poa_multi_create.argtypes = [vp, C.c_uint32, vp, C.c_int, vp, vp, C.POINTER(PoaConfig), C.c_uint64, C.POINTER(vp)]
+    L.poa_multi_run.restype = C.c_int
+    L.poa_multi_run.argtypes = [vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp]
+    L.poa_multi_fetch.restype = C.c_int
+    L.poa_multi_fetch.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(PoaStats)]
+    L.poa_multi_stats.restype = C.c_int
+    L.poa_multi_stats.argtypes = [vp, C.POINTER(PoaStats)]
+    L.poa_multi_device_results.restype = C.c_int
+    L.poa_multi_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.poa_multi_workspace_bytes.restype = C.c_int
+    L.poa_multi_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.poa_multi_destroy.argtypes = [vp]
+    L.poa_multi_destroy.restype = None
+    L.poa_align_multi.restype = C.c_int
+    L.poa_align_multi.argtypes = [vp, C.c_uint32, vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp, vp, vp, vp, vp, C.c_uint64, vp,
+                                  C.POINTER(PoaStats), C.c_int]
     _lib = L
     return L
 

@@ -417,6 +417,100 @@ class ResidentBatch:
             pass
 
 
+class _MultiInput:
+    """graphs + per-graph query lists (or graph_qoff + packed queries) as the arrays poa_multi_* take."""
+
+    def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None):
+        self.dgs = [_device_graph(g) for g in graphs]
+        if seqs_per_graph is not None:
+            if len(seqs_per_graph) != len(self.dgs):
+                raise ValueError("seqs_per_graph needs one list of queries per graph")
+            graph_qoff = np.concatenate([[0], np.cumsum([len(s) for s in seqs_per_graph])])
+            qseq, qoff = pack_queries([q for s in seqs_per_graph for q in s])
+        self.graph_qoff = np.ascontiguousarray(graph_qoff, np.uint64)
+        self.qseq = np.ascontiguousarray(qseq, np.uint8)
+        self.qoff = np.ascontiguousarray(qoff, np.uint64)
+        self.n = len(self.qoff) - 1
+        if len(self.graph_qoff) != len(self.dgs) + 1:
+            raise ValueError("graph_qoff needs n_graphs + 1 entries")
+        # the C ABI takes the query count from graph_qoff[n_graphs]: check it here, where the count is known
+        if int(self.graph_qoff[-1]) != self.n:
+            raise ValueError("graph_qoff[n_graphs] = %d is not the query count %d" % (int(self.graph_qoff[-1]), self.n))
+        self.handles = (C.c_void_p * max(len(self.dgs), 1))(*[dg.handle for dg in self.dgs])
+        self.n_graphs = len(self.dgs)
+        per_graph = np.diff(self.graph_qoff.astype(np.int64))
+        self.pair_capacity = int(self.qoff[-1]) + int(sum(int(c) * dg.graph.n for c, dg in zip(per_graph, self.dgs) if c > 0))
+
+
+def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None):
+    """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
+    largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan."""
+    mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
+    total, largest = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().poa_multi_footprint(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff),
+                                              C.byref(config) if config is not None else None, C.byref(total), C.byref(largest)))
+    return int(total.value), int(largest.value)
+
+
+class MultiGraphBatch:
+    """The queries of many graphs resident in HBM (`poa_multi_*`): one checkpointed run covers all of them, one wavefront per
+    query.  Queries are grouped by graph — seqs_per_graph[g] are graph g's, or graph_qoff + packed qseq / qoff; results come
+    back in query order, rpos = node index in that query's own graph."""
+
+    def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None):
+        mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
+        self.input, self.n, self.pair_capacity = mi, mi.n, mi.pair_capacity
+        self.graph_qoff, self.qseq, self.qoff = mi.graph_qoff, mi.qseq, mi.qoff
+        h = C.c_void_p()
+        _lib.check(_lib.lib().poa_multi_create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
+                                               C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
+        self.handle = h
+
+    def run(self, costs, stream=None, config=None):
+        """Launch on `stream` without synchronising (config: None or make_config("checkpoint", ...))."""
+        c = costs._c()
+        if config is None:
+            config = make_config("checkpoint")   # (carries the POA_<NAME> overrides, if any are set)
+        _lib.check(_lib.lib().poa_multi_run(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+
+    def fetch(self, want_pairs=True):
+        n = self.n
+        score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        pair_off = np.zeros(n + 1, np.uint64)
+        pairs = np.zeros((max(self.pair_capacity, 1), 2), np.uint32) if want_pairs else None
+        st = _lib.PoaStats()
+        _lib.check(_lib.lib().poa_multi_fetch(self.handle, _p(score), _p(pairs), _p(pair_off), self.pair_capacity, _p(flags), C.byref(st)))
+        if want_pairs:
+            pairs = pairs[:int(pair_off[n])]
+        return BatchResult(score, pairs, pair_off, flags, st.as_dict())
+
+    def stats(self):
+        st = _lib.PoaStats()
+        _lib.check(_lib.lib().poa_multi_stats(self.handle, C.byref(st)))
+        return st.as_dict()
+
+    def workspace_bytes(self):
+        v = C.c_uint64(0)
+        _lib.check(_lib.lib().poa_multi_workspace_bytes(self.handle, C.byref(v)))
+        return int(v.value)
+
+    def device_results(self):
+        ptrs = [C.c_void_p() for _ in range(4)]
+        _lib.check(_lib.lib().poa_multi_device_results(self.handle, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("score", "flags", "pair_off", "pairs"), [p.value for p in ptrs]))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.lib().poa_multi_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PoastaAligner:
     """`PoastaAligner::new(config, aln_type)` (mod.rs:53)."""
 
@@ -508,6 +602,27 @@ class PoastaAligner:
         cfg = make_config(self.mode, self.config.heuristic, pruning, self.queue_entries_per_cell, aln_type=self.aln_type)
         _lib.check(_lib.lib().poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, _p(qseq), _p(qoff), _p(score),
                                                  _p(pairs), _p(pair_off), cap, _p(flags), C.byref(st), self.device))
+        if want_pairs:
+            pairs = pairs[:int(pair_off[n])]
+        return BatchResult(score, pairs, pair_off, flags, st.as_dict())
+
+    def align_multi(self, graphs, seqs_per_graph, want_pairs=True):
+        """Many graphs, a few reads each, in one checkpointed run (poa_align_multi): seqs_per_graph[g] are the queries of
+        graphs[g].  Returns a BatchResult over all queries in that order: dense mode's score, alignment and flags of every
+        query against its own graph.  One-piece costs, Global."""
+        if getattr(self.config, "two_piece", False) or self.aln_type != AlignmentType.Global:
+            raise ValueError("align_multi: one-piece costs and AlignmentType.Global only")
+        mi = _MultiInput(graphs, seqs_per_graph)
+        n = mi.n
+        score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        pair_off = np.zeros(n + 1, np.uint64)
+        pairs = np.zeros((max(mi.pair_capacity, 1), 2), np.uint32) if want_pairs else None
+        st = _lib.PoaStats()
+        c = self.config.costs._c()
+        cfg = make_config("checkpoint", self.config.heuristic)
+        _lib.check(_lib.lib().poa_align_multi(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq),
+                                              _p(mi.qoff), _p(score), _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags),
+                                              C.byref(st), self.device))
         if want_pairs:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())

@@ -36,6 +36,8 @@ struct TuneView {
 #include "poa_forward_sweep.hpp"
 #include "poa_checkpoint.hpp"
 #include "poa_checkpoint2.hpp"
+#include "poa_multi_plan.hpp"
+#include "poa_multi.hpp"
 
 using namespace poa_amd;
 
@@ -2220,3 +2222,356 @@ int poa_planes_2piece(const poa_graph_t* g, const poa_costs2_t* costs, const uin
     uint32_t sc = 0, fl = 0;
     return run_two_piece(g, costs, nullptr, 1, seq, qoff, &sc, nullptr, nullptr, 0, &fl, nullptr, device, out, nullptr);
 }
+
+
+// ---- multi-graph checkpointed batch (poa_multi.hpp, poa_multi_plan.hpp) -----------------------------------------------------
+// The batch's buffers, events, fetch and statistics are those of a poa_batch (`core`, no graph of its own): poa_batch_fetch,
+// poa_batch_stats and poa_batch_device_results serve it unchanged.  What is new lies beside it: the plan, the concatenated
+// tables of all graphs and one parameter block per graph.
+struct poa_multi {
+    poa_batch core;
+    MultiPlan plan;
+    std::vector<uint64_t> ub_open, ub_extend;   // per graph with queries: the u16 bound is open * ub_open + extend * ub_extend
+    uint64_t stored_rows_pitch = 0;             // sum over queries of (2 x (slotted + snapshot rows) + 3 x rows) x pitch: cells a run stores
+    DevBuf<uint32_t> d_slot, d_pred_slot, d_graph_of, d_carry_off;
+    DevBuf<MultiGraphParams> d_params;
+};
+
+namespace {
+int multi_mode_check(const poa_config_t* cfg, const char* who) {
+    if (cfg && cfg->mode != POA_MODE_CHECKPOINT)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a multi-graph batch runs in POA_MODE_CHECKPOINT only");
+    if (cfg && cfg->span != POA_SPAN_GLOBAL)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": checkpointed mode is Global: an ends-free result is defined by the reference's search");
+    return POA_OK;
+}
+
+int multi_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                  const poa_config_t* cfg, uint64_t workspace_bytes, MultiPlan& plan, const char* who) {
+    if (!graph_qoff || !qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    std::vector<MultiGraphIn> in(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
+        in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, &graphs[g]->ckpt};
+    }
+    uint32_t seg_rows = 0;
+    { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
+    std::string err;
+    const int rc = build_multi_plan(in.data(), n_graphs, graph_qoff, qoff, seg_rows, workspace_bytes, plan, err);
+    if (rc != 0) return fail(rc, std::string(who) + ": " + err);
+    return POA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int poa_multi_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                        const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, "poa_multi_footprint: null argument");
+    int rc = multi_mode_check(cfg, "poa_multi_footprint");
+    if (rc != POA_OK) return rc;
+    MultiPlan plan;
+    try {
+        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, "poa_multi_footprint");
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_footprint: host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    if (bytes) *bytes = plan.bytes_total;
+    if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
+    return POA_OK;
+}
+
+int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                     const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    if (!out) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: out is null");
+    *out = nullptr;
+    int rc = multi_mode_check(cfg, "poa_multi_create");
+    if (rc != POA_OK) return rc;
+    std::unique_ptr<poa_multi> m(new (std::nothrow) poa_multi);
+    if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
+    MultiPlan& pl = m->plan;
+    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
+    try {
+        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, pl, "poa_multi_create");
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_create: host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    const uint32_t n = pl.n_queries;
+    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: null argument");
+    const int ndev = poa_device_count();
+    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t scratch_total = pl.scratch_off[n];
+    const uint64_t fixed = scratch_total * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + pl.max_carry_words * 4 +
+                           (pl.n_rows_total + pl.n_edges_total) * 32;
+    uint64_t ws = workspace_bytes;
+    if (ws == 0) {
+        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
+        ws = std::min<uint64_t>(pl.bytes_total, avail);
+    }
+    if (ws < pl.largest_query_bytes) {
+        if (pl.largest_query_bytes + fixed > free_b)
+            return fail(POA_ERR_OUT_OF_MEMORY, "the checkpointed footprint of the largest query does not fit in device memory");
+        ws = pl.largest_query_bytes;
+    }
+    if (ws < pl.bytes_total) {
+        try {
+            rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, ws, pl, "poa_multi_create");
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_create: host allocation failed"); }
+        if (rc != POA_OK) return rc;
+    }
+
+    // the core batch: queries, results, pair buffers, events
+    poa_batch* b = &m->core;
+    b->graph = nullptr; b->device = device; b->n_queries = n;
+    b->ckpt = true; b->last_mode = POA_MODE_CHECKPOINT;
+    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.bytes_total;
+    b->plan_ws = pl.workspace_bytes;
+    try {
+        b->h_qoff.assign(qoff, qoff + n + 1);
+        b->h_pitch = pl.pitch;
+        b->h_scratch_off = pl.scratch_off;
+        b->plan[0].off = pl.region_off;
+        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
+        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    b->active_plan = 0;
+    for (uint32_t g = 0; g < n_graphs; ++g) b->max_len = std::max(b->max_len, pl.graphs[g].max_len);
+
+    // concatenated tables, one copy per distinct handle, and the parameter block of every listed graph
+    std::vector<RowMeta> h_rows(pl.n_rows_total);
+    std::vector<uint32_t> h_slot(pl.n_rows_total), h_pred_rows(pl.n_edges_total), h_pred_slot(pl.n_edges_total), h_pred_src(pl.n_edges_total);
+    std::vector<uint32_t> h_snap_off(pl.n_snap_off_total), h_snap_dst(pl.n_snap_dst_total), h_boundary(pl.n_boundary_total);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const uint64_t stored = 2ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 3ull * gp.n_rows;
+        for (uint64_t i = graph_qoff[g]; i < graph_qoff[g + 1]; ++i) m->stored_rows_pitch += stored * pl.pitch[i];
+        if (gp.n_queries) {
+            m->ub_open.push_back((gp.max_len ? 1 : 0) + (graphs[g]->g.min_path_nodes ? 1 : 0));
+            m->ub_extend.push_back(gp.max_len + graphs[g]->g.min_path_nodes);
+        }
+        if (gp.table_of != g) continue;
+        const FlatGraph& fg = graphs[g]->g;
+        const SweepRows& sw = graphs[g]->sweep;
+        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
+        std::copy(sw.slot.begin(), sw.slot.end(), h_slot.begin() + gp.row_base);
+        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
+        std::copy(sw.pred_slot.begin(), sw.pred_slot.end(), h_pred_slot.begin() + gp.edge_base);
+        std::copy(gp.ckpt.pred_src.begin(), gp.ckpt.pred_src.end(), h_pred_src.begin() + gp.edge_base);
+        std::copy(gp.ckpt.snap_off.begin(), gp.ckpt.snap_off.end(), h_snap_off.begin() + gp.snap_off_base);
+        std::copy(gp.ckpt.snap_dst.begin(), gp.ckpt.snap_dst.end(), h_snap_dst.begin() + gp.snap_dst_base);
+        std::copy(gp.ckpt.boundary.begin(), gp.ckpt.boundary.end(), h_boundary.begin() + gp.boundary_base);
+    }
+
+    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
+    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
+    HIP_TRY(m->d_slot.alloc(std::max<size_t>(h_slot.size(), 1)));
+    HIP_TRY(m->d_pred_slot.alloc(std::max<size_t>(h_pred_slot.size(), 1)));
+    HIP_TRY(b->d_ck_pred_src.alloc(std::max<size_t>(h_pred_src.size(), 1)));
+    HIP_TRY(b->d_ck_snap_off.alloc(std::max<size_t>(h_snap_off.size(), 1)));
+    HIP_TRY(b->d_ck_snap_dst.alloc(std::max<size_t>(h_snap_dst.size(), 1)));
+    HIP_TRY(b->d_ck_boundary.alloc(std::max<size_t>(h_boundary.size(), 1)));
+    HIP_TRY(m->d_graph_of.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(m->d_carry_off.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(m->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
+    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n], 1)));
+    HIP_TRY(b->d_qoff.alloc((size_t)n + 1));
+    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_scratch_off.alloc((size_t)n + 1));
+    HIP_TRY(b->d_pair_off.alloc((size_t)n + 1));
+    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
+    HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
+    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>(pl.max_carry_words, 1)));
+    HIP_TRY(b->d_pipeline_error.alloc(1));
+    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
+    if (n) {
+        std::string werr;
+        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "checkpointed workspace: " + werr);
+    }
+
+    std::vector<MultiGraphParams> h_params(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        MultiGraphParams& mp = h_params[g];
+        std::memset(&mp, 0, sizeof(mp));
+        CkptParams& kp = mp.P;
+        kp.rows = b->d_rows.p + gp.row_base; kp.slot = m->d_slot.p + gp.row_base;
+        kp.pred_rows = b->d_pred_rows.p + gp.edge_base; kp.pred_slot = m->d_pred_slot.p + gp.edge_base; kp.pred_src = b->d_ck_pred_src.p + gp.edge_base;
+        kp.snap_off = b->d_ck_snap_off.p + gp.snap_off_base; kp.snap_dst = b->d_ck_snap_dst.p + gp.snap_dst_base;
+        kp.boundary = b->d_ck_boundary.p + gp.boundary_base;
+        kp.n_rows = fg.n; kp.n_slots = gp.n_slots; kp.n_snap = gp.ckpt.n_snap_rows; kp.seg_rows = gp.ckpt.max_segment; kp.n_segments = gp.ckpt.n_segments();
+        kp.start_row = fg.start_row; kp.end_row = fg.end_row;
+        kp.qseq = b->d_qseq.p; kp.qoff = b->d_qoff.p; kp.pitch = b->d_pitch.p; kp.plane_off = b->plan[0].d_off.p;
+        kp.planes = b->d_planes.p; kp.carry = b->d_carry.p;
+        kp.scratch_off = b->d_scratch_off.p; kp.scratch = b->d_scratch.p;
+        kp.score = b->d_score.p; kp.flags = b->d_flags.p; kp.n_pairs = b->d_npairs.p;
+        mp.empty = fg.n_real == 0 ? 1u : 0u;
+    }
+
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
+    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
+    HIP_TRY(up(m->d_slot.p, h_slot.data(), h_slot.size() * 4));
+    HIP_TRY(up(m->d_pred_slot.p, h_pred_slot.data(), h_pred_slot.size() * 4));
+    HIP_TRY(up(b->d_ck_pred_src.p, h_pred_src.data(), h_pred_src.size() * 4));
+    HIP_TRY(up(b->d_ck_snap_off.p, h_snap_off.data(), h_snap_off.size() * 4));
+    HIP_TRY(up(b->d_ck_snap_dst.p, h_snap_dst.data(), h_snap_dst.size() * 4));
+    HIP_TRY(up(b->d_ck_boundary.p, h_boundary.data(), h_boundary.size() * 4));
+    HIP_TRY(up(m->d_params.p, h_params.data(), h_params.size() * sizeof(MultiGraphParams)));
+    HIP_TRY(up(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    HIP_TRY(up(m->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
+    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n]));
+    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n + 1) * 8));
+    HIP_TRY(up(b->d_scratch_off.p, pl.scratch_off.data(), ((size_t)n + 1) * 8));
+    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
+    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+
+    *out = m.release();
+    return POA_OK;
+}
+
+// per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2), over the queries of all graphs; scan and
+// compaction of the pairs over all queries, as run_ckpt does for one graph
+int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
+    if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: null argument");
+    const int mrc = multi_mode_check(cfg, "poa_multi_run");
+    if (mrc != POA_OK) return mrc;
+    const TuneView T(cfg);
+    poa_batch* b = &m->core;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(b->device));
+    b->last_mode = POA_MODE_CHECKPOINT;
+    b->two_piece = false;
+    b->last_stream = stream;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_multi_run: call poa_multi_stats/fetch at least every 256 runs");
+    // u16 cells only if every graph's own bound (run_ckpt's ub, with that graph's longest query and shortest path) allows them
+    bool narrow = true;
+    for (size_t g = 0; g < m->ub_open.size(); ++g)
+        narrow = narrow && (uint64_t)costs->gap_open * m->ub_open[g] + (uint64_t)costs->gap_extend * m->ub_extend[g] <= 65534;
+    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = 0;
+    const MultiPlan& pl = m->plan;
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * pl.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    b->sweep_bytes_written = m->stored_rows_pitch * (narrow ? 2 : 4);
+    size_t ev = 1;
+    for (const auto& ch : pl.chunks) {
+        MultiLaunch ml;
+        ml.graphs = m->d_params.p; ml.graph_of = m->d_graph_of.p; ml.carry_off = m->d_carry_off.p; ml.carry = b->d_carry.p;
+        ml.first_query = ch.first; ml.n_queries = ch.count;
+        ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
+        const uint32_t max_pitch = ch.max_pitch;
+        const dim3 grid((ch.count + 3) / 4), block(256);
+        // Q follows the chunk's largest pitch, as LAUNCH_CKPT does for a single graph
+#define LAUNCH_CKPT_MULTI(KERNEL)                                                                        \
+    do {                                                                                                \
+        if (narrow) {                                                                                   \
+            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<1, uint16_t>), grid, block, 0, stream, ml); \
+            else hipLaunchKernelGGL((KERNEL<2, uint16_t>), grid, block, 0, stream, ml);                  \
+        } else {                                                                                        \
+            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<1, uint32_t>), grid, block, 0, stream, ml); \
+            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<2, uint32_t>), grid, block, 0, stream, ml); \
+            else hipLaunchKernelGGL((KERNEL<4, uint32_t>), grid, block, 0, stream, ml);                  \
+        }                                                                                               \
+    } while (0)
+        LAUNCH_CKPT_MULTI(poa_ckpt_sweep_multi_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        LAUNCH_CKPT_MULTI(poa_ckpt_trace_multi_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+#undef LAUNCH_CKPT_MULTI
+    }
+    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
+int poa_multi_fetch(poa_multi_t* m, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
+                    uint32_t* flags, poa_stats_t* stats) {
+    if (!m) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch: null batch");
+    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch: poa_multi_run has not been called");
+    return poa_batch_fetch(&m->core, score, pairs, pair_off, pair_capacity, flags, stats);
+}
+
+int poa_multi_stats(poa_multi_t* m, poa_stats_t* stats) {
+    if (!m || !stats) return fail(POA_ERR_INVALID_ARG, "poa_multi_stats: null argument");
+    return poa_batch_stats(&m->core, stats);
+}
+
+int poa_multi_device_results(poa_multi_t* m, void** score, void** flags, void** pair_off, void** pairs) {
+    if (!m) return fail(POA_ERR_INVALID_ARG, "poa_multi_device_results: null batch");
+    return poa_batch_device_results(&m->core, score, flags, pair_off, pairs);
+}
+
+int poa_multi_workspace_bytes(poa_multi_t* m, uint64_t* bytes) {
+    if (!m || !bytes) return fail(POA_ERR_INVALID_ARG, "poa_multi_workspace_bytes: null argument");
+    *bytes = m->core.d_planes.bytes;
+    return POA_OK;
+}
+
+void poa_multi_destroy(poa_multi_t* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->core.device);
+    if (m->core.ran) (void)hipStreamSynchronize(m->core.last_stream);  // the plane workspace may be handed to another batch next
+    delete m;
+}
+
+int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs_t* costs,
+                    const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs,
+                    uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi: null argument");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    poa_multi_t* m = nullptr;
+    int rc = poa_multi_create(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
+    if (rc != POA_OK) return rc;
+    rc = poa_multi_run(m, costs, cfg, nullptr);
+    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
+    poa_multi_destroy(m);
+    return rc;
+}
+
+}  // extern "C"

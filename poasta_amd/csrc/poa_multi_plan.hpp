@@ -1,0 +1,81 @@
+// Host-side plan of a multi-graph checkpointed batch (poa_multi_*, poa_multi.hpp).  Host code, no device needed.
+//
+// A multi-graph batch runs the queries of MANY graphs in one launch of the checkpointed kernels (poa_checkpoint.hpp): one
+// wavefront per query, each wave reading the tables of its own query's graph.  Queries are grouped by graph: graph g owns the
+// queries [graph_qoff[g], graph_qoff[g + 1]).  The plan says where everything lies:
+//
+//   per graph    its CheckpointPlan — what poa_graph_checkpoint_plan gives for that graph alone at the batch's segment length —
+//                and the bases of its tables in the CONCATENATED device tables.  Four index spaces: rows (RowMeta, slot; n_rows
+//                entries per graph), edges (pred_rows, pred_slot, pred_src), snap_off (n_rows + 1 entries: a CSR of its own, which
+//                indexes snap_dst from that graph's snap_dst base) and boundary (n_segments + 1).  The values in the tables stay
+//                graph-local (row 0 is the graph's first row): a wave addresses them from its graph's base pointers, so the
+//                kernels' bodies see exactly the tables a single-graph batch would hand them.  A handle listed more than once
+//                has one copy of its tables.
+//   per query    graph id; pitch = columns rounded up to 64 (the rule of a single-graph batch); the offset of its region in the
+//                plane workspace, in 4-byte cells and relative to its chunk: a query holds rows_per_query(graph) x pitch cells
+//                + 256 bytes of padding; the offset of its pair scratch, capacity len + n_rows(graph).
+//   chunks       greedy in query order by that footprint under `workspace_bytes`: a chunk is closed in front of the first query
+//                that no longer fits.  A boundary may fall inside a graph's range or between two graphs; a graph without queries
+//                never shows.  The offsets are in cells of the run's cell type: a u16 run uses the same numbers, i.e. the
+//                first half of every region's bytes.
+//   strip carries  pass 1 hands the insertion value and the last column's M from strip to strip through two parities of
+//                2 x n_rows words per query (ckpt_rows: carry + parity * 2 * n_rows + 2 * row).  With graphs of different n_rows
+//                a common stride would have to be 4 x the LARGEST n_rows in the batch for every query; instead every query has
+//                its own offset, carry_off[q], into the chunk's carry buffer, and only a query wider than one strip of the
+//                widest kernel variant (pitch > 1024 columns: 64 lanes x 8 u16 cells x Q 2, or x 4 u32 cells x Q 4) takes
+//                4 x n_rows(graph) words there.  Every variant the launch code selects for a chunk has strips of at least the
+//                chunk's largest pitch when that pitch is <= 1024, so a query of pitch <= 1024 never touches a carry.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "poa_sweep_rows.hpp"
+
+namespace poa_amd {
+
+constexpr uint32_t MULTI_STRIP_COLUMNS = 1024;   // widest strip of the checkpointed kernels, both cell types
+constexpr uint64_t MULTI_REGION_PAD_CELLS = 64;  // 256 bytes behind every query's region
+
+struct MultiGraphIn {            // what the plan reads of a graph handle
+    const FlatGraph* g;
+    const SweepRows* sweep;
+    const CheckpointPlan* own;   // the handle's plan at the engine's own segment length
+};
+
+struct MultiGraphPlan {
+    CheckpointPlan ckpt;
+    uint32_t table_of = 0;       // first listing of the same handle: it owns the tables, this listing shares its bases
+    uint32_t n_rows = 0, n_edges = 0, n_slots = 0;
+    uint64_t row_base = 0, edge_base = 0, snap_off_base = 0, snap_dst_base = 0, boundary_base = 0;
+    uint64_t max_len = 0;        // longest query of this graph (0: none)
+    uint32_t n_queries = 0;
+};
+
+struct MultiPlan {
+    struct Chunk { uint32_t first, count; uint64_t cells; uint64_t carry_words; uint32_t max_pitch; };
+    uint32_t n_queries = 0;
+    std::vector<MultiGraphPlan> graphs;
+    uint64_t n_rows_total = 0, n_edges_total = 0, n_snap_off_total = 0, n_snap_dst_total = 0, n_boundary_total = 0;
+    std::vector<uint32_t> graph_of, pitch, carry_off;   // [n]
+    std::vector<uint64_t> region_off;                   // [n] 4-byte cells from the start of the query's chunk
+    std::vector<uint64_t> scratch_off;                  // [n + 1] pairs
+    std::vector<Chunk> chunks;
+    uint64_t bytes_total = 0;           // the whole batch as one chunk
+    uint64_t largest_query_bytes = 0;
+    uint64_t workspace_bytes = 0;       // the largest chunk: what the batch holds
+    uint64_t max_carry_words = 0;       // the largest chunk's carries
+    uint64_t total_cells = 0, total_bases = 0;
+};
+
+// 4-byte cells a query of `len` symbols holds on a graph with that plan, padding included
+inline uint64_t multi_query_cells(const CheckpointPlan& cp, uint64_t len) {
+    return (uint64_t)cp.rows_per_query * (((len + 1 + 63) / 64) * 64) + MULTI_REGION_PAD_CELLS;
+}
+
+// workspace_bytes 0: no cap (one chunk).  A cap below the largest query's footprint is raised to it.
+// Returns 0, or -1 (invalid argument) / -7 (unsupported) — the values of POA_ERR_INVALID_ARG / POA_ERR_UNSUPPORTED — with `err` set.
+int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                     uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err);
+
+}  // namespace poa_amd

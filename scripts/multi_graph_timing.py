@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Many small graphs: one multi-graph batch against the per-graph loops, one process, one GPU, interleaved repetitions.
+
+Workload: 256 graphs of about 200 rows (LinearishPOA at a backbone of 190), 32 reads of about 200 bp each, fixed seeds,
+costs 4 / 6 / 2.  Per step, with the pairs fetched:
+  (a)  poa_multi_run + poa_multi_fetch on a resident multi-graph batch; (a1) the one-shot poa_align_multi, which also creates
+       and destroys the batch, as the loops below do per graph;
+  (b)  the loop over the graphs of poa_align_batch_ex in POA_MODE_CHECKPOINT;
+  (c)  the same loop in dense mode.
+(b) and (c) are the paths a host had before.  The first --warmup steps are dropped; medians with min / max of the rest.  Kernel-only
+times are the HIP-event sums of poa_stats_t (ms_forward, ms_traceback), summed over the calls of a step.  Writes
+profiles/pr_multi_graph/timing.json.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--graphs", type=int, default=256)
+    ap.add_argument("--reads", type=int, default=32)
+    ap.add_argument("--length", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=11)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pr_multi_graph", "timing.json"))
+    args = ap.parse_args()
+    import numpy as np
+    from poasta_amd import _lib, aligner, workloads as W
+
+    graphs, packed, seqs = [], [], []
+    for k in range(args.graphs):
+        g, (qseq, qoff) = W.scaled_linearish(190, 10, 5, args.reads, args.length, graph_seed=100 + k, query_seed=5000 + k)
+        graphs.append(g)
+        packed.append((qseq, qoff))
+        seqs.append([qseq[int(qoff[i]):int(qoff[i + 1])] for i in range(args.reads)])
+    dgs = [aligner._device_graph(g) for g in graphs]
+    costs = aligner.GapAffine(4, 2, 6)
+    c = costs._c()
+    L = _lib.lib()
+    n_total = args.graphs * args.reads
+    cells = sum(g.n * (int(qoff[-1]) + args.reads) for g, (_, qoff) in zip(graphs, packed))
+
+    mb = aligner.MultiGraphBatch(graphs, seqs)
+    al = aligner.PoastaAligner(aligner.AffineMinGapCost(costs))
+
+    def step_multi():
+        mb.run(costs)
+        r = mb.fetch()
+        return r, r.stats["ms_forward"], r.stats["ms_traceback"]
+
+    def step_one_shot():
+        r = al.align_multi(graphs, seqs)
+        return r, r.stats["ms_forward"], r.stats["ms_traceback"]
+
+    def loop(mode):
+        cfg = aligner.make_config(mode)
+
+        def step():
+            score, flags, pairs, counts = [], [], [], []
+            fwd = tb = 0.0
+            for dg, (qseq, qoff) in zip(dgs, packed):
+                n = len(qoff) - 1
+                cap = int(qoff[-1]) + n * dg.graph.n
+                s, f, po = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n + 1, np.uint64)
+                pr = np.zeros((cap, 2), np.uint32)
+                st = _lib.PoaStats()
+                _lib.check(L.poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, aligner._p(qseq), aligner._p(qoff), aligner._p(s),
+                                                aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st), 0))
+                fwd += st.ms_forward
+                tb += st.ms_traceback
+                score.append(s); flags.append(f); pairs.append(pr[:int(po[n])]); counts.append(np.diff(po.astype(np.int64)))
+            off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.uint64)
+            return aligner.BatchResult(np.concatenate(score), np.concatenate(pairs), off, np.concatenate(flags), {}), fwd, tb
+        return step
+
+    paths = {"multi_run_fetch": step_multi, "multi_one_shot": step_one_shot, "loop_checkpoint": loop("checkpoint"), "loop_dense": loop("dense")}
+    rows = {k: [] for k in paths}
+    sums = {}
+    for rep in range(args.warmup + args.steps):
+        for name, step in paths.items():
+            t0 = time.perf_counter()
+            res, fwd, tb = step()
+            wall = (time.perf_counter() - t0) * 1e3
+            if rep >= args.warmup:
+                rows[name].append((wall, fwd, tb))
+            sums[name] = {"score_sum": int(res.score.astype(np.uint64).sum()), "flags_crc32": zlib.crc32(res.flags.tobytes()),
+                          "n_pairs": int(res.pair_off[-1]), "pairs_crc32": zlib.crc32(np.ascontiguousarray(res.pairs).tobytes())}
+            del res
+
+    def med(v):
+        v = sorted(v)
+        return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+    out = {"workload": "%d graphs x %d reads of %d bp, LinearishPOA backbone 190" % (args.graphs, args.reads, args.length),
+           "costs": "4 / 6 / 2 (mismatch / open / extend)", "graphs": args.graphs, "queries": n_total,
+           "rows_per_graph": {"min": min(g.n for g in graphs), "max": max(g.n for g in graphs)}, "cells": cells,
+           "steps": args.steps, "warmup": args.warmup, "multi_workspace_bytes": mb.workspace_bytes(),
+           "multi_footprint_bytes": aligner.multi_footprint(graphs, seqs)[0],
+           "results_equal": all(sums[k] == sums["loop_dense"] for k in sums)}
+    for name in paths:
+        out[name] = {"ms_step": med([r[0] for r in rows[name]]), "ms_forward_kernels": med([r[1] for r in rows[name]]),
+                     "ms_traceback_kernels": med([r[2] for r in rows[name]])}
+        out[name].update(sums[name])
+    for name in ("multi_run_fetch", "multi_one_shot"):
+        for base in ("loop_checkpoint", "loop_dense"):
+            out["ms_step_ratio_%s_over_%s" % (name, base)] = round(out[name]["ms_step"]["median"] / out[base]["ms_step"]["median"], 4)
+    mb.close()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if out["results_equal"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
