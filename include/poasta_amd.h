@@ -445,6 +445,65 @@ int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const u
                     uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags,
                     poa_stats_t* stats, int device);
 
+/* ---- score set: score-only runs over (query, graph) pairs of many graphs ------------------- */
+/* For the question that comes before the alignment — which of these graphs does a read belong to (read-to-family assignment,
+ * choosing the window or haplotype graph before a POA build, demultiplexing against amplicon graphs): one launch per kernel
+ * class covers every pair, one wavefront per pair, each wave reading its own pair's graph's tables.  The winners then go to
+ * poa_multi_* for their alignments.
+ *   graphs[n_graphs]          graph handles; the same handle may be listed more than once (its tables are uploaded once)
+ *   qseq / qoff[n_queries+1]  the pool of queries, uploaded once however many pairs name them
+ *   pair_query[n_pairs],      u32 indices into the query pool and the graph list, in any order, with repeats; a graph or a
+ *   pair_graph[n_pairs]       query may have no pair at all.  Both NULL and n_pairs == n_queries * n_graphs: the full matrix,
+ *                             pair p = (query p / n_graphs, graph p % n_graphs).  n_pairs == 0 is valid and returns nothing.
+ *   cfg                       NULL or mode POA_MODE_SCORE, the only mode.  Every other mode, and POA_SPAN_ENDS_FREE:
+ *                             POA_ERR_UNSUPPORTED.  tune[POA_TUNE_PLANES] and tune[POA_TUNE_PX] apply to a run, as they do to
+ *                             a score-mode poa_batch_run_ex.
+ * Results are in pair order: score[p] and flags[p] are, bit for bit, what poa_align_batch_ex in POA_MODE_SCORE returns for that
+ * query against that graph alone (poa_scoreset_run), or poa_align_batch_2piece_ex in that mode (poa_scoreset_run_2piece, through
+ * the cost equivalence open' = open1 + extend1 - extend2, extend' = extend2 of DESIGN.md §6a): dense mode's score; flags carry
+ * only POA_FLAG_EMPTY_GRAPH and POA_FLAG_SHORT_QUERY; a pair against a graph without real nodes gets score 4 * len and
+ * POA_FLAG_EMPTY_GRAPH.  The two runs may alternate on one set, with other costs each time.
+ * POA_ERR_INVALID_ARG: a pair index out of range, a NULL graph or array (other than the both-NULL matrix form), an n_pairs that
+ * does not match the matrix form, poa_scoreset_fetch before a run, gap_extend1 < gap_extend2.
+ * Memory: a pair holds max(n_slots(its graph), 1) x pitch 4-byte cells of M and of D + 256 bytes (poa_graph_sweep_slots; pitch =
+ * len + 1 rounded up to 64) — the per-query rule of a score-mode batch with the pair's own graph's n_slots.
+ * poa_scoreset_footprint returns the sum over all pairs (the set as one chunk) and its largest term, on the host, without a
+ * device.  poa_scoreset_create takes workspace_bytes as a cap (0: the whole set, or what free device memory allows; a cap below
+ * the largest pair is raised to it) and cuts the pairs into chunks greedily in pair order.  The set is sized for u32 cells.
+ * The cell width of a run is u16 only if EVERY graph that appears in a pair allows it — [open + extend x the longest query
+ * paired with it] + [open + extend x its shortest path] <= 65534, with the reduced costs for the two-piece run — and
+ * tune[POA_TUNE_PLANES] is not 32; else u32 for the whole run.  Both are exact: results do not depend on it.
+ * Carries between strips (pairs of more than 1024 columns only): 16 bytes per graph row of such a pair in flight.
+ * poa_scoreset_run* launch on `stream` (a hipStream_t, NULL = default stream) without synchronising; after the set's creation
+ * a run allocates nothing on the device.  poa_stats_t counts pairs: n_queries = n_pairs, cells = sum rows(graph) x (len + 1),
+ * plane_bytes = the slot bytes the last run stored.  poa_graph_update on a member graph after poa_scoreset_create: the set
+ * keeps the tables it copied and must not be run again.  A poa_scoreset_t belongs to one thread at a time. */
+typedef struct poa_scoreset poa_scoreset_t;
+/* host only, no device: bytes of slot workspace for the whole set as one chunk, and of its largest pair */
+int poa_scoreset_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff,
+                           uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph, const poa_config_t* cfg,
+                           uint64_t* bytes, uint64_t* largest_pair_bytes);
+int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int device, uint32_t n_queries, const uint8_t* qseq,
+                        const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph,
+                        const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out);
+int poa_scoreset_run(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);
+int poa_scoreset_run_2piece(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream);
+/* synchronises; score[n_pairs], flags[n_pairs] (may be NULL) in pair order */
+int poa_scoreset_fetch(poa_scoreset_t* s, uint32_t* score, uint32_t* flags, poa_stats_t* stats);
+int poa_scoreset_stats(poa_scoreset_t* s, poa_stats_t* stats);
+int poa_scoreset_device_results(poa_scoreset_t* s, void** score, void** flags);
+/* bytes of the slot workspace the set holds: its largest chunk */
+int poa_scoreset_workspace_bytes(poa_scoreset_t* s, uint64_t* bytes);
+void poa_scoreset_destroy(poa_scoreset_t* s);
+/* one-shot: create, run, fetch, destroy */
+int poa_score_pairs(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_config_t* cfg,
+                    uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query,
+                    const uint32_t* pair_graph, uint32_t* score, uint32_t* flags, poa_stats_t* stats, int device);
+int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs2_t* costs, const poa_config_t* cfg,
+                           uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs,
+                           const uint32_t* pair_query, const uint32_t* pair_graph, uint32_t* score, uint32_t* flags,
+                           poa_stats_t* stats, int device);
+
 #ifdef __cplusplus
 }
 #endif

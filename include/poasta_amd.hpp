@@ -23,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "poasta_amd.h"
@@ -439,6 +440,56 @@ private:
     poa_batch_t* b_ = nullptr;
     uint32_t n_;
     uint64_t cap_ = 0;
+};
+
+// (query, graph) pairs resident in HBM (poa_scoreset_*): one score-only run covers all of them.  `pairs` holds (index into
+// seqs, index into graphs) in any order, with repeats; empty: the full matrix, pair p = (p / graphs.size(), p % graphs.size()).
+// run() takes the one-piece or the two-piece costs, one set may alternate them; fetch() returns score and flags in pair order.
+class ScoreSet {
+public:
+    struct Result { std::vector<uint32_t> score, flags; };
+    ScoreSet(const std::vector<const graphs::POAGraph*>& graphs, const std::vector<std::string>& seqs,
+             const std::vector<std::pair<uint32_t, uint32_t>>& pairs = {}, int device = 0, uint64_t workspace_bytes = 0) {
+        std::vector<const poa_graph_t*> handles;
+        for (const graphs::POAGraph* g : graphs) handles.push_back(g->device_graph());
+        std::vector<uint64_t> qoff(seqs.size() + 1, 0);
+        std::string qseq;
+        for (size_t i = 0; i < seqs.size(); ++i) { qseq += seqs[i]; qoff[i + 1] = qseq.size(); }
+        std::vector<uint32_t> pq, pg;
+        for (const auto& p : pairs) { pq.push_back(p.first); pg.push_back(p.second); }
+        n_ = pairs.empty() ? (uint64_t)seqs.size() * graphs.size() : pairs.size();
+        if (poa_scoreset_create(handles.data(), (uint32_t)handles.size(), device, (uint32_t)seqs.size(), (const uint8_t*)qseq.data(), qoff.data(),
+                                n_, pairs.empty() ? nullptr : pq.data(), pairs.empty() ? nullptr : pg.data(), nullptr, workspace_bytes, &s_) != POA_OK)
+            throw PoastaError(std::string("poa_scoreset_create: ") + poa_last_error());
+    }
+    ScoreSet(const ScoreSet&) = delete;
+    ScoreSet& operator=(const ScoreSet&) = delete;
+    ~ScoreSet() { poa_scoreset_destroy(s_); }
+
+    void run(const GapAffine& costs, void* stream = nullptr, const poa_config_t* cfg = nullptr) {
+        const poa_costs_t c{costs.mismatch(), costs.gap_open(), costs.gap_extend(), 0};
+        if (poa_scoreset_run(s_, &c, cfg, stream) != POA_OK) throw PoastaError(std::string("poa_scoreset_run: ") + poa_last_error());
+    }
+    void run(const GapAffine2Piece& costs, void* stream = nullptr, const poa_config_t* cfg = nullptr) {
+        poa_costs2_t c{};
+        c.mismatch = costs.mismatch(); c.gap_open1 = costs.gap_open(); c.gap_extend1 = costs.gap_extend();
+        c.gap_open2 = costs.gap_open2(); c.gap_extend2 = costs.gap_extend2();
+        if (poa_scoreset_run_2piece(s_, &c, cfg, stream) != POA_OK) throw PoastaError(std::string("poa_scoreset_run_2piece: ") + poa_last_error());
+    }
+    // synchronises the stream of the last run and copies its results to the host
+    Result fetch(poa_stats_t* stats = nullptr) {
+        Result r;
+        r.score.resize(n_); r.flags.resize(n_);
+        if (poa_scoreset_fetch(s_, r.score.data(), r.flags.data(), stats) != POA_OK)
+            throw PoastaError(std::string("poa_scoreset_fetch: ") + poa_last_error());
+        return r;
+    }
+    uint64_t size() const { return n_; }
+    poa_scoreset_t* handle() const { return s_; }
+
+private:
+    poa_scoreset_t* s_ = nullptr;
+    uint64_t n_ = 0;
 };
 
 }  // namespace aligner

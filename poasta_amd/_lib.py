@@ -25,7 +25,10 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
            "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
            "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
-           "poa_multi_workspace_bytes", "poa_multi_destroy", "poa_align_multi"]
+           "poa_multi_workspace_bytes", "poa_multi_destroy", "poa_align_multi",
+           "poa_scoreset_footprint", "poa_scoreset_create", "poa_scoreset_run", "poa_scoreset_run_2piece", "poa_scoreset_fetch",
+           "poa_scoreset_stats", "poa_scoreset_device_results", "poa_scoreset_workspace_bytes", "poa_scoreset_destroy",
+           "poa_score_pairs", "poa_score_pairs_2piece"]
 
 
 class PoaCosts2(C.Structure):
@@ -199,6 +202,33 @@ def lib():
     L.poa_align_multi.restype = C.c_int
     L.poa_align_multi.argtypes = [vp, C.c_uint32, vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp, vp, vp, vp, vp, C.c_uint64, vp,
                                   C.POINTER(PoaStats), C.c_int]
+    # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)
+    L.poa_scoreset_footprint.restype = C.c_int
+    L.poa_scoreset_footprint.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]
+    L.poa_scoreset_create.restype = C.c_int
+    L.poa_scoreset_create.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.c_uint64,
+                                      C.POINTER(vp)]
+    L.poa_scoreset_run.restype = C.c_int
+    L.poa_scoreset_run.argtypes = [vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp]
+    L.poa_scoreset_run_2piece.restype = C.c_int
+    L.poa_scoreset_run_2piece.argtypes = [vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp]
+    L.poa_scoreset_fetch.restype = C.c_int
+    L.poa_scoreset_fetch.argtypes = [vp, vp, vp, C.POINTER(PoaStats)]
+    L.poa_scoreset_stats.restype = C.c_int
+    L.poa_scoreset_stats.argtypes = [vp, C.POINTER(PoaStats)]
+    L.poa_scoreset_device_results.restype = C.c_int
+    L.poa_scoreset_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.poa_scoreset_workspace_bytes.restype = C.c_int
+    L.poa_scoreset_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.poa_scoreset_destroy.argtypes = [vp]
+    L.poa_scoreset_destroy.restype = None
+    L.poa_score_pairs.restype = C.c_int
+    L.poa_score_pairs.argtypes = [vp, C.c_uint32, C.POINTER(PoaCosts), C.POINTER(PoaConfig), C.c_uint32, vp, vp, C.c_uint64, vp, vp, vp, vp,
+                                  C.POINTER(PoaStats), C.c_int]
+    L.poa_score_pairs_2piece.restype = C.c_int
+    L.poa_score_pairs_2piece.argtypes = [vp, C.c_uint32, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), C.c_uint32, vp, vp, C.c_uint64, vp, vp,
+                                         vp, vp, C.POINTER(PoaStats), C.c_int]
     _lib = L
     return L
 

@@ -511,6 +511,103 @@ class MultiGraphBatch:
             pass
 
 
+class _ScoreSetInput:
+    """graphs + a pool of queries + (query, graph) pairs as the arrays poa_scoreset_* take.  pairs None: the full matrix."""
+
+    def __init__(self, graphs, seqs=None, qseq=None, qoff=None, pairs=None):
+        self.dgs = [_device_graph(g) for g in graphs]
+        if seqs is not None:
+            qseq, qoff = pack_queries(seqs)
+        self.qseq = np.ascontiguousarray(qseq, np.uint8)
+        self.qoff = np.ascontiguousarray(qoff, np.uint64)
+        self.n_queries = len(self.qoff) - 1
+        self.n_graphs = len(self.dgs)
+        self.handles = (C.c_void_p * max(self.n_graphs, 1))(*[dg.handle for dg in self.dgs])
+        if pairs is None:
+            self.pair_query = self.pair_graph = None
+            self.n = self.n_queries * self.n_graphs
+        else:
+            pr = np.asarray(pairs, np.int64).reshape(-1, 2)
+            # the C ABI checks these too; here the caller gets the offending pair named in Python terms
+            bad = np.flatnonzero((pr[:, 0] < 0) | (pr[:, 0] >= self.n_queries) | (pr[:, 1] < 0) | (pr[:, 1] >= self.n_graphs))
+            if len(bad):
+                raise ValueError("pair %d = (query %d, graph %d) is out of range (%d queries, %d graphs)"
+                                 % (int(bad[0]), int(pr[bad[0], 0]), int(pr[bad[0], 1]), self.n_queries, self.n_graphs))
+            self.pair_query = np.ascontiguousarray(pr[:, 0], np.uint32)
+            self.pair_graph = np.ascontiguousarray(pr[:, 1], np.uint32)
+            self.n = len(pr)
+
+    def pair_args(self):
+        return self.n, _p(self.pair_query), _p(self.pair_graph)
+
+
+def scoreset_footprint(graphs, seqs=None, qseq=None, qoff=None, pairs=None, config=None):
+    """(bytes, largest_pair_bytes) of a score set: the slot workspace of the whole set as one chunk and of its largest pair
+    (poa_scoreset_footprint; host only)."""
+    si = _ScoreSetInput(graphs, seqs, qseq, qoff, pairs)
+    total, largest = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().poa_scoreset_footprint(si.handles, si.n_graphs, si.n_queries, _p(si.qoff), *si.pair_args(),
+                                                 C.byref(config) if config is not None else None, C.byref(total), C.byref(largest)))
+    return int(total.value), int(largest.value)
+
+
+class ScoreSet:
+    """(query, graph) pairs resident in HBM (`poa_scoreset_*`): one score-only run covers all of them, one wavefront per pair.
+    graphs: the graph list; seqs (or packed qseq / qoff): the pool of queries, uploaded once; pairs: an [n, 2] array of
+    (query index, graph index) in any order, with repeats — None: the full queries x graphs matrix, pair p = (p // n_graphs,
+    p % n_graphs).  Results come back in pair order."""
+
+    def __init__(self, graphs, seqs=None, qseq=None, qoff=None, pairs=None, workspace_bytes=0, config=None, device=0):
+        si = _ScoreSetInput(graphs, seqs, qseq, qoff, pairs)
+        self.input, self.n, self.n_queries, self.n_graphs = si, si.n, si.n_queries, si.n_graphs
+        h = C.c_void_p()
+        _lib.check(_lib.lib().poa_scoreset_create(si.handles, si.n_graphs, device, si.n_queries, _p(si.qseq), _p(si.qoff), *si.pair_args(),
+                                                  C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
+        self.handle = h
+
+    def run(self, costs, stream=None, config=None):
+        """Launch on `stream` without synchronising.  costs: GapAffine (poa_scoreset_run) or GapAffine2Piece
+        (poa_scoreset_run_2piece); config: None or make_config("score", ...)."""
+        c = costs._c()
+        if config is None:
+            config = make_config("score")   # (carries the POA_<NAME> overrides, if any are set)
+        fn = _lib.lib().poa_scoreset_run_2piece if isinstance(costs, GapAffine2Piece) else _lib.lib().poa_scoreset_run
+        _lib.check(fn(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+
+    def fetch(self):
+        """Synchronise; (score, flags, stats): u32 arrays in pair order and the poa_stats_t of the runs since the last call."""
+        score, flags = np.zeros(self.n, np.uint32), np.zeros(self.n, np.uint32)
+        st = _lib.PoaStats()
+        _lib.check(_lib.lib().poa_scoreset_fetch(self.handle, _p(score), _p(flags), C.byref(st)))
+        return score, flags, st.as_dict()
+
+    def stats(self):
+        st = _lib.PoaStats()
+        _lib.check(_lib.lib().poa_scoreset_stats(self.handle, C.byref(st)))
+        return st.as_dict()
+
+    def workspace_bytes(self):
+        v = C.c_uint64(0)
+        _lib.check(_lib.lib().poa_scoreset_workspace_bytes(self.handle, C.byref(v)))
+        return int(v.value)
+
+    def device_results(self):
+        ptrs = [C.c_void_p() for _ in range(2)]
+        _lib.check(_lib.lib().poa_scoreset_device_results(self.handle, *[C.byref(p) for p in ptrs]))
+        return dict(zip(("score", "flags"), [p.value for p in ptrs]))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.lib().poa_scoreset_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PoastaAligner:
     """`PoastaAligner::new(config, aln_type)` (mod.rs:53)."""
 
@@ -626,3 +723,25 @@ class PoastaAligner:
         if want_pairs:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())
+
+    def score_pairs(self, graphs, seqs, pairs):
+        """Scores of (query, graph) pairs over many graphs in one score-only run (poa_score_pairs): pairs is an [n, 2] array of
+        (index into seqs, index into graphs), None for the full matrix.  Returns (score, flags) in pair order: what score_batch
+        gives for that query against that graph alone."""
+        if self.aln_type != AlignmentType.Global:
+            raise ValueError("score_pairs: AlignmentType.Global only")
+        si = _ScoreSetInput(graphs, seqs, pairs=pairs)
+        score, flags = np.zeros(si.n, np.uint32), np.zeros(si.n, np.uint32)
+        st = _lib.PoaStats()
+        c = self.config.costs._c()
+        cfg = make_config("score", self.config.heuristic)
+        fn = _lib.lib().poa_score_pairs_2piece if getattr(self.config, "two_piece", False) else _lib.lib().poa_score_pairs
+        _lib.check(fn(si.handles, si.n_graphs, C.byref(c), C.byref(cfg), si.n_queries, _p(si.qseq), _p(si.qoff), *si.pair_args(),
+                      _p(score), _p(flags), C.byref(st), self.device))
+        self.last_stats = st.as_dict()
+        return score, flags
+
+    def score_matrix(self, graphs, seqs):
+        """The full queries x graphs matrix of scores, a [n_queries, n_graphs] u32 array (score_pairs with pairs=None)."""
+        score, _ = self.score_pairs(graphs, seqs, None)
+        return score.reshape(len(seqs), len(graphs))

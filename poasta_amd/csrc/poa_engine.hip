@@ -38,6 +38,8 @@ struct TuneView {
 #include "poa_checkpoint2.hpp"
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
+#include "poa_scoreset_plan.hpp"
+#include "poa_scoreset.hpp"
 
 using namespace poa_amd;
 
@@ -2572,6 +2574,377 @@ int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const u
     if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
     poa_multi_destroy(m);
     return rc;
+}
+
+}  // extern "C"
+
+
+// ---- score set (poa_scoreset.hpp, poa_scoreset_plan.hpp) ---------------------------------------------------------------------
+// Score-only runs over (query, graph) pairs of many graphs.  The set's result buffers, events and statistics are those of a
+// score-mode poa_batch (`core`, no graph of its own, one "query" per pair); what is new lies beside it: the plan, the
+// concatenated tables of all graphs, one parameter block per graph and the class lists of the three run variants.
+struct poa_scoreset {
+    poa_batch core;
+    ScoreSetPlan plan;
+    std::vector<uint64_t> ub_open, ub_extend;   // per graph with pairs: the u16 bound is open * ub_open + extend * ub_extend
+    DevBuf<uint32_t> d_slot, d_pred_slot, d_pair_graph, d_pair_query, d_carry_off, d_class_list[SS_N_VARIANTS];
+    DevBuf<ScoreGraphParams> d_params;
+};
+
+namespace {
+int scoreset_mode_check(const poa_config_t* cfg, const char* who) {
+    if (cfg && cfg->mode != POA_MODE_SCORE)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a score set runs in POA_MODE_SCORE only");
+    if (cfg && cfg->span != POA_SPAN_GLOBAL)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": score-only mode is Global: an ends-free result is defined by the reference's search");
+    return POA_OK;
+}
+
+int scoreset_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff, uint64_t n_pairs,
+                     const uint32_t* pair_query, const uint32_t* pair_graph, uint64_t workspace_bytes, ScoreSetPlan& plan, const char* who) {
+    if (!qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    std::vector<ScoreSetGraphIn> in(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
+        in[g] = ScoreSetGraphIn{&graphs[g]->g, &graphs[g]->sweep};
+    }
+    std::string err;
+    const int rc = build_scoreset_plan(in.data(), n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, workspace_bytes, plan, err);
+    if (rc != 0) return fail(rc, std::string(who) + ": " + err);
+    return POA_OK;
+}
+
+// one sweep launch per chunk and non-empty kernel class, nothing else.  Costs are 32-bit, as in run_sweep.
+int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const poa_config_t* cfg, hipStream_t stream, const char* who) {
+    const TuneView T(cfg);
+    poa_batch* b = &s->core;
+    HIP_TRY(hipSetDevice(b->device));
+    b->last_mode = POA_MODE_SCORE;
+    b->two_piece = false;
+    b->last_stream = stream;
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": call poa_scoreset_stats/fetch at least every 256 runs");
+    // u16 cells only if every graph's own bound (run_sweep's ub, with the longest query paired with it and its shortest path) allows them
+    bool narrow = true;
+    for (size_t g = 0; g < s->ub_open.size(); ++g)
+        narrow = narrow && (uint64_t)cost_o * s->ub_open[g] + (uint64_t)cost_e * s->ub_extend[g] <= 65534;
+    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    bool want_px = true;
+    if (const int* xv = T.ptr(POA_TUNE_PX)) want_px = (*xv) != 0;
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = 0;
+    const ScoreSetPlan& pl = s->plan;
+    const uint32_t variant = narrow ? (want_px ? SS_VAR_U16_PX : SS_VAR_U16) : SS_VAR_U32;
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * pl.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
+    b->sweep_bytes_written = variant == SS_VAR_U16_PX ? 2ull * (pl.slotted_px * 2048ull + pl.slotted_pitch * 2ull)
+                                                      : 2ull * pl.slotted_pitch_all * (narrow ? 2ull : 4ull);
+    size_t ev = 1;
+    for (const auto& ch : pl.chunks) {
+        ScoreSetLaunch sl;
+        sl.graphs = s->d_params.p; sl.pair_graph = s->d_pair_graph.p; sl.pair_query = s->d_pair_query.p;
+        sl.pitch = b->d_pitch.p; sl.region_off = b->plan[0].d_off.p; sl.carry_off = s->d_carry_off.p;
+        sl.qseq = b->d_qseq.p; sl.qoff = b->d_qoff.p; sl.planes = b->d_planes.p; sl.carry = b->d_carry.p;
+        sl.cost_x = cost_x; sl.cost_oe = cost_o + cost_e; sl.cost_e = cost_e;
+        for (uint32_t c = 0; c < SS_N_CLASSES; ++c) {
+            const uint32_t begin = ch.class_begin[variant][c], count = ch.class_begin[variant][c + 1] - begin;
+            if (!count) continue;
+            sl.list = s->d_class_list[variant].p + begin; sl.n = count;
+            const dim3 grid((count + 3) / 4), block(256);
+            if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_kernel, grid, block, 0, stream, sl);
+            else if (narrow) {
+                if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_kernel<1, uint16_t>), grid, block, 0, stream, sl);
+                else hipLaunchKernelGGL((poa_scoreset_sweep_kernel<2, uint16_t>), grid, block, 0, stream, sl);
+            } else {
+                if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_kernel<1, uint32_t>), grid, block, 0, stream, sl);
+                else if (c == SS_CLASS_Q2) hipLaunchKernelGGL((poa_scoreset_sweep_kernel<2, uint32_t>), grid, block, 0, stream, sl);
+                else hipLaunchKernelGGL((poa_scoreset_sweep_kernel<4, uint32_t>), grid, block, 0, stream, sl);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+    }
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int poa_scoreset_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff, uint64_t n_pairs,
+                           const uint32_t* pair_query, const uint32_t* pair_graph, const poa_config_t* cfg, uint64_t* bytes,
+                           uint64_t* largest_pair_bytes) {
+    if (!bytes && !largest_pair_bytes) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_footprint: null argument");
+    int rc = scoreset_mode_check(cfg, "poa_scoreset_footprint");
+    if (rc != POA_OK) return rc;
+    ScoreSetPlan plan;
+    try {
+        rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, 0, plan, "poa_scoreset_footprint");
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_footprint: host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    if (bytes) *bytes = plan.bytes_total;
+    if (largest_pair_bytes) *largest_pair_bytes = plan.largest_pair_bytes;
+    return POA_OK;
+}
+
+int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int device, uint32_t n_queries, const uint8_t* qseq,
+                        const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph,
+                        const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out) {
+    if (!out) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: out is null");
+    *out = nullptr;
+    int rc = scoreset_mode_check(cfg, "poa_scoreset_create");
+    if (rc != POA_OK) return rc;
+    std::unique_ptr<poa_scoreset> s(new (std::nothrow) poa_scoreset);
+    if (!s) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
+    ScoreSetPlan& pl = s->plan;
+    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
+    try {
+        rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, 0, pl, "poa_scoreset_create");
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_create: host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    const uint32_t n = pl.n_pairs;
+    if (n_queries && qoff[n_queries] && !qseq) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: null argument");
+    const int ndev = poa_device_count();
+    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t fixed = (uint64_t)n * 64 + (uint64_t)n_queries * 8 + qoff[n_queries] + (64ull << 20) + pl.max_carry_words * 4 +
+                           (pl.n_rows_total + pl.n_edges_total) * 32;
+    uint64_t ws = workspace_bytes;
+    if (ws == 0) {
+        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
+        ws = std::min<uint64_t>(pl.bytes_total, avail);
+    }
+    if (ws < pl.largest_pair_bytes) {
+        if (pl.largest_pair_bytes + fixed > free_b)
+            return fail(POA_ERR_OUT_OF_MEMORY, "the slot footprint of the largest pair does not fit in device memory");
+        ws = pl.largest_pair_bytes;
+    }
+    if (ws < pl.bytes_total) {
+        try {
+            rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, ws, pl, "poa_scoreset_create");
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_create: host allocation failed"); }
+        if (rc != POA_OK) return rc;
+    }
+
+    // the core batch: one "query" per pair — results, events, statistics
+    poa_batch* b = &s->core;
+    b->graph = nullptr; b->device = device; b->n_queries = n;
+    b->sweep = true; b->last_mode = POA_MODE_SCORE;
+    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.bytes_total;
+    b->plan_ws = pl.workspace_bytes;
+    try {
+        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
+        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    b->active_plan = 0;
+
+    // concatenated tables, one copy per distinct handle, and the parameter block of every listed graph
+    std::vector<RowMeta> h_rows(pl.n_rows_total);
+    std::vector<uint32_t> h_slot(pl.n_rows_total), h_pred_rows(pl.n_edges_total), h_pred_slot(pl.n_edges_total);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const ScoreSetGraphPlan& gp = pl.graphs[g];
+        if (gp.n_pairs) {
+            s->ub_open.push_back((gp.max_len ? 1 : 0) + (graphs[g]->g.min_path_nodes ? 1 : 0));
+            s->ub_extend.push_back(gp.max_len + graphs[g]->g.min_path_nodes);
+            b->max_len = std::max(b->max_len, gp.max_len);
+        }
+        if (gp.table_of != g) continue;
+        const FlatGraph& fg = graphs[g]->g;
+        const SweepRows& sw = graphs[g]->sweep;
+        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
+        std::copy(sw.slot.begin(), sw.slot.end(), h_slot.begin() + gp.row_base);
+        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
+        std::copy(sw.pred_slot.begin(), sw.pred_slot.end(), h_pred_slot.begin() + gp.edge_base);
+    }
+
+    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
+    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
+    HIP_TRY(s->d_slot.alloc(std::max<size_t>(h_slot.size(), 1)));
+    HIP_TRY(s->d_pred_slot.alloc(std::max<size_t>(h_pred_slot.size(), 1)));
+    HIP_TRY(s->d_pair_graph.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(s->d_pair_query.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(s->d_carry_off.alloc(std::max<uint32_t>(n, 1)));
+    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(s->d_class_list[v].alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(s->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
+    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n_queries], 1)));
+    HIP_TRY(b->d_qoff.alloc((size_t)n_queries + 1));
+    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>(pl.max_carry_words, 1)));
+    HIP_TRY(b->d_pipeline_error.alloc(1));
+    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
+    if (n) {
+        std::string werr;
+        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "score-set workspace: " + werr);
+    }
+
+    std::vector<ScoreGraphParams> h_params(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const ScoreSetGraphPlan& gp = pl.graphs[g];
+        ScoreGraphParams& sp = h_params[g];
+        std::memset(&sp, 0, sizeof(sp));
+        SweepParams& kp = sp.P;
+        kp.rows = b->d_rows.p + gp.row_base; kp.slot = s->d_slot.p + gp.row_base;
+        kp.pred_rows = b->d_pred_rows.p + gp.edge_base; kp.pred_slot = s->d_pred_slot.p + gp.edge_base;
+        kp.n_rows = gp.n_rows; kp.n_slots = std::max<uint32_t>(gp.n_slots, 1u);
+        kp.qseq = b->d_qseq.p; kp.qoff = b->d_qoff.p; kp.pitch = b->d_pitch.p; kp.plane_off = b->plan[0].d_off.p;
+        kp.planes = b->d_planes.p; kp.carry = b->d_carry.p;
+        kp.score = b->d_score.p; kp.flags = b->d_flags.p;
+        sp.empty = gp.empty ? 1u : 0u;
+    }
+
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
+    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
+    HIP_TRY(up(s->d_slot.p, h_slot.data(), h_slot.size() * 4));
+    HIP_TRY(up(s->d_pred_slot.p, h_pred_slot.data(), h_pred_slot.size() * 4));
+    HIP_TRY(up(s->d_params.p, h_params.data(), h_params.size() * sizeof(ScoreGraphParams)));
+    HIP_TRY(up(s->d_pair_graph.p, pl.pair_graph.data(), (size_t)n * 4));
+    HIP_TRY(up(s->d_pair_query.p, pl.pair_query.data(), (size_t)n * 4));
+    HIP_TRY(up(s->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
+    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(up(s->d_class_list[v].p, pl.class_list[v].data(), (size_t)n * 4));
+    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n_queries]));
+    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n_queries + 1) * 8));
+    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
+    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+
+    *out = s.release();
+    return POA_OK;
+}
+
+int poa_scoreset_run(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, void* stream) {
+    if (!s || !costs) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run");
+    if (rc != POA_OK) return rc;
+    return scoreset_run(s, costs->mismatch, costs->gap_open, costs->gap_extend, cfg, (hipStream_t)stream, "poa_scoreset_run");
+}
+
+int poa_scoreset_run_2piece(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream) {
+    if (!s || !costs) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run_2piece: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run_2piece");
+    if (rc != POA_OK) return rc;
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    // the two-piece optimum is the one-piece optimum under open' = open1 + extend1 - extend2, extend' = extend2
+    return scoreset_run(s, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
+                        (hipStream_t)stream, "poa_scoreset_run_2piece");
+}
+
+int poa_scoreset_fetch(poa_scoreset_t* s, uint32_t* score, uint32_t* flags, poa_stats_t* stats) {
+    if (!s) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch: null set");
+    poa_batch* b = &s->core;
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch: poa_scoreset_run has not been called");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const uint32_t n = b->n_queries;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t n_flagged = 0;
+    if (n) {
+        if (score) HIP_TRY(hipMemcpy(score, b->d_score.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> fl_local;
+        uint32_t* fl = flags;
+        if (!fl && stats) { fl_local.resize(n); fl = fl_local.data(); }
+        if (fl) HIP_TRY(hipMemcpy(fl, b->d_flags.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (fl) for (uint32_t i = 0; i < n; ++i) n_flagged += fl[i] != 0;
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        collect_stats(b, stats);
+        stats->n_flagged = n_flagged;
+        stats->ms_d2h = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();   // blocking copies: host time
+    }
+    return POA_OK;
+}
+
+int poa_scoreset_stats(poa_scoreset_t* s, poa_stats_t* stats) {
+    if (!s || !stats) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_stats: null argument");
+    return poa_batch_stats(&s->core, stats);
+}
+
+int poa_scoreset_device_results(poa_scoreset_t* s, void** score, void** flags) {
+    if (!s) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_device_results: null set");
+    return poa_batch_device_results(&s->core, score, flags, nullptr, nullptr);
+}
+
+int poa_scoreset_workspace_bytes(poa_scoreset_t* s, uint64_t* bytes) {
+    if (!s || !bytes) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_workspace_bytes: null argument");
+    *bytes = s->core.d_planes.bytes;
+    return POA_OK;
+}
+
+void poa_scoreset_destroy(poa_scoreset_t* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->core.device);
+    if (s->core.ran) (void)hipStreamSynchronize(s->core.last_stream);  // the workspace may be handed to another batch next
+    delete s;
+}
+
+// one-shot: exactly one of costs / costs2 is set
+static int score_pairs_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_costs2_t* costs2,
+                            const poa_config_t* cfg, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs,
+                            const uint32_t* pair_query, const uint32_t* pair_graph, uint32_t* score, uint32_t* flags, poa_stats_t* stats,
+                            int device) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    poa_scoreset_t* s = nullptr;
+    int rc = poa_scoreset_create(graphs, n_graphs, device, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, cfg, 0, &s);
+    if (rc != POA_OK) return rc;
+    rc = costs ? poa_scoreset_run(s, costs, cfg, nullptr) : poa_scoreset_run_2piece(s, costs2, cfg, nullptr);
+    if (rc == POA_OK) rc = poa_scoreset_fetch(s, score, flags, stats);
+    poa_scoreset_destroy(s);
+    return rc;
+}
+
+int poa_score_pairs(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_config_t* cfg,
+                    uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query,
+                    const uint32_t* pair_graph, uint32_t* score, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_score_pairs: null argument");
+    return score_pairs_impl(graphs, n_graphs, costs, nullptr, cfg, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, score, flags, stats, device);
+}
+
+int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs2_t* costs, const poa_config_t* cfg,
+                           uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query,
+                           const uint32_t* pair_graph, uint32_t* score, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_score_pairs_2piece: null argument");
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    return score_pairs_impl(graphs, n_graphs, nullptr, costs, cfg, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, score, flags, stats, device);
 }
 
 }  // extern "C"

@@ -51,24 +51,21 @@ struct SweepParams {
 // ---------------------------------------------------------------------------------------------------------------------
 // General path: any pitch (strips of W = Q * 64 * K columns, one after the other), u16 cells where the engine's bound on
 // the optimal score allows them (arithmetic in 32-bit registers, as in poa_forward_kernel), else u32.
+//
+// The rows of one query, all strips: the body of poa_sweep_kernel, shared with the score-set kernels (poa_scoreset.hpp), which
+// hand it the tables of the pair's own graph in P.  Of P it reads the graph tables, n_rows, n_slots, the costs and score /
+// flags; the query (L symbols at q, `pitch` columns), its slot region (M at Mp, D behind it), its carries (4 x n_rows words,
+// touched only by a query wider than one strip) and the index `out` of its result come from the caller.
 template <int Q, typename T>
-__global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
+__device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t out, const uint32_t lane, const uint32_t L,
+                                           const uint8_t* __restrict__ q, const uint32_t pitch, T* __restrict__ Mp,
+                                           uint32_t* __restrict__ carry) {
     using IO = PlaneIO<T>;
     constexpr int K = IO::K;
     constexpr int C = K * Q;
     constexpr uint32_t QW = 64 * K;
     constexpr uint32_t W = QW * Q;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
-    if (wq >= P.n_queries) return;
-    const uint32_t qi = P.first_query + wq;
-    const uint64_t qbeg = P.qoff[qi];
-    const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
-    const uint8_t* __restrict__ q = P.qseq + qbeg;
-    const uint32_t pitch = P.pitch[qi];
-    T* __restrict__ Mp = reinterpret_cast<T*>(P.planes) + P.plane_off[qi];
     T* __restrict__ Dp = Mp + (uint64_t)P.n_slots * pitch;
-    uint32_t* __restrict__ carry = P.carry + 4ull * wq * P.n_rows;
     const uint32_t x = P.cost_x, oe = P.cost_oe, e = P.cost_e;
     const uint32_t n_strips = (pitch + W - 1) / W;
     const uint32_t step = K * e;
@@ -225,8 +222,8 @@ __global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
                         if (sbase + m * QW + K * lane + k == L) v = Mc[K * m + k];
                 const uint32_t owner = ((L - sbase) % QW) / K;
                 if (lane == owner) {
-                    P.score[qi] = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
-                    P.flags[qi] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+                    P.score[out] = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
+                    P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
                 }
             }
 #pragma unroll
@@ -236,6 +233,18 @@ __global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
     }
 }
 
+template <int Q, typename T>
+__global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
+    if (wq >= P.n_queries) return;
+    const uint32_t qi = P.first_query + wq;
+    const uint64_t qbeg = P.qoff[qi];
+    const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
+    sweep_rows<Q, T>(P, qi, lane, L, P.qseq + qbeg, P.pitch[qi], reinterpret_cast<T*>(P.planes) + P.plane_off[qi],
+                     P.carry + 4ull * wq * P.n_rows);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Headline path: packed u16, one strip (pitch <= 1024), the pairs-across-quads register mapping of poa_forward_px_kernel
 // (register k of a lane: lo half = column 8l + k, hi half = column 512 + 8l + k) and its row step in the MF = 3 shape, without
@@ -243,19 +252,15 @@ __global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
 // 16-byte words at [h * 64 + l] — since nothing but this kernel reads it: no v_perm_b32 repack on the way out or back in,
 // and no store at all for a row without a slot.  Columns at and beyond the pitch hold ordinary "past the end of the query"
 // values that only ever flow to the right, away from column L.
-__global__ __launch_bounds__(256) void poa_sweep_px_kernel(SweepParams P) {
+//
+// The rows of one query: the body of poa_sweep_px_kernel, shared with the score-set kernels (poa_scoreset.hpp) as sweep_rows
+// is.  L <= 1023 symbols at q; Mp is the calling lane's place in the query's region, [M: n_slots x 128 uint4 | D: n_slots x
+// 128 uint4] + lane; the result goes to index `out`.
+__device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32_t out, const uint32_t lane, const uint32_t L,
+                                              const uint8_t* __restrict__ q, uint4* __restrict__ Mp) {
     constexpr int K = 8;
     constexpr uint32_t QW = 64 * K;
     constexpr uint32_t I16 = 0xFFFFu, INF2 = 0xFFFFFFFFu;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
-    if (wq >= P.n_queries) return;
-    const uint32_t qi = P.first_query + wq;
-    const uint64_t qbeg = P.qoff[qi];
-    const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);  // <= 1023 (launcher: one strip)
-    const uint8_t* __restrict__ q = P.qseq + qbeg;
-    // per query: [M: n_slots x 128 uint4 | D: n_slots x 128 uint4]
-    uint4* __restrict__ Mp = reinterpret_cast<uint4*>(P.planes) + (uint64_t)wq * P.n_slots * 256u + lane;
     uint4* __restrict__ Dp = Mp + (uint64_t)P.n_slots * 128u;
     const uint32_t e = P.cost_e, x = P.cost_x;
     auto pack16 = [](uint32_t v) { v = v < I16 ? v : I16; return v | (v << 16); };
@@ -465,9 +470,20 @@ __global__ __launch_bounds__(256) void poa_sweep_px_kernel(SweepParams P) {
         const uint32_t kk = col & 7u;
         uint32_t v = reinterpret_cast<const uint32_t*>(&my_tab[(kk >> 2) * 64])[kk & 3u];
         v = L >= QW ? v >> 16 : v & 0xFFFFu;
-        P.score[qi] = v == I16 ? INF : v;
-        P.flags[qi] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+        P.score[out] = v == I16 ? INF : v;
+        P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
     }
+}
+
+__global__ __launch_bounds__(256) void poa_sweep_px_kernel(SweepParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
+    if (wq >= P.n_queries) return;
+    const uint32_t qi = P.first_query + wq;
+    const uint64_t qbeg = P.qoff[qi];
+    const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);  // <= 1023 (launcher: one strip)
+    // per query: [M: n_slots x 128 uint4 | D: n_slots x 128 uint4]
+    sweep_px_rows(P, qi, lane, L, P.qseq + qbeg, reinterpret_cast<uint4*>(P.planes) + (uint64_t)wq * P.n_slots * 256u + lane);
 }
 
 }  // namespace poa_amd

@@ -1,0 +1,92 @@
+// Score sets (poa_scoreset_*) for gfx950: the score-only sweep of poa_forward_sweep.hpp over a list of (query, graph) PAIRS of
+// many graphs in one launch.  One wavefront per pair; nothing is ordered between waves, so the four waves of
+// a block may belong to four graphs.
+//
+// What a single-graph launch passes as its kernel argument, SweepParams, lies here once per graph in a device array.  A wave
+// reads its pair's graph id and query id, copies that graph's block into registers, patches the costs and calls the SAME row
+// bodies (sweep_rows, sweep_px_rows) as the single-graph kernels, which take `const SweepParams&` and never see where it came
+// from.  The ids go through readfirstlane, as in poa_multi.hpp: the block's address is then a scalar, the copy is a run of
+// scalar loads into SGPRs, and every table pointer and row count the bodies use stays as uniform as a kernel argument is.
+//
+// A launch covers one kernel CLASS of one chunk (ScoreSetPlan): `list` holds the chunk's pairs of that class, wave w takes
+// pair list[w].  Results are written at the pair's own index, so they land in pair order whatever the class order is.
+// A pair's slot region starts at its own offset into the chunk's workspace (4-byte cells, whatever the cell type of the run: a
+// u16 run and the packed kernel's 2048-byte slot rows use the front of a region sized for u32), its strip carries at
+// carry_off[p] (4 x n_rows(graph) words, only for a pair wider than 1024 columns).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "poa_forward_sweep.hpp"
+
+namespace poa_amd {
+
+struct ScoreGraphParams {
+    SweepParams P;         // the graph's tables, n_rows, n_slots, score / flags; the costs are patched per wave, the rest is unused
+    uint32_t empty;        // the graph has no real nodes: score 4 * len, POA_FLAG_EMPTY_GRAPH (PoastaAligner::align, mod.rs:124-142)
+    uint32_t pad;
+};
+
+struct ScoreSetLaunch {
+    const ScoreGraphParams* graphs;   // [n_graphs]
+    const uint32_t* list;             // [n] pairs of this launch
+    const uint32_t* pair_graph;       // [n_pairs]
+    const uint32_t* pair_query;       // [n_pairs]
+    const uint32_t* pitch;            // [n_pairs]
+    const uint64_t* region_off;       // [n_pairs] 4-byte cells from the start of the pair's chunk
+    const uint32_t* carry_off;        // [n_pairs] words into `carry`, relative to the pair's chunk
+    const uint8_t* qseq;
+    const uint64_t* qoff;             // [n_queries + 1]
+    uint32_t* planes;
+    uint32_t* carry;
+    uint32_t n;
+    uint32_t cost_x, cost_oe, cost_e;
+};
+
+__device__ __forceinline__ uint32_t scoreset_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// the wave's pair, its query and its graph's parameter block; false: nothing to compute for this wave (no pair, or a pair
+// against a graph without real nodes, whose shortcut result is written here)
+__device__ __forceinline__ bool scoreset_load(const ScoreSetLaunch& A, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
+                                              const uint8_t*& q) {
+    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (w >= A.n) return false;
+    p = scoreset_uni(A.list[w]);
+    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
+    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
+    P = gp->P;
+    const uint32_t empty = gp->empty;
+    P.cost_x = A.cost_x; P.cost_oe = A.cost_oe; P.cost_e = A.cost_e;
+    const uint64_t qbeg = A.qoff[qid];
+    L = (uint32_t)(A.qoff[qid + 1] - qbeg);
+    q = A.qseq + qbeg;
+    if (empty) {
+        if (lane == 0) { P.score[p] = L * 4u; P.flags[p] = POA_FLAG_EMPTY_GRAPH; }
+        return false;
+    }
+    return true;
+}
+
+template <int Q, typename T>
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_kernel(ScoreSetLaunch A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    if (!scoreset_load(A, lane, p, P, L, q)) return;
+    sweep_rows<Q, T>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                     A.carry + scoreset_uni(A.carry_off[p]));
+}
+
+// pairs of one strip, 512 < pitch <= 1024, on a u16 run: slot rows in the packed kernel's register layout, 2048 bytes each
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_px_kernel(ScoreSetLaunch A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    if (!scoreset_load(A, lane, p, P, L, q)) return;
+    sweep_px_rows(P, p, lane, L, q, reinterpret_cast<uint4*>(A.planes + A.region_off[p]) + lane);
+}
+
+}  // namespace poa_amd
