@@ -152,6 +152,8 @@ enum {
     POA_TUNE_WS_ADAPT,        /* wave replay: entries tested in the step after an expansion (0: always WS_LANES) */
     POA_TUNE_WS_REC,          /* 0: the wave replay's one-round-trip path reads the graph arrays instead of the per-row records */
     POA_TUNE_CKPT_ROWS,       /* checkpointed mode: rows per segment (read when the batch is created; 0 / unset: the engine's choice) */
+    POA_TUNE_BAND,            /* 0: the one-strip dense kernel computes every cell instead of an exact band (poa_batch_band_info) */
+    POA_TUNE_BAND_DELTA,      /* banded kernel: cap of the band distance D (tests: a small cap sends every query to the full kernel) */
     POA_TUNE_COUNT = 32
 };
 
@@ -385,6 +387,11 @@ int poa_batch_fetch_search_counters(poa_batch_t* b, uint32_t* out);
 #define POA_LAYOUT_DERIVED_GAPS 8u /* compact cells keep the two Match-state flags only; the traceback derives the gap-state ones */
 #define POA_LAYOUT_RELATIVE 4u  /* cells hold score - e * (shortest-path depth of the row - column): scores beyond u16 */
 int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout);
+/* the banded forward pass of the last dense run (one-strip batches, 512 < widest plane row <= 1024): out[0] = 1 if it ran,
+ * out[1] = queries whose banded result was certified exact and kept, out[2] = queries the full kernel recomputed, out[3] = the
+ * smallest band distance D among the queries it ran on (a query is certified when its score is <= e * (D - 4)).
+ * Synchronises with the run's stream. */
+int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);

@@ -385,6 +385,12 @@ class ResidentBatch:
         _lib.check(_lib.lib().poa_batch_last_layout(self.handle, C.byref(v)))
         return {name for bit, name in ((1, "u16"), (2, "compact"), (4, "relative"), (8, "derived_gaps")) if v.value & bit}
 
+    def band_info(self):
+        """The banded forward pass of the last dense run: {"used", "banded", "fell_back", "min_d"} (poa_batch_band_info)."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.lib().poa_batch_band_info(self.handle, out))
+        return {"used": bool(out[0]), "banded": int(out[1]), "fell_back": int(out[2]), "min_d": int(out[3])}
+
     def device_results(self):
         ptrs = [C.c_void_p() for _ in range(4)]
         _lib.check(_lib.lib().poa_batch_device_results(self.handle, *[C.byref(p) for p in ptrs]))

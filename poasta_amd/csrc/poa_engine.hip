@@ -31,6 +31,8 @@ struct TuneView {
 #include "poa_kernels.hpp"
 #include "poa_forward_packed.hpp"
 #include "poa_forward_px.hpp"
+#include "poa_band_plan.hpp"
+#include "poa_forward_band.hpp"
 #include "poa_twopiece.hpp"
 #include "poa_sweep_rows.hpp"
 #include "poa_forward_sweep.hpp"
@@ -259,6 +261,17 @@ struct poa_batch {
     bool ckpt2 = false;                // a checkpointed batch of the two-piece model (POA_MODE_CHECKPOINT2, poa_checkpoint2.hpp): `ckpt` is set too
     DevBuf<uint32_t> d_ck_snap_off, d_ck_snap_dst, d_ck_pred_src, d_ck_boundary;
 
+    // banded forward pass (poa_forward_band.hpp): one band class per distinct query length, planned at the first run that
+    // takes the banded kernel (the plan depends on the graph and the lengths alone) and kept
+    bool band_ready = false;
+    uint32_t band_n_seg = 0;
+    std::vector<uint32_t> h_band_cls, h_band_d;          // per query: class; per class: band distance D
+    DevBuf<uint32_t> d_band_cls, d_band_d, d_band_base;  // the same on the device, and the window bases [class][segment]
+    DevBuf<uint32_t> d_band_list, d_band_count;          // queries the full kernel redoes: [n_queries], and their number per chunk
+    // the last run (poa_batch_band_info)
+    bool band_used = false;
+    uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
+
     // one event set per run since the last stats call: [begin, (fwd_end, tb_end) per chunk..., end]
     std::vector<std::vector<hipEvent_t>> runs;
     std::vector<std::vector<hipEvent_t>> free_sets;
@@ -330,6 +343,38 @@ static void collect_stats(poa_batch* b, poa_stats_t* stats) {
 static uint32_t mw_waves(uint32_t strips) {
     const uint32_t groups = (strips + MW_MAX_WAVES - 1) / MW_MAX_WAVES;
     return (strips + groups - 1) / groups;
+}
+
+// the band plan of a resident batch: classes by query length, their band distances and window bases, uploaded once
+static int prepare_band(poa_batch* b) {
+    if (b->band_ready) return POA_OK;
+    const FlatGraph& fg = b->graph->g;
+    BandTables bt;
+    build_band_tables(fg, bt);
+    b->band_n_seg = band_segments(fg.n);
+    std::map<uint64_t, uint32_t> cls_of_len;
+    std::vector<uint32_t> bases;
+    b->h_band_cls.resize(b->n_queries);
+    b->h_band_d.clear();
+    for (uint32_t i = 0; i < b->n_queries; ++i) {
+        const uint64_t len = b->h_qoff[i + 1] - b->h_qoff[i];
+        auto it = cls_of_len.find(len);
+        if (it == cls_of_len.end()) {
+            it = cls_of_len.emplace(len, (uint32_t)b->h_band_d.size()).first;
+            bases.resize(bases.size() + b->band_n_seg);
+            b->h_band_d.push_back(plan_band(fg, bt, (uint32_t)len, BAND_SEG_ROWS, BAND_WINDOW, bases.data() + bases.size() - b->band_n_seg));
+        }
+        b->h_band_cls[i] = it->second;
+    }
+    HIP_TRY(b->d_band_cls.alloc(b->n_queries));
+    HIP_TRY(b->d_band_d.alloc(b->h_band_d.size()));
+    HIP_TRY(b->d_band_base.alloc(bases.size()));
+    HIP_TRY(b->d_band_list.alloc(b->n_queries));
+    HIP_TRY(hipMemcpy(b->d_band_cls.p, b->h_band_cls.data(), b->h_band_cls.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_band_d.p, b->h_band_d.data(), b->h_band_d.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_band_base.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice));
+    b->band_ready = true;
+    return POA_OK;
 }
 
 static bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch) {
@@ -1012,6 +1057,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     if (relative) { narrow = true; compact = true; }
     b->relative = relative;
     b->dense_narrow = narrow; b->dense_compact = compact; b->dense_relative = relative; b->dense_derived_gaps = false;
+    b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->narrow = narrow;
     b->compact = compact;
     // 2-byte elements let twice the queries share the workspace; the exact replay needs the u32 plan
@@ -1046,8 +1092,19 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     if (const int* fv = T.ptr(POA_TUNE_FUSE_TB)) fuse_tb = (*fv) != 0;
     int quads_override = 0;
     if (const int* ov = T.ptr(POA_TUNE_FWD_QUADS)) quads_override = (*ov);  // tuning override
+    // the banded one-strip kernel (poa_forward_band.hpp) wherever poa_forward_px_kernel<3> would run in a dense run; its bound
+    // needs e > 0.  POA_BAND=0 switches it off, POA_BAND_DELTA caps the band distance (tests)
+    bool want_band = mode == POA_MODE_DENSE && costs->gap_extend > 0;
+    if (const int* bv = T.ptr(POA_TUNE_BAND)) want_band = want_band && (*bv) != 0;
+    uint32_t band_cap = 0xFFFFFFFFu;
+    if (const int* dv = T.ptr(POA_TUNE_BAND_DELTA)) band_cap = (*dv) > 0 ? (uint32_t)(*dv) : 0u;
+    if (want_band && !PL.chunks.empty()) {   // one fallback counter per chunk, cleared per run
+        if (b->d_band_count.n < PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(PL.chunks.size()));
+        HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, PL.chunks.size() * 4, stream));
+    }
     size_t ev = 1;
-    for (const auto& ch : PL.chunks) {
+    for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
+        const auto& ch = PL.chunks[ci];
         TbParams tp;
         tp.rows = b->d_rows.p; tp.pred_rows = b->d_pred_rows.p; tp.n_rows = fg.n;
         tp.start_row = fg.start_row; tp.end_row = fg.end_row;
@@ -1105,7 +1162,23 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                     else if (mf >= 1) mf = 3;
                     tp.code_fmt = mf == 3 ? 4u : (mf == 2 ? 3u : (mf == 1 ? 2u : 1u));
                     b->dense_derived_gaps = mf == 3;
-                    if (mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, dim3(blocks), dim3(256), 0, stream, fp);
+                    if (mf == 3 && want_band && max_pitch > 512) {
+                        // the banded pass, then the full pass (the same kernel with eight registers per row array and one window of
+                        // 1024 columns) over the queries it could not certify: the grid is sized for the chunk and the waves past the
+                        // device-side count return at once, so the host never waits for the count
+                        int rc = prepare_band(b);
+                        if (rc != POA_OK) return rc;
+                        BandParams bp;
+                        bp.cls = b->d_band_cls.p; bp.cls_d = b->d_band_d.p; bp.cls_base = b->d_band_base.p; bp.n_seg = b->band_n_seg;
+                        bp.d_cap = band_cap; bp.list = b->d_band_list.p; bp.count = b->d_band_count.p + ci;
+                        hipLaunchKernelGGL(poa_forward_band_kernel<false>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+                        HIP_TRY(hipGetLastError());
+                        hipLaunchKernelGGL(poa_forward_band_kernel<true>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+                        uint32_t min_d = 0xFFFFFFFFu;
+                        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) min_d = std::min(min_d, std::min(b->h_band_d[b->h_band_cls[i]], band_cap));
+                        b->band_min_d = b->band_used ? std::min(b->band_min_d, min_d) : min_d;
+                        b->band_used = true; b->band_queries += ch.count; b->band_chunks = (uint32_t)ci + 1;
+                    } else if (mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, dim3(blocks), dim3(256), 0, stream, fp);
                     else if (mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, dim3(blocks), dim3(256), 0, stream, fp);
                     else if (mf == 1) hipLaunchKernelGGL(poa_forward_px_kernel<1>, dim3(blocks), dim3(256), 0, stream, fp);
                     else hipLaunchKernelGGL(poa_forward_px_kernel<0>, dim3(blocks), dim3(256), 0, stream, fp);
@@ -1537,6 +1610,21 @@ int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout) {
     if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_layout: poa_batch_run has not been called");
     *layout = (b->dense_narrow ? POA_LAYOUT_U16 : 0u) | (b->dense_compact ? POA_LAYOUT_COMPACT : 0u) | (b->dense_relative ? POA_LAYOUT_RELATIVE : 0u) |
               (b->dense_derived_gaps ? POA_LAYOUT_DERIVED_GAPS : 0u);
+    return POA_OK;
+}
+
+int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_info: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_info: poa_batch_run has not been called");
+    out[0] = b->band_used ? 1u : 0u; out[1] = 0; out[2] = 0; out[3] = b->band_used ? b->band_min_d : 0u;
+    if (!b->band_used) return POA_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    std::vector<uint32_t> counts(b->band_chunks);
+    HIP_TRY(hipMemcpy(counts.data(), b->d_band_count.p, counts.size() * 4, hipMemcpyDeviceToHost));
+    uint32_t fell = 0;
+    for (uint32_t c : counts) fell += c;
+    out[2] = fell; out[1] = b->band_queries - std::min(fell, b->band_queries);
     return POA_OK;
 }
 

@@ -26,7 +26,10 @@ for f in glob.glob("$OUT/pmc_*/*/*counter_collection.csv"):
 json.dump(out, open("$OUT/pmc_summary.json", "w"), indent=1, sort_keys=True)
 for f in glob.glob("$OUT/trace/*/*kernel_stats.csv"):
     open("$OUT/kernel_stats.csv", "w").write(open(f).read())
-kname, k = next(((n, v) for n, v in out.items() if "poa_forward_px_kernel" in n), (None, None))
+# the headline's forward kernel: the banded one where it ran, else the full one-strip kernel
+kname, k = next(((n, v) for n, v in out.items() if "poa_forward_band_kernel" in n), (None, None))
+if not k:
+    kname, k = next(((n, v) for n, v in out.items() if "poa_forward_px_kernel" in n), (None, None))
 if k and "WRITE_SIZE" in k and "FETCH_SIZE" in k:
     w, fch = k["WRITE_SIZE"] * 1024.0, k["FETCH_SIZE"] * 1024.0 * 2.0   # KiB -> bytes; gfx950 tallies 128-B fetches at 64 B
     kc = {"workload": "config2", "queries": 10000, "kernel": kname.split("(")[0].replace("void ", ""),
