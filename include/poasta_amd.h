@@ -395,6 +395,16 @@ int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);
+/* debugging / parity: the planes of query i as a dense one-piece run stored them in the compact derived-gaps layout (the last
+ * run's layout has POA_LAYOUT_DERIVED_GAPS and not POA_LAYOUT_RELATIVE), rows x (len+1) each, row = the engine's row
+ * (poa_graph_node_rows), the pitch padding stripped:
+ *   m_raw   the stored M words as they lie in memory: the score in bits 0..13 (0x3FFF: INF), bit 14: I == M, bit 15: D == M
+ *   d       the kept D rows (0xFFFF: INF); a row the layout does not keep is filled with 0xFFFF and has d_kept[row] = 0
+ *   d_kept  [rows] 1 for the rows whose D the layout keeps
+ * After the banded forward pass only the cells inside a certified query's windows were written by that run.  Valid under the rule
+ * of poa_batch_fetch_planes (the query's chunk was the last one run); any other layout or mode: POA_ERR_UNSUPPORTED.  Synchronises
+ * with the run's stream. */
+int poa_batch_fetch_compact(poa_batch_t* b, uint32_t query, uint16_t* m_raw, uint16_t* d, uint8_t* d_kept);
 /* the five planes M, I1, D1, I2, D2 of query i after a dense poa_batch_run_2piece, rows x (len + 1) each — valid under the rule
  * of poa_batch_fetch_planes: the query's chunk was the last one run, and the last run was a dense two-piece run */
 int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2);

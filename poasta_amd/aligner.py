@@ -403,6 +403,17 @@ class ResidentBatch:
         _lib.check(_lib.lib().poa_batch_fetch_planes(self.handle, query, _p(m), _p(i), _p(d)))
         return m, i, d
 
+    def compact_planes(self, query):
+        """(m_raw, d, d_kept) of one query after a dense run in the compact derived-gaps layout (poa_batch_fetch_compact): the
+        stored M words u16[rows, len + 1] (score in bits 0..13, bit 14: I == M, bit 15: D == M), the kept D rows u16[rows, len + 1]
+        (0xFFFF where d_kept[row] is False) and d_kept bool[rows]; row = the engine's row (DeviceGraph.node_rows)."""
+        rows = self.dg.graph.n
+        cols = int(self.qoff[query + 1] - self.qoff[query]) + 1
+        m_raw, d = np.zeros((rows, cols), np.uint16), np.zeros((rows, cols), np.uint16)
+        kept = np.zeros(rows, np.uint8)
+        _lib.check(_lib.lib().poa_batch_fetch_compact(self.handle, query, _p(m_raw), _p(d), _p(kept)))
+        return m_raw, d, kept.astype(bool)
+
     def planes_2piece(self, query):
         """M, I1, D1, I2, D2 of one query after a dense two-piece run, rows = topological rank (its chunk must be the last one run)."""
         rows = self.dg.graph.n

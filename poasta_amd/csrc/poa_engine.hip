@@ -1661,6 +1661,39 @@ int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t
     return POA_OK;
 }
 
+int poa_batch_fetch_compact(poa_batch_t* b, uint32_t query, uint16_t* m_raw, uint16_t* d, uint8_t* d_kept) {
+    if (!b || !m_raw || !d || !d_kept) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_compact: null argument");
+    if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_compact: bad query / not run");
+    if (b->sweep) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_compact: a score-only batch keeps no score planes");
+    if (b->ckpt || b->ckpt2) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_compact: a checkpointed batch keeps snapshots and one segment window, no score planes");
+    if (b->last_mode != POA_MODE_DENSE) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_compact: after an exact / hybrid run the workspace holds the replayed search's tiled table");
+    if (b->two_piece) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_compact: the last run was a two-piece run; its five planes come from poa_batch_fetch_planes_2piece");
+    if (!b->compact || !b->dense_derived_gaps || b->dense_relative)
+        return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_compact: the last run did not store the compact derived-gaps layout (poa_batch_last_layout)");
+    const auto& last = b->cur().chunks.back();
+    if (query < last.first || query >= last.first + last.count)
+        return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_compact: the query's planes were overwritten by a later chunk");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const FlatGraph& fg = b->graph->g;
+    const uint32_t rows = fg.n, pitch = b->h_pitch[query];
+    const uint32_t cols = (uint32_t)(b->h_qoff[query + 1] - b->h_qoff[query]) + 1;
+    const uint64_t RP = (uint64_t)rows * pitch;
+    const uint16_t* Mp = reinterpret_cast<const uint16_t*>(b->d_planes.p) + b->cur().off[query];
+    const uint16_t* Dp = Mp + RP + RP / 4;   // the kept D rows, row r at slot d_slot[r] (compact_plane_elems)
+    HIP_TRY(hipMemcpy2D(m_raw, (size_t)cols * 2, Mp, (size_t)pitch * 2, (size_t)cols * 2, rows, hipMemcpyDeviceToHost));
+    const uint32_t n_slots = fg.d_slot.empty() ? rows : fg.n_store_d;
+    std::vector<uint16_t> kept((size_t)n_slots * cols);
+    if (n_slots) HIP_TRY(hipMemcpy2D(kept.data(), (size_t)cols * 2, Dp, (size_t)pitch * 2, (size_t)cols * 2, n_slots, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < rows; ++r) {
+        const uint32_t slot = fg.d_slot.empty() ? r : fg.d_slot[r];
+        d_kept[r] = (fg.rows[r].flags & ROW_STORE_D) && slot < n_slots ? 1 : 0;
+        if (d_kept[r]) std::copy(kept.begin() + (size_t)slot * cols, kept.begin() + (size_t)(slot + 1) * cols, d + (size_t)r * cols);
+        else std::fill(d + (size_t)r * cols, d + (size_t)(r + 1) * cols, (uint16_t)0xFFFFu);
+    }
+    return POA_OK;
+}
+
 // ---- two-piece model on a resident batch (kernels: poa_twopiece.hpp with TwoPieceBatchParams) ------------------------------------
 // The u32 plan of the two-piece pass, cut on the first u32 run: five planes of 4-byte cells per query.  The batch's workspace
 // was sized for three; it is replaced by a larger one only if the longest query's five planes do not fit it.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised differential run (GPU box): the HIP path against the oracle on random graphs, costs and query lengths —
-dense mode vs the oracle's dense restatement (scores, alignments, flags), exact mode vs the oracle's A*, the two-piece model on
+dense mode vs the oracle's dense restatement (scores, alignments, flags) and, where the banded forward pass ran, vs the same batch
+under POA_BAND=0, exact mode vs the oracle's A*, the two-piece model on
 a resident batch (poa_batch_run_2piece) vs the oracle's two-piece dense pass and the one-shot call.
 Test infrastructure; prints one JSON line; non-zero exit on the first difference."""
 import argparse, json, os, sys, time
@@ -18,7 +19,7 @@ ap.add_argument("--seconds", type=float, default=240.0)
 ap.add_argument("--verbose", action="store_true")
 args = ap.parse_args()
 t0 = time.time()
-n_dense = n_exact = n_exact2 = n_res2 = n_cases = 0
+n_dense = n_exact = n_exact2 = n_res2 = n_cases = n_banded = n_fell_back = 0
 for seed in range(args.first, args.first + args.seeds):
     if time.time() - t0 > args.seconds:
         break
@@ -110,6 +111,28 @@ for seed in range(args.first, args.first + args.seeds):
                                   oracle=[int(D["score"][i]), int(D["flags"][i])])))
             sys.exit(1)
         n_dense += 1
+    if span is None:
+        # the banded one-strip forward pass and its fallback: the same resident batch with and without it
+        rb = E.ResidentBatch(g, qseq, qoff)
+        rb.run(E.GapAffine(m, e, o))
+        rbd = rb.fetch()
+        info = rb.band_info()
+        if "derived_gaps" in rb.layout() and info["used"]:
+            os.environ["POA_BAND"] = "0"
+            rb.run(E.GapAffine(m, e, o))
+            os.environ.pop("POA_BAND")
+            rfull = rb.fetch()
+            nq = len(qs)
+            ok = (info["banded"] + info["fell_back"] == nq and not rb.band_info()["used"] and np.array_equal(rbd.score, rfull.score)
+                  and np.array_equal(rbd.flags, rfull.flags) and np.array_equal(rbd.pair_off, rfull.pair_off)
+                  and np.array_equal(rbd.pairs[:int(rbd.pair_off[nq])], rfull.pairs[:int(rfull.pair_off[nq])])
+                  and np.array_equal(rbd.score, D["score"]) and np.array_equal(rbd.flags, D["flags"]))
+            if not ok:
+                print(json.dumps(dict(fail="banded vs POA_BAND=0", seed=seed, kind=kind, costs=costs, band_info=info)))
+                sys.exit(1)
+            n_banded += info["banded"]
+            n_fell_back += info["fell_back"]
+        rb.close()
     if span is None and kind != 7:
         # two-piece model on a resident batch: random second piece, cell width and workspace (a small one cuts chunks), two runs
         # of one batch (u32 planes, then the width the costs give) with a one-piece run between them
@@ -208,4 +231,4 @@ for seed in range(args.first, args.first + args.seeds):
     n_cases += 1
     if n_cases % 100 == 0:  # keeps a long run visibly alive
         print(json.dumps(dict(progress=n_cases, seconds=round(time.time() - t0, 1))), flush=True)
-print(json.dumps(dict(ok=True, graphs=n_cases, dense_queries=n_dense, exact_queries=n_exact, two_piece_exact_queries=n_exact2, two_piece_resident_queries=n_res2, seconds=round(time.time() - t0, 1))))
+print(json.dumps(dict(ok=True, graphs=n_cases, dense_queries=n_dense, exact_queries=n_exact, two_piece_exact_queries=n_exact2, two_piece_resident_queries=n_res2, banded_queries=n_banded, band_fallback_queries=n_fell_back, seconds=round(time.time() - t0, 1))))
