@@ -462,6 +462,40 @@ int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const u
                     uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags,
                     poa_stats_t* stats, int device);
 
+/* The same batch under the two-piece affine model: for every query what poa_align_batch_2piece returns for it against its own
+ * graph alone — score, pairs, pair_off, flags, bit for bit (poa_align_batch_2piece_ex in POA_MODE_CHECKPOINT2, graph by
+ * graph).  Global only.  The argument lists are those of the one-piece namesakes with poa_costs2_t for the costs; the object is
+ * a poa_multi_t, and poa_multi_fetch / _stats / _device_results / _workspace_bytes / _destroy serve it unchanged.  Its
+ * footprint is fixed at creation, before any costs are seen, and differs from the one-piece batch's: hence a create function
+ * of its own, and poa_multi_create / _run / _footprint / poa_align_multi keep refusing POA_MODE_CHECKPOINT2.
+ *   cfg      NULL or mode POA_MODE_CHECKPOINT2; every other mode, and POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED.
+ *            tune[POA_TUNE_CKPT_ROWS] (read at creation / by the footprint) applies to every graph, tune[POA_TUNE_PLANES] to a run.
+ * POA_ERR_INVALID_ARG: poa_multi_run on a batch of poa_multi_create_2piece, poa_multi_run_2piece on a batch of
+ * poa_multi_create, gap_extend1 < gap_extend2, the argument errors of poa_multi_create, a fetch before a run.  The batch stays
+ * usable after a refused call; the run may be repeated with other costs and on any stream, and allocates nothing on the device.
+ * Memory: a query holds rows_per_query2(its graph) x pitch 4-byte cells + 256 bytes (poa_graph_checkpoint_plan2 of its graph
+ * alone at the batch's segment length: three kept planes, five window planes; pitch = len + 1 rounded up to 64).
+ * poa_multi_footprint_2piece returns the sum and the largest term; chunks are cut greedily in query order under
+ * workspace_bytes exactly as poa_multi_create cuts them (0: the whole batch, or what free memory allows; a cap below the
+ * largest query is raised to it).  The batch is sized for u32 cells; a u16 run uses the same chunks and half of every region.
+ * The cell width of a run is u16 only if EVERY graph that has queries allows it — [open1 + extend1 x its longest query] +
+ * [open1 + extend1 x its shortest path] <= 65534 — costs->wide_planes is 0 and tune[POA_TUNE_PLANES] is not 32; else u32 for
+ * the whole run.  Both are exact: results do not depend on it.  Carries between strips (queries of more than 1024 columns
+ * only): 24 bytes per graph row of such a query in flight; a query of pitch <= 1024 never touches a carry.
+ * poa_stats_t is summed over graphs as for poa_multi_run: cells = sum rows(graph_i) x (len_i + 1), plane_bytes = sum over
+ * queries of (3 x (slotted + snapshot rows) + 5 x rows) x pitch x cell bytes. */
+int poa_multi_footprint_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
+                               const uint64_t* qoff, const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes);
+int poa_multi_create_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device,
+                            const uint8_t* qseq, const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes,
+                            poa_multi_t** out);
+int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream);
+/* one-shot: create, run, fetch, destroy */
+int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
+                           const poa_costs2_t* costs, const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff,
+                           uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
+                           uint32_t* flags, poa_stats_t* stats, int device);
+
 /* ---- score set: score-only runs over (query, graph) pairs of many graphs ------------------- */
 /* For the question that comes before the alignment — which of these graphs does a read belong to (read-to-family assignment,
  * choosing the window or haplotype graph before a POA build, demultiplexing against amplicon graphs): one launch per kernel

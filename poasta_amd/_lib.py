@@ -26,6 +26,7 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
            "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
            "poa_multi_workspace_bytes", "poa_multi_destroy", "poa_align_multi",
+           "poa_multi_footprint_2piece", "poa_multi_create_2piece", "poa_multi_run_2piece", "poa_align_multi_2piece",
            "poa_scoreset_footprint", "poa_scoreset_create", "poa_scoreset_run", "poa_scoreset_run_2piece", "poa_scoreset_fetch",
            "poa_scoreset_stats", "poa_scoreset_device_results", "poa_scoreset_workspace_bytes", "poa_scoreset_destroy",
            "poa_score_pairs", "poa_score_pairs_2piece"]
@@ -208,6 +209,16 @@ def lib():
     L.poa_align_multi.restype = C.c_int
     L.poa_align_multi.argtypes = [vp, C.c_uint32, vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp, vp, vp, vp, vp, C.c_uint64, vp,
                                   C.POINTER(PoaStats), C.c_int]
+    # the two-piece model on the same object: the argument lists of the namesakes, poa_costs2_t for the costs
+    L.poa_multi_footprint_2piece.restype = C.c_int
+    L.poa_multi_footprint_2piece.argtypes = L.poa_multi_footprint.argtypes
+    L.poa_multi_create_2piece.restype = C.c_int
+    L.poa_multi_create_2piece.argtypes = L.poa_multi_create.argtypes
+    L.poa_multi_run_2piece.restype = C.c_int
+    L.poa_multi_run_2piece.argtypes = [vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp]
+    L.poa_align_multi_2piece.restype = C.c_int
+    L.poa_align_multi_2piece.argtypes = [vp, C.c_uint32, vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp, vp, vp, vp, vp, C.c_uint64, vp,
+                                         C.POINTER(PoaStats), C.c_int]
     # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)
     L.poa_scoreset_footprint.restype = C.c_int
     L.poa_scoreset_footprint.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64),

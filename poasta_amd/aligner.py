@@ -459,36 +459,45 @@ class _MultiInput:
         self.pair_capacity = int(self.qoff[-1]) + int(sum(int(c) * dg.graph.n for c, dg in zip(per_graph, self.dgs) if c > 0))
 
 
-def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None):
+def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False):
     """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
-    largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan."""
+    largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan.
+    two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2")."""
     mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
     total, largest = C.c_uint64(0), C.c_uint64(0)
-    _lib.check(_lib.lib().poa_multi_footprint(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff),
-                                              C.byref(config) if config is not None else None, C.byref(total), C.byref(largest)))
+    fn = _lib.lib().poa_multi_footprint_2piece if two_piece else _lib.lib().poa_multi_footprint
+    _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff), C.byref(config) if config is not None else None,
+                  C.byref(total), C.byref(largest)))
     return int(total.value), int(largest.value)
 
 
 class MultiGraphBatch:
     """The queries of many graphs resident in HBM (`poa_multi_*`): one checkpointed run covers all of them, one wavefront per
     query.  Queries are grouped by graph — seqs_per_graph[g] are graph g's, or graph_qoff + packed qseq / qoff; results come
-    back in query order, rpos = node index in that query's own graph."""
+    back in query order, rpos = node index in that query's own graph.  two_piece=True: the batch of the two-piece model
+    (`poa_multi_create_2piece`; its footprint differs, so the model is chosen at creation), run with GapAffine2Piece costs."""
 
-    def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None):
+    def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None,
+                 two_piece=False):
         mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
         self.input, self.n, self.pair_capacity = mi, mi.n, mi.pair_capacity
         self.graph_qoff, self.qseq, self.qoff = mi.graph_qoff, mi.qseq, mi.qoff
+        self.two_piece = bool(two_piece)
         h = C.c_void_p()
-        _lib.check(_lib.lib().poa_multi_create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
-                                               C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
+        create = _lib.lib().poa_multi_create_2piece if self.two_piece else _lib.lib().poa_multi_create
+        _lib.check(create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
+                          C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
 
     def run(self, costs, stream=None, config=None):
-        """Launch on `stream` without synchronising (config: None or make_config("checkpoint", ...))."""
+        """Launch on `stream` without synchronising (config: None or make_config("checkpoint", ...); for a two_piece batch
+        make_config("checkpoint2", ...)).  GapAffine2Piece costs run through poa_multi_run_2piece, all others through
+        poa_multi_run: costs of the other model than the batch's are refused by the library (POA_ERR_INVALID_ARG)."""
         c = costs._c()
         if config is None:
-            config = make_config("checkpoint")   # (carries the POA_<NAME> overrides, if any are set)
-        _lib.check(_lib.lib().poa_multi_run(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+            config = make_config("checkpoint2" if self.two_piece else "checkpoint")   # (carries the POA_<NAME> overrides, if any are set)
+        run = _lib.lib().poa_multi_run_2piece if isinstance(costs, GapAffine2Piece) else _lib.lib().poa_multi_run
+        _lib.check(run(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
 
     def fetch(self, want_pairs=True):
         n = self.n
@@ -723,9 +732,11 @@ class PoastaAligner:
     def align_multi(self, graphs, seqs_per_graph, want_pairs=True):
         """Many graphs, a few reads each, in one checkpointed run (poa_align_multi): seqs_per_graph[g] are the queries of
         graphs[g].  Returns a BatchResult over all queries in that order: dense mode's score, alignment and flags of every
-        query against its own graph.  One-piece costs, Global."""
-        if getattr(self.config, "two_piece", False) or self.aln_type != AlignmentType.Global:
-            raise ValueError("align_multi: one-piece costs and AlignmentType.Global only")
+        query against its own graph.  Global.  A two-piece config (Affine2PieceDijkstra / Affine2PieceMinGapCost) runs
+        poa_align_multi_2piece: the dense two-piece pass's results."""
+        if self.aln_type != AlignmentType.Global:
+            raise ValueError("align_multi: AlignmentType.Global only")
+        two_piece = getattr(self.config, "two_piece", False)
         mi = _MultiInput(graphs, seqs_per_graph)
         n = mi.n
         score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
@@ -733,10 +744,10 @@ class PoastaAligner:
         pairs = np.zeros((max(mi.pair_capacity, 1), 2), np.uint32) if want_pairs else None
         st = _lib.PoaStats()
         c = self.config.costs._c()
-        cfg = make_config("checkpoint", self.config.heuristic)
-        _lib.check(_lib.lib().poa_align_multi(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq),
-                                              _p(mi.qoff), _p(score), _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags),
-                                              C.byref(st), self.device))
+        cfg = make_config("checkpoint2" if two_piece else "checkpoint", self.config.heuristic)
+        fn = _lib.lib().poa_align_multi_2piece if two_piece else _lib.lib().poa_align_multi
+        _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq), _p(mi.qoff), _p(score),
+                      _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags), C.byref(st), self.device))
         if want_pairs:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())

@@ -40,6 +40,7 @@ struct TuneView {
 #include "poa_checkpoint2.hpp"
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
+#include "poa_multi2.hpp"
 #include "poa_scoreset_plan.hpp"
 #include "poa_scoreset.hpp"
 
@@ -2358,70 +2359,74 @@ struct poa_multi {
     uint64_t stored_rows_pitch = 0;             // sum over queries of (2 x (slotted + snapshot rows) + 3 x rows) x pitch: cells a run stores
     DevBuf<uint32_t> d_slot, d_pred_slot, d_graph_of, d_carry_off;
     DevBuf<MultiGraphParams> d_params;
+    DevBuf<Multi2GraphParams> d_params2;        // a batch of poa_multi_create_2piece holds these instead (core.ckpt2 is set)
 };
 
 namespace {
-int multi_mode_check(const poa_config_t* cfg, const char* who) {
-    if (cfg && cfg->mode != POA_MODE_CHECKPOINT)
-        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a multi-graph batch runs in POA_MODE_CHECKPOINT only");
+int multi_mode_check(const poa_config_t* cfg, const char* who, bool two_piece = false) {
+    if (cfg && cfg->mode != (two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT))
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + (two_piece ? ": a two-piece multi-graph batch runs in POA_MODE_CHECKPOINT2 only"
+                                                                       : ": a multi-graph batch runs in POA_MODE_CHECKPOINT only"));
     if (cfg && cfg->span != POA_SPAN_GLOBAL)
         return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": checkpointed mode is Global: an ends-free result is defined by the reference's search");
     return POA_OK;
 }
 
 int multi_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                  const poa_config_t* cfg, uint64_t workspace_bytes, MultiPlan& plan, const char* who) {
+                  const poa_config_t* cfg, uint64_t workspace_bytes, MultiPlan& plan, const char* who, bool two_piece = false) {
     if (!graph_qoff || !qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
     std::vector<MultiGraphIn> in(n_graphs);
     for (uint32_t g = 0; g < n_graphs; ++g) {
         if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
-        in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, &graphs[g]->ckpt};
+        in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, two_piece ? &graphs[g]->ckpt2 : &graphs[g]->ckpt};
     }
     uint32_t seg_rows = 0;
     { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
     std::string err;
-    const int rc = build_multi_plan(in.data(), n_graphs, graph_qoff, qoff, seg_rows, workspace_bytes, plan, err);
+    const int rc = build_multi_plan(in.data(), n_graphs, graph_qoff, qoff, seg_rows, workspace_bytes, plan, err, two_piece);
     if (rc != 0) return fail(rc, std::string(who) + ": " + err);
     return POA_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int poa_multi_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                        const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
-    if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, "poa_multi_footprint: null argument");
-    int rc = multi_mode_check(cfg, "poa_multi_footprint");
+// poa_multi_footprint and poa_multi_footprint_2piece: the same sum with the plan of the model
+int multi_footprint_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                         const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes, bool two_piece, const char* who_c) {
+    const std::string who(who_c);
+    if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
+    int rc = multi_mode_check(cfg, who_c, two_piece);
     if (rc != POA_OK) return rc;
     MultiPlan plan;
     try {
-        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, "poa_multi_footprint");
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_footprint: host allocation failed"); }
+        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, who_c, two_piece);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
     if (rc != POA_OK) return rc;
     if (bytes) *bytes = plan.bytes_total;
     if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
     return POA_OK;
 }
 
-int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
-                     const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
-    if (!out) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: out is null");
+// poa_multi_create and poa_multi_create_2piece: one batch, the plan's weights, the carries and the parameter blocks by the model
+int multi_create_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                      const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out, bool two_piece,
+                      const char* who_c) {
+    const std::string who(who_c);
+    if (!out) return fail(POA_ERR_INVALID_ARG, who + ": out is null");
     *out = nullptr;
-    int rc = multi_mode_check(cfg, "poa_multi_create");
+    int rc = multi_mode_check(cfg, who_c, two_piece);
     if (rc != POA_OK) return rc;
     std::unique_ptr<poa_multi> m(new (std::nothrow) poa_multi);
     if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
     MultiPlan& pl = m->plan;
     // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
     try {
-        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, pl, "poa_multi_create");
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_create: host allocation failed"); }
+        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, pl, who_c, two_piece);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
     if (rc != POA_OK) return rc;
     const uint32_t n = pl.n_queries;
-    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: null argument");
+    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
     const int ndev = poa_device_count();
     if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, "poa_multi_create: device ordinal out of range");
+    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, who + ": device ordinal out of range");
     HIP_TRY(hipSetDevice(device));
 
     size_t free_b = 0, total_b = 0;
@@ -2441,15 +2446,15 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
     }
     if (ws < pl.bytes_total) {
         try {
-            rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, ws, pl, "poa_multi_create");
-        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_multi_create: host allocation failed"); }
+            rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, ws, pl, who_c, two_piece);
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
         if (rc != POA_OK) return rc;
     }
 
     // the core batch: queries, results, pair buffers, events
     poa_batch* b = &m->core;
     b->graph = nullptr; b->device = device; b->n_queries = n;
-    b->ckpt = true; b->last_mode = POA_MODE_CHECKPOINT;
+    b->ckpt = true; b->ckpt2 = two_piece; b->last_mode = two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT;
     b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.bytes_total;
     b->plan_ws = pl.workspace_bytes;
     try {
@@ -2469,7 +2474,9 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
     std::vector<uint32_t> h_snap_off(pl.n_snap_off_total), h_snap_dst(pl.n_snap_dst_total), h_boundary(pl.n_boundary_total);
     for (uint32_t g = 0; g < n_graphs; ++g) {
         const MultiGraphPlan& gp = pl.graphs[g];
-        const uint64_t stored = 2ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 3ull * gp.n_rows;
+        // (two-piece: M, D1, D2 of the kept rows and five window planes, run_ckpt2's rule)
+        const uint64_t stored = two_piece ? 3ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 5ull * gp.n_rows
+                                          : 2ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 3ull * gp.n_rows;
         for (uint64_t i = graph_qoff[g]; i < graph_qoff[g + 1]; ++i) m->stored_rows_pitch += stored * pl.pitch[i];
         if (gp.n_queries) {
             m->ub_open.push_back((gp.max_len ? 1 : 0) + (graphs[g]->g.min_path_nodes ? 1 : 0));
@@ -2498,7 +2505,8 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
     HIP_TRY(b->d_ck_boundary.alloc(std::max<size_t>(h_boundary.size(), 1)));
     HIP_TRY(m->d_graph_of.alloc(std::max<uint32_t>(n, 1)));
     HIP_TRY(m->d_carry_off.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(m->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
+    if (two_piece) HIP_TRY(m->d_params2.alloc(std::max<uint32_t>(n_graphs, 1)));
+    else HIP_TRY(m->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
     HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n], 1)));
     HIP_TRY(b->d_qoff.alloc((size_t)n + 1));
     HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
@@ -2518,13 +2526,14 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
         if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "checkpointed workspace: " + werr);
     }
 
-    std::vector<MultiGraphParams> h_params(n_graphs);
-    for (uint32_t g = 0; g < n_graphs; ++g) {
+    // one block per listed graph, CkptParams or Ckpt2Params by the model: the same fields but for the type of `scratch`
+    std::vector<MultiGraphParams> h_params(two_piece ? 0 : n_graphs);
+    std::vector<Multi2GraphParams> h_params2(two_piece ? n_graphs : 0);
+    auto fill = [&](auto& mp, uint32_t g) {
         const MultiGraphPlan& gp = pl.graphs[g];
         const FlatGraph& fg = graphs[g]->g;
-        MultiGraphParams& mp = h_params[g];
         std::memset(&mp, 0, sizeof(mp));
-        CkptParams& kp = mp.P;
+        auto& kp = mp.P;
         kp.rows = b->d_rows.p + gp.row_base; kp.slot = m->d_slot.p + gp.row_base;
         kp.pred_rows = b->d_pred_rows.p + gp.edge_base; kp.pred_slot = m->d_pred_slot.p + gp.edge_base; kp.pred_src = b->d_ck_pred_src.p + gp.edge_base;
         kp.snap_off = b->d_ck_snap_off.p + gp.snap_off_base; kp.snap_dst = b->d_ck_snap_dst.p + gp.snap_dst_base;
@@ -2533,9 +2542,13 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
         kp.start_row = fg.start_row; kp.end_row = fg.end_row;
         kp.qseq = b->d_qseq.p; kp.qoff = b->d_qoff.p; kp.pitch = b->d_pitch.p; kp.plane_off = b->plan[0].d_off.p;
         kp.planes = b->d_planes.p; kp.carry = b->d_carry.p;
-        kp.scratch_off = b->d_scratch_off.p; kp.scratch = b->d_scratch.p;
+        kp.scratch_off = b->d_scratch_off.p; kp.scratch = reinterpret_cast<decltype(kp.scratch)>(b->d_scratch.p);
         kp.score = b->d_score.p; kp.flags = b->d_flags.p; kp.n_pairs = b->d_npairs.p;
         mp.empty = fg.n_real == 0 ? 1u : 0u;
+    };
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (two_piece) fill(h_params2[g], g);
+        else fill(h_params[g], g);
     }
 
     hipEvent_t e0, e1;
@@ -2551,7 +2564,8 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
     HIP_TRY(up(b->d_ck_snap_off.p, h_snap_off.data(), h_snap_off.size() * 4));
     HIP_TRY(up(b->d_ck_snap_dst.p, h_snap_dst.data(), h_snap_dst.size() * 4));
     HIP_TRY(up(b->d_ck_boundary.p, h_boundary.data(), h_boundary.size() * 4));
-    HIP_TRY(up(m->d_params.p, h_params.data(), h_params.size() * sizeof(MultiGraphParams)));
+    if (two_piece) HIP_TRY(up(m->d_params2.p, h_params2.data(), h_params2.size() * sizeof(Multi2GraphParams)));
+    else HIP_TRY(up(m->d_params.p, h_params.data(), h_params.size() * sizeof(MultiGraphParams)));
     HIP_TRY(up(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
     HIP_TRY(up(m->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
     HIP_TRY(up(b->d_qseq.p, qseq, qoff[n]));
@@ -2568,11 +2582,36 @@ int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const 
     *out = m.release();
     return POA_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int poa_multi_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                        const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    return multi_footprint_impl(graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, false, "poa_multi_footprint");
+}
+
+int poa_multi_footprint_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                               const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    return multi_footprint_impl(graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, true, "poa_multi_footprint_2piece");
+}
+
+int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                     const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, false, "poa_multi_create");
+}
+
+int poa_multi_create_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                            const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, true, "poa_multi_create_2piece");
+}
 
 // per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2), over the queries of all graphs; scan and
 // compaction of the pairs over all queries, as run_ckpt does for one graph
 int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: null argument");
+    // (the batch's model first: whatever the mode, this entry point cannot run a two-piece batch)
+    if (m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_2piece (it runs through poa_multi_run_2piece only)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run");
     if (mrc != POA_OK) return mrc;
     const TuneView T(cfg);
@@ -2653,6 +2692,95 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     return POA_OK;
 }
 
+// The same run under the two-piece model (poa_multi2.hpp), on a batch of poa_multi_create_2piece: the cell width by run_ckpt2's
+// bound for every graph that has queries, the chunks of the batch under either width.
+int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
+    if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");
+    if (!m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create (a two-piece run needs poa_multi_create_2piece: its footprint differs)");
+    const int mrc = multi_mode_check(cfg, "poa_multi_run_2piece", true);
+    if (mrc != POA_OK) return mrc;
+    const TuneView T(cfg);
+    poa_batch* b = &m->core;
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(b->device));
+    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_2piece: call poa_multi_stats/fetch at least every 256 runs");
+    b->last_mode = POA_MODE_CHECKPOINT2;
+    b->two_piece = false;   // (no full planes to fetch)
+    b->last_stream = stream;
+    // u16 cells only if every graph's own bound (run_ckpt2's ub: the first piece's costs, that graph's longest query and shortest
+    // path) allows them, and neither wide_planes nor the planes tunable asks for u32
+    bool narrow = !costs->wide_planes;
+    for (size_t g = 0; g < m->ub_open.size(); ++g)
+        narrow = narrow && (uint64_t)costs->gap_open1 * m->ub_open[g] + (uint64_t)costs->gap_extend1 * m->ub_extend[g] <= 65534;
+    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    b->narrow = narrow; b->compact = false; b->relative = false;
+    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    b->active_plan = 0;
+    const MultiPlan& pl = m->plan;
+    std::vector<hipEvent_t> events;
+    const size_t n_events = 2 + 3 * pl.chunks.size();
+    for (size_t k = 0; k < b->free_sets.size(); ++k) {
+        if (b->free_sets[k].size() == n_events) {
+            events = std::move(b->free_sets[k]);
+            b->free_sets.erase(b->free_sets.begin() + (long)k);
+            break;
+        }
+    }
+    if (events.empty()) {
+        events.resize(n_events);
+        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
+    }
+    b->runs.push_back(events);
+    HIP_TRY(hipEventRecord(events[0], stream));
+    if (b->n_queries == 0) {
+        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        HIP_TRY(hipEventRecord(events[1], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    b->sweep_bytes_written = m->stored_rows_pitch * (narrow ? 2 : 4);
+    size_t ev = 1;
+    for (const auto& ch : pl.chunks) {
+        Multi2Launch ml;
+        ml.graphs = m->d_params2.p; ml.graph_of = m->d_graph_of.p; ml.carry_off = m->d_carry_off.p; ml.carry = b->d_carry.p;
+        ml.first_query = ch.first; ml.n_queries = ch.count;
+        ml.x = costs->mismatch; ml.o1 = costs->gap_open1; ml.e1 = costs->gap_extend1; ml.e2 = costs->gap_extend2;
+        ml.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
+        const uint32_t max_pitch = ch.max_pitch;
+        const dim3 grid((ch.count + 3) / 4), block(256);
+        // NP follows the chunk's largest pitch: a strip of 64 x K x NP columns (K 8 for u16, 4 for u32) covers it up to 1024 columns
+#define LAUNCH_CKPT2_MULTI(KERNEL)                                                                       \
+    do {                                                                                                \
+        if (narrow) {                                                                                   \
+            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<uint16_t, 1>), grid, block, 0, stream, ml); \
+            else hipLaunchKernelGGL((KERNEL<uint16_t, 2>), grid, block, 0, stream, ml);                  \
+        } else {                                                                                        \
+            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<uint32_t, 1>), grid, block, 0, stream, ml); \
+            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<uint32_t, 2>), grid, block, 0, stream, ml); \
+            else hipLaunchKernelGGL((KERNEL<uint32_t, 4>), grid, block, 0, stream, ml);                  \
+        }                                                                                               \
+    } while (0)
+        LAUNCH_CKPT2_MULTI(poa2_ckpt_sweep_multi_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        LAUNCH_CKPT2_MULTI(poa2_ckpt_trace_multi_kernel);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+        HIP_TRY(hipEventRecord(events[ev++], stream));
+#undef LAUNCH_CKPT2_MULTI
+    }
+    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(events[ev], stream));
+    b->ran = true;
+    return POA_OK;
+}
+
 int poa_multi_fetch(poa_multi_t* m, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
                     uint32_t* flags, poa_stats_t* stats) {
     if (!m) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch: null batch");
@@ -2692,6 +2820,22 @@ int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const u
     int rc = poa_multi_create(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
     if (rc != POA_OK) return rc;
     rc = poa_multi_run(m, costs, cfg, nullptr);
+    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
+    poa_multi_destroy(m);
+    return rc;
+}
+
+int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs2_t* costs,
+                           const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs,
+                           uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi_2piece: null argument");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (costs->gap_extend1 < costs->gap_extend2)   // (before a batch is made for it)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    poa_multi_t* m = nullptr;
+    int rc = poa_multi_create_2piece(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
+    if (rc != POA_OK) return rc;
+    rc = poa_multi_run_2piece(m, costs, cfg, nullptr);
     if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
     poa_multi_destroy(m);
     return rc;

@@ -10,7 +10,7 @@ constexpr int ERR_INVALID_ARG = -1, ERR_UNSUPPORTED = -7;   // POA_ERR_INVALID_A
 }
 
 int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                     uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err) {
+                     uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool two_piece) {
     out = MultiPlan();
     if (!graph_qoff || !qoff || (n_graphs && !graphs)) { err = "multi-graph batch: null argument"; return ERR_INVALID_ARG; }
     if (graph_qoff[0] != 0) { err = "multi-graph batch: graph_qoff[0] is not 0"; return ERR_INVALID_ARG; }
@@ -44,7 +44,7 @@ int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64
             gp.snap_dst_base = first.snap_dst_base; gp.boundary_base = first.boundary_base;
         } else {
             if (segment_rows == 0 || segment_rows == in.own->segment_rows) gp.ckpt = *in.own;
-            else build_checkpoint_plan(*in.g, *in.sweep, segment_rows, gp.ckpt);
+            else build_checkpoint_plan(*in.g, *in.sweep, segment_rows, gp.ckpt, two_piece);
             gp.row_base = out.n_rows_total; gp.edge_base = out.n_edges_total; gp.snap_off_base = out.n_snap_off_total;
             gp.snap_dst_base = out.n_snap_dst_total; gp.boundary_base = out.n_boundary_total;
             out.n_rows_total += gp.n_rows; out.n_edges_total += gp.n_edges; out.n_snap_off_total += gp.ckpt.snap_off.size();
@@ -89,7 +89,8 @@ int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64
         }
         out.region_off[i] = cur.cells;
         cur.cells += cells;
-        const uint64_t cw = out.pitch[i] > MULTI_STRIP_COLUMNS ? 4ull * gp.n_rows : 0ull;
+        // two parities of two words per row (ckpt_rows), of three under the two-piece model (ckpt2_rows)
+        const uint64_t cw = out.pitch[i] > MULTI_STRIP_COLUMNS ? (two_piece ? 6ull : 4ull) * gp.n_rows : 0ull;
         if (cur.carry_words + cw > 0xFFFFFFFFull) {
             err = "multi-graph batch: the strip carries of one chunk exceed 2^32 words; cap workspace_bytes";
             return ERR_UNSUPPORTED;

@@ -25,6 +25,11 @@
 //                widest kernel variant (pitch > 1024 columns: 64 lanes x 8 u16 cells x Q 2, or x 4 u32 cells x Q 4) takes
 //                4 x n_rows(graph) words there.  Every variant the launch code selects for a chunk has strips of at least the
 //                chunk's largest pitch when that pitch is <= 1024, so a query of pitch <= 1024 never touches a carry.
+//
+// The two-piece variant (poa_multi_*_2piece, poa_multi2.hpp; `two_piece` below) is the same plan with the two-piece weights:
+// per graph the two-piece CheckpointPlan (three kept planes, five window planes: what poa_graph_checkpoint_plan2 gives for
+// that graph alone; MultiGraphIn::own is then the handle's two-piece plan), and 6 x n_rows carry words for a query wider than
+// one strip (ckpt2_rows: two parities of three words per row).  Its strips are 1024 columns under both cell types too.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -40,7 +45,7 @@ constexpr uint64_t MULTI_REGION_PAD_CELLS = 64;  // 256 bytes behind every query
 struct MultiGraphIn {            // what the plan reads of a graph handle
     const FlatGraph* g;
     const SweepRows* sweep;
-    const CheckpointPlan* own;   // the handle's plan at the engine's own segment length
+    const CheckpointPlan* own;   // the handle's plan at the engine's own segment length (two_piece: its two-piece plan)
 };
 
 struct MultiGraphPlan {
@@ -76,6 +81,6 @@ inline uint64_t multi_query_cells(const CheckpointPlan& cp, uint64_t len) {
 // workspace_bytes 0: no cap (one chunk).  A cap below the largest query's footprint is raised to it.
 // Returns 0, or -1 (invalid argument) / -7 (unsupported) — the values of POA_ERR_INVALID_ARG / POA_ERR_UNSUPPORTED — with `err` set.
 int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                     uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err);
+                     uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool two_piece = false);
 
 }  // namespace poa_amd

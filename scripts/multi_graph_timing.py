@@ -10,6 +10,10 @@ costs 4 / 6 / 2.  Per step, with the pairs fetched:
 (b) and (c) are the paths a host had before.  The first --warmup steps are dropped; medians with min / max of the rest.  Kernel-only
 times are the HIP-event sums of poa_stats_t (ms_forward, ms_traceback), summed over the calls of a step.  Writes
 profiles/pr_multi_graph/timing.json.
+
+--two-piece: the same shape and the same four paths under the two-piece model, costs 4 / 6,24 / 2,1: (a) poa_multi_run_2piece +
+poa_multi_fetch on a batch of poa_multi_create_2piece, (a1) poa_align_multi_2piece, (b) the loop of poa_align_batch_2piece_ex in
+POA_MODE_CHECKPOINT2, (c) the loop of the dense poa_align_batch_2piece.  Writes profiles/pr_multi_graph_2piece/timing.json.
 """
 import argparse
 import ctypes as C
@@ -30,8 +34,12 @@ def main():
     ap.add_argument("--length", type=int, default=200)
     ap.add_argument("--steps", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pr_multi_graph", "timing.json"))
+    ap.add_argument("--two-piece", action="store_true", help="the two-piece model, costs 4 / 6,24 / 2,1 (poa_multi_*_2piece)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    two = args.two_piece
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pr_multi_graph_2piece" if two else "pr_multi_graph", "timing.json")
     import numpy as np
     from poasta_amd import _lib, aligner, workloads as W
 
@@ -42,18 +50,21 @@ def main():
         packed.append((qseq, qoff))
         seqs.append([qseq[int(qoff[i]):int(qoff[i + 1])] for i in range(args.reads)])
     dgs = [aligner._device_graph(g) for g in graphs]
-    costs = aligner.GapAffine(4, 2, 6)
+    costs = aligner.GapAffine2Piece(4, 2, 6, 1, 24) if two else aligner.GapAffine(4, 2, 6)
     c = costs._c()
     L = _lib.lib()
     n_total = args.graphs * args.reads
     cells = sum(g.n * (int(qoff[-1]) + args.reads) for g, (_, qoff) in zip(graphs, packed))
 
-    mb = aligner.MultiGraphBatch(graphs, seqs)
-    al = aligner.PoastaAligner(aligner.AffineMinGapCost(costs))
+    mb = aligner.MultiGraphBatch(graphs, seqs, two_piece=two)
+    al = aligner.PoastaAligner(aligner.Affine2PieceDijkstra(costs) if two else aligner.AffineMinGapCost(costs))
+
+    last_multi_stats = {}
 
     def step_multi():
         mb.run(costs)
         r = mb.fetch()
+        last_multi_stats.update(r.stats)
         return r, r.stats["ms_forward"], r.stats["ms_traceback"]
 
     def step_one_shot():
@@ -61,7 +72,10 @@ def main():
         return r, r.stats["ms_forward"], r.stats["ms_traceback"]
 
     def loop(mode):
-        cfg = aligner.make_config(mode)
+        if not two:
+            cfg = aligner.make_config(mode)
+        elif mode == "checkpoint":
+            cfg = aligner.make_config("checkpoint2")   # (the dense two-piece call takes no config)
 
         def step():
             score, flags, pairs, counts = [], [], [], []
@@ -72,8 +86,16 @@ def main():
                 s, f, po = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n + 1, np.uint64)
                 pr = np.zeros((cap, 2), np.uint32)
                 st = _lib.PoaStats()
-                _lib.check(L.poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, aligner._p(qseq), aligner._p(qoff), aligner._p(s),
-                                                aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st), 0))
+                if not two:
+                    _lib.check(L.poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, aligner._p(qseq), aligner._p(qoff), aligner._p(s),
+                                                    aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st), 0))
+                elif mode == "dense":
+                    _lib.check(L.poa_align_batch_2piece(dg.handle, C.byref(c), n, aligner._p(qseq), aligner._p(qoff), aligner._p(s),
+                                                        aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st), 0))
+                else:
+                    _lib.check(L.poa_align_batch_2piece_ex(dg.handle, C.byref(c), C.byref(cfg), n, aligner._p(qseq), aligner._p(qoff),
+                                                           aligner._p(s), aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st),
+                                                           None, 0))
                 fwd += st.ms_forward
                 tb += st.ms_traceback
                 score.append(s); flags.append(f); pairs.append(pr[:int(po[n])]); counts.append(np.diff(po.astype(np.int64)))
@@ -100,10 +122,10 @@ def main():
         return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
 
     out = {"workload": "%d graphs x %d reads of %d bp, LinearishPOA backbone 190" % (args.graphs, args.reads, args.length),
-           "costs": "4 / 6 / 2 (mismatch / open / extend)", "graphs": args.graphs, "queries": n_total,
+           "costs": "4 / 6,24 / 2,1 (mismatch / open1,open2 / extend1,extend2)" if two else "4 / 6 / 2 (mismatch / open / extend)", "graphs": args.graphs, "queries": n_total,
            "rows_per_graph": {"min": min(g.n for g in graphs), "max": max(g.n for g in graphs)}, "cells": cells,
            "steps": args.steps, "warmup": args.warmup, "multi_workspace_bytes": mb.workspace_bytes(),
-           "multi_footprint_bytes": aligner.multi_footprint(graphs, seqs)[0],
+           "multi_footprint_bytes": aligner.multi_footprint(graphs, seqs, two_piece=two)[0],
            "results_equal": all(sums[k] == sums["loop_dense"] for k in sums)}
     for name in paths:
         out[name] = {"ms_step": med([r[0] for r in rows[name]]), "ms_forward_kernels": med([r[1] for r in rows[name]]),
@@ -112,6 +134,8 @@ def main():
     for name in ("multi_run_fetch", "multi_one_shot"):
         for base in ("loop_checkpoint", "loop_dense"):
             out["ms_step_ratio_%s_over_%s" % (name, base)] = round(out[name]["ms_step"]["median"] / out[base]["ms_step"]["median"], 4)
+    # the resident run's own record (poa_stats_t of the last step): cell bytes stored, chunks, the passes
+    out["multi_run_stats"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in last_multi_stats.items()}
     mb.close()
     print(json.dumps(out))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
