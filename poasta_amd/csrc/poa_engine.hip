@@ -273,7 +273,7 @@ struct poa_batch {
     bool band_used = false;
     uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
 
-    // one event set per run since the last stats call: [begin, (fwd_end, tb_end) per chunk..., end]
+    // one event set per run since the last stats call, written by RunFrame and read by collect_stats
     std::vector<std::vector<hipEvent_t>> runs;
     std::vector<std::vector<hipEvent_t>> free_sets;
     bool ran = false;
@@ -335,6 +335,119 @@ static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     stats->ms_forward = fwd; stats->ms_traceback = tb; stats->ms_exact = ex; stats->ms_total = total;
     for (auto& r : b->runs) b->free_sets.push_back(std::move(r));
     b->runs.clear();
+}
+
+// ---- the frame of a run: every run path of a poa_batch (and of the batches built around one) goes through here ------------
+// The event set collect_stats reads back is written here and nowhere else: [begin, (forward end, traceback end, exact end) per
+// chunk ..., end], 2 + 3 x chunks events.  A path calls open, begin, three marks per chunk, and one of the ends.
+struct RunFrame {
+    poa_batch* b = nullptr;
+    hipStream_t stream = nullptr;
+    std::vector<hipEvent_t> events;
+    size_t ev = 1;
+
+    // At most 256 event sets wait for poa_*_stats / _fetch; `refusal` is the entry point's own text.  A path writes nothing into
+    // the batch before this passes, so a refused run leaves the batch as the previous run left it.
+    int open(poa_batch* batch, const std::string& refusal) {
+        b = batch;
+        if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, refusal);
+        return POA_OK;
+    }
+    // takes a free event set of the run's size or creates one, and records the begin event
+    int begin(hipStream_t s, size_t n_chunks) {
+        stream = s;
+        b->last_stream = stream;
+        const size_t n_events = 2 + 3 * n_chunks;
+        for (size_t k = 0; k < b->free_sets.size(); ++k) {
+            if (b->free_sets[k].size() == n_events) {
+                events = std::move(b->free_sets[k]);
+                b->free_sets.erase(b->free_sets.begin() + (long)k);
+                break;
+            }
+        }
+        if (events.empty()) {
+            events.reserve(n_events);
+            while (events.size() < n_events) {
+                hipEvent_t e;
+                const hipError_t rc = hipEventCreate(&e);
+                if (rc != hipSuccess) {
+                    for (auto made : events) (void)hipEventDestroy(made);
+                    return fail(POA_ERR_HIP, std::string("hipEventCreate(&e): ") + hipGetErrorString(rc));
+                }
+                events.push_back(e);
+            }
+        }
+        b->runs.push_back(events);
+        HIP_TRY(hipEventRecord(events[0], stream));
+        return POA_OK;
+    }
+    // the next `n` marks of the current chunk, in the order forward end, traceback end, exact end
+    int mark(int n = 1) {
+        while (n-- > 0) HIP_TRY(hipEventRecord(events[ev++], stream));
+        return POA_OK;
+    }
+    int end() {
+        HIP_TRY(hipEventRecord(events[ev], stream));
+        b->ran = true;
+        return POA_OK;
+    }
+    // a batch without queries: an empty pair list where the batch has pair buffers, and the run is over
+    int end_empty(bool has_pairs) {
+        if (has_pairs) HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
+        return end();
+    }
+    // the pairs of all queries: offsets by a scan of the counts, then compaction of the traceback scratch into d_pairs
+    int end_pairs() {
+        hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
+                           b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
+        HIP_TRY(hipGetLastError());
+        return end();
+    }
+};
+
+// u16 cells whenever every value that can matter fits.  u16 arithmetic saturates at 0xFFFF = INF, so every stored value is
+// min(true value, 0xFFFF); costs are non-negative, hence every cell on an optimal path — and every predecessor candidate the
+// traceback can accept — has a value <= the final score, and the final score is at most
+//     ub = [o + e*L] + [o + e*(nodes on the shortest start->end path)]      (insert the query, delete that path),
+// each bracket counted only if its length is not zero: ub = o * n_open + e * n_extend.  ub <= 0xFFFE  =>  everything the result
+// depends on is exact in u16.  (The cruder bound (rows + L + 2) * max(x, o+e) on ANY finite value is always >= ub.)  The
+// two-piece model takes the first piece's costs: a gap never costs more than its first-piece price.
+static uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend) { return open * n_open + extend * n_extend; }
+static bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend) {
+    return score_bound(open, extend, n_open, n_extend) <= 65534;
+}
+// the same for one graph and the longest query that meets it
+static uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t max_len, const FlatGraph& fg) {
+    return score_bound(open, extend, (max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0), max_len + fg.min_path_nodes);
+}
+static bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t max_len, const FlatGraph& fg) {
+    return u16_cells_suffice(open, extend, (max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0), max_len + fg.min_path_nodes);
+}
+// POA_PLANES=32 forces u32 cells (debug / A-B)
+static bool planes32(const TuneView& T) { const int* pv = T.ptr(POA_TUNE_PLANES); return pv && *pv == 32; }
+
+// the layout of the last run, as poa_batch_last_layout and the plane fetches read it
+static void set_layout(poa_batch* b, bool narrow, bool compact = false, bool relative = false) {
+    b->narrow = narrow; b->compact = compact; b->relative = relative;
+    b->dense_narrow = narrow; b->dense_compact = compact; b->dense_relative = relative; b->dense_derived_gaps = false;
+}
+
+// The kernels that keep a row in registers take the cell type and the number of column groups per lane as template arguments: a
+// group is 512 columns of u16 cells or 256 of u32, and the chunk's largest pitch says how many a strip of up to 1024 columns
+// needs.  `launch` receives both as tags (a value of the cell type, a std::integral_constant) and names the kernel.
+template <typename Launch>
+static void launch_by_pitch(bool narrow, uint32_t max_pitch, Launch&& launch) {
+    using std::integral_constant;
+    if (narrow) {
+        if (max_pitch <= 512) launch(uint16_t{}, integral_constant<int, 1>{});
+        else launch(uint16_t{}, integral_constant<int, 2>{});
+    } else {
+        if (max_pitch <= 256) launch(uint32_t{}, integral_constant<int, 1>{});
+        else if (max_pitch <= 512) launch(uint32_t{}, integral_constant<int, 2>{});
+        else launch(uint32_t{}, integral_constant<int, 4>{});
+    }
 }
 
 // the 1024-column multi-wave kernel when the chunk fills the chip with one wave per 1024 columns (else 512-column strips of
@@ -814,45 +927,20 @@ static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_confi
 // reduction (poa_align_batch_2piece_ex) opens a gap at open1 + extend1 - extend2, which need not fit poa_costs_t.
 static int run_sweep(poa_batch* b, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const TuneView& T, hipStream_t stream) {
     HIP_TRY(hipSetDevice(b->device));
-    const poa_graph* gh = b->graph;
-    const FlatGraph& fg = gh->g;
-    b->last_mode = POA_MODE_SCORE;
-    b->two_piece = false;
-    b->last_stream = stream;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
-    // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the end cell depends on is exact in them
-    const uint64_t ub = (b->max_len ? (uint64_t)cost_o + (uint64_t)cost_e * b->max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)cost_o + (uint64_t)cost_e * fg.min_path_nodes : 0);
-    bool narrow = ub <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    const FlatGraph& fg = b->graph->g;
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
+    const bool narrow = u16_cells_suffice(cost_o, cost_e, b->max_len, fg) && !planes32(T);
     bool want_px = true;
     if (const int* xv = T.ptr(POA_TUNE_PX)) want_px = (*xv) != 0;
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    if (const int rc = run.begin(stream, b->plan[0].chunks.size())) return rc;
+    b->last_mode = POA_MODE_SCORE;
+    b->two_piece = false;
+    set_layout(b, narrow);
     b->active_plan = 0;
     const poa_batch::Plan& PL = b->cur();
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * PL.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(false);
     b->sweep_bytes_written = 0;
-    size_t ev = 1;
     for (const auto& ch : PL.chunks) {
         SweepParams sp;
         sp.rows = b->d_rows.p; sp.pred_rows = b->d_pred_rows.p; sp.slot = b->d_dslot.p; sp.pred_slot = b->d_pred_dslot.p;
@@ -872,22 +960,13 @@ static int run_sweep(poa_batch* b, uint32_t cost_x, uint32_t cost_o, uint32_t co
         // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
         b->sweep_bytes_written += 2ull * b->sweep_slotted * (px ? 2048ull * ch.count : pitch_sum * (narrow ? 2 : 4));
         if (px) hipLaunchKernelGGL(poa_sweep_px_kernel, dim3(blocks), dim3(256), 0, stream, sp);
-        else if (narrow) {
-            if (max_pitch <= 512) hipLaunchKernelGGL((poa_sweep_kernel<1, uint16_t>), dim3(blocks), dim3(256), 0, stream, sp);
-            else hipLaunchKernelGGL((poa_sweep_kernel<2, uint16_t>), dim3(blocks), dim3(256), 0, stream, sp);
-        } else {
-            if (max_pitch <= 256) hipLaunchKernelGGL((poa_sweep_kernel<1, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
-            else if (max_pitch <= 512) hipLaunchKernelGGL((poa_sweep_kernel<2, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
-            else hipLaunchKernelGGL((poa_sweep_kernel<4, uint32_t>), dim3(blocks), dim3(256), 0, stream, sp);
-        }
+        else launch_by_pitch(narrow, max_pitch, [&](auto cell, auto q) {
+            hipLaunchKernelGGL((poa_sweep_kernel<decltype(q)::value, decltype(cell)>), dim3(blocks), dim3(256), 0, stream, sp);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark(3)) return rc;
     }
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end();
 }
 
 // Checkpointed run of a batch created for it: per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2);
@@ -896,42 +975,18 @@ static int run_ckpt(poa_batch* b, const poa_costs_t* costs, const TuneView& T, h
     HIP_TRY(hipSetDevice(b->device));
     const FlatGraph& fg = b->graph->g;
     const CheckpointPlan& cp = b->ckpt_plan;
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
+    const bool narrow = u16_cells_suffice(costs->gap_open, costs->gap_extend, b->max_len, fg) && !planes32(T);
+    const int plan = (narrow && !b->plan16_same) ? 1 : 0;
+    if (const int rc = run.begin(stream, b->plan[plan].chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT;
     b->two_piece = false;
-    b->last_stream = stream;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
-    // u16 cells under the bound dense mode uses (poa_batch_run_ex): every value the result depends on is exact in them
-    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * b->max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * fg.min_path_nodes : 0);
-    bool narrow = ub <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
-    b->active_plan = (narrow && !b->plan16_same) ? 1 : 0;
+    set_layout(b, narrow);
+    b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * PL.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     b->sweep_bytes_written = 0;
-    size_t ev = 1;
     for (const auto& ch : PL.chunks) {
         CkptParams kp;
         kp.rows = b->d_rows.p; kp.pred_rows = b->d_pred_rows.p; kp.slot = b->d_dslot.p; kp.pred_slot = b->d_pred_dslot.p;
@@ -951,34 +1006,18 @@ static int run_ckpt(poa_batch* b, const poa_costs_t* costs, const TuneView& T, h
         // every segment, which a Global alignment does unless an edge skips one
         b->sweep_bytes_written += (2ull * (b->sweep_slotted + cp.n_snap_rows) + 3ull * fg.n) * pitch_sum * (narrow ? 2 : 4);
         const dim3 grid((ch.count + 3) / 4), block(256);
-#define LAUNCH_CKPT(KERNEL)                                                                              \
-    do {                                                                                                \
-        if (narrow) {                                                                                   \
-            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<1, uint16_t>), grid, block, 0, stream, kp); \
-            else hipLaunchKernelGGL((KERNEL<2, uint16_t>), grid, block, 0, stream, kp);                  \
-        } else {                                                                                        \
-            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<1, uint32_t>), grid, block, 0, stream, kp); \
-            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<2, uint32_t>), grid, block, 0, stream, kp); \
-            else hipLaunchKernelGGL((KERNEL<4, uint32_t>), grid, block, 0, stream, kp);                  \
-        }                                                                                               \
-    } while (0)
-        LAUNCH_CKPT(poa_ckpt_sweep_kernel);
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto q) {
+            hipLaunchKernelGGL((poa_ckpt_sweep_kernel<decltype(q)::value, decltype(cell)>), grid, block, 0, stream, kp);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        LAUNCH_CKPT(poa_ckpt_trace_kernel);
+        if (const int rc = run.mark()) return rc;
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto q) {
+            hipLaunchKernelGGL((poa_ckpt_trace_kernel<decltype(q)::value, decltype(cell)>), grid, block, 0, stream, kp);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-#undef LAUNCH_CKPT
+        if (const int rc = run.mark(2)) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
 int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream_v) { return poa_batch_run_ex(b, costs, nullptr, stream_v); }
@@ -986,7 +1025,6 @@ int poa_batch_run(poa_batch_t* b, const poa_costs_t* costs, void* stream_v) { re
 int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!b || !costs) return fail(POA_ERR_INVALID_ARG, "poa_batch_run: null argument");
     const TuneView T(cfg);   // what this call overrides, read once
-    b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
     uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
     if (mode == POA_MODE_CHECKPOINT2) {
         if (b->ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_ex: a POA_MODE_CHECKPOINT2 batch runs through poa_batch_run_2piece only");
@@ -1022,20 +1060,11 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         int rc = prepare_exact(b, costs, cfg);
         if (rc != POA_OK) return rc;
     }
-    b->last_mode = mode;
-    b->two_piece = false;
-    b->last_stream = stream;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
-    // u16 planes whenever every value that can matter fits.  u16 arithmetic saturates at 0xFFFF = INF, so every stored
-    // value is min(true value, 0xFFFF); costs are non-negative, hence every cell on an optimal path — and every
-    // predecessor candidate the traceback can accept — has a value <= the final score, and the final score is at most
-    //     ub = [o + e*L] + [o + e*(nodes on the shortest start->end path)]      (insert the query, delete that path).
-    // ub <= 65534  =>  everything the result depends on is exact in u16.  (The cruder bound (rows + L + 2) * max(x, o+e)
-    // on ANY finite value is always >= ub.)  POA_PLANES=32 forces u32 (debug / A-B).
-    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * b->max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * fg.min_path_nodes : 0);
-    bool narrow = ub <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
+    // u16 planes under the bound of u16_cells_suffice; the flag variants of the px kernel below take the bound itself
+    const uint64_t ub = score_bound(costs->gap_open, costs->gap_extend, b->max_len, fg);
+    bool narrow = u16_cells_suffice(costs->gap_open, costs->gap_extend, b->max_len, fg) && !planes32(T);
     // compact layout (u16 only): 4-bit codes instead of the I plane, D rows only where they are read back.
     // POA_CFG_FULL_PLANES (or POA_COMPACT=0) keeps all three planes, e.g. for poa_batch_fetch_planes.
     const bool want_full = cfg && (cfg->flags & POA_CFG_FULL_PLANES);
@@ -1045,7 +1074,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     if (const int* pv2 = T.ptr(POA_TUNE_PACKED)) packed = (*pv2) != 0;
     // Scores beyond u16 (a read against a much longer graph, Global): store every cell relative to the depth potential
     // e * (row_depth - column) (FlatGraph::row_depth).  All moves keep non-negative costs there, so the saturation argument
-    // above holds for the relative values, and the largest one on an optimal path is the end cell's:
+    // of u16_cells_suffice holds for the relative values, and the largest one on an optimal path is the end cell's:
     //     S* - e * (shortest path nodes - L)  <=  ub - e * min_path_nodes + e * L  =  2 * (o + e * L).
     // Only the pairs-across-quads kernels (compact layout) implement it; POA_RELATIVE=0 keeps u32 planes, =1 forces it
     // wherever the bound allows (A-B against the absolute encodings).
@@ -1056,35 +1085,17 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         else relative = rel_ub <= 65534 && !want_full && packed;
     }
     if (relative) { narrow = true; compact = true; }
-    b->relative = relative;
-    b->dense_narrow = narrow; b->dense_compact = compact; b->dense_relative = relative; b->dense_derived_gaps = false;
-    b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
-    b->narrow = narrow;
-    b->compact = compact;
     // 2-byte elements let twice the queries share the workspace; the exact replay needs the u32 plan
-    b->active_plan = (narrow && mode == POA_MODE_DENSE && !b->plan16_same) ? (compact ? 2 : 1) : 0;
+    const int plan = (narrow && mode == POA_MODE_DENSE && !b->plan16_same) ? (compact ? 2 : 1) : 0;
+    if (const int rc = run.begin(stream, b->plan[plan].chunks.size())) return rc;
+    b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
+    b->last_mode = mode;
+    b->two_piece = false;
+    set_layout(b, narrow, compact, relative);
+    b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
+    b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * PL.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     uint32_t spec_depth = 12;  // traceback speculation depth (lanes per round) of the full-plane layouts; the compact one: see the launch below
     if (const int* sv = T.ptr(POA_TUNE_TB_DEPTH)) { const int v = (*sv); if (v >= 1 && v <= 64) spec_depth = (uint32_t)v; }
     int tb_group = 16;   // POA_TB_GROUP override (lanes per walk); default: chosen per chunk at the launch below
@@ -1103,7 +1114,6 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         if (b->d_band_count.n < PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(PL.chunks.size()));
         HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, PL.chunks.size() * 4, stream));
     }
-    size_t ev = 1;
     for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
         const auto& ch = PL.chunks[ci];
         TbParams tp;
@@ -1234,7 +1244,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
             else LAUNCH_FWD(4, uint32_t);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark()) return rc;
 
         if (!(fuse_tb && !relative && max_pitch <= 1024 && (!compact || packed))) {
             // Lanes per walk: as many as keep the launch within ~6 000 waves (what the chip holds at this kernel's occupancy
@@ -1257,7 +1267,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
             else hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark()) return rc;
 
         if (mode != POA_MODE_DENSE) {
             // exact replay of the reference's search on the (re-initialised, u32) planes of this chunk
@@ -1489,16 +1499,9 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
             HIP_TRY(hipGetLastError());
             b->narrow = false; b->compact = false; b->relative = false;  // the planes now hold the replayed u32 table
         }
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark()) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
 int poa_batch_fetch(poa_batch_t* b, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
@@ -1728,40 +1731,19 @@ static int run_ckpt2(poa_batch* b, const poa_costs2_t* costs, hipStream_t stream
     HIP_TRY(hipSetDevice(b->device));
     const FlatGraph& fg = b->graph->g;
     const CheckpointPlan& cp = b->ckpt_plan;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
     if (b->n_queries && cp.n_segments() == 0) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: the graph has no rows");
+    // cell width: the first piece's costs bound the optimum; wide_planes forces u32
+    const bool narrow = u16_cells_suffice(costs->gap_open1, costs->gap_extend1, b->max_len, fg) && !costs->wide_planes;
+    const int plan = (narrow && !b->plan16_same) ? 1 : 0;   // the batch is sized for u32: a u16 run packs twice the queries per chunk
+    if (const int rc = run.begin(stream, b->plan[plan].chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT2;
     b->two_piece = false;   // (no full planes to fetch)
-    b->last_stream = stream;
-    // cell width: the rule of the dense two-piece run (the first piece's costs bound the optimum; wide_planes forces u32)
-    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * b->max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * fg.min_path_nodes : 0);
-    const bool narrow = ub <= 65534 && !costs->wide_planes;
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
-    b->active_plan = (narrow && !b->plan16_same) ? 1 : 0;   // the batch is sized for u32: a u16 run packs twice the queries per chunk
+    set_layout(b, narrow);
+    b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * PL.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     b->sweep_bytes_written = 0;
     Ckpt2Params kp;
     kp.rows = b->d_rows.p; kp.pred_rows = b->d_pred_rows.p; kp.slot = b->d_dslot.p; kp.pred_slot = b->d_pred_dslot.p;
@@ -1774,7 +1756,6 @@ static int run_ckpt2(poa_batch* b, const poa_costs2_t* costs, hipStream_t stream
     kp.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
     kp.scratch_off = b->d_scratch_off.p; kp.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p);
     kp.score = b->d_score.p; kp.flags = b->d_flags.p; kp.n_pairs = b->d_npairs.p;
-    size_t ev = 1;
     for (const auto& ch : PL.chunks) {
         kp.first_query = ch.first; kp.n_queries = ch.count;
         uint64_t pitch_sum = 0;
@@ -1786,21 +1767,13 @@ static int run_ckpt2(poa_batch* b, const poa_costs2_t* costs, hipStream_t stream
         if (narrow) hipLaunchKernelGGL((poa2_ckpt_sweep_kernel<uint16_t, 2>), dim3(ch.count), dim3(64), 0, stream, kp);
         else hipLaunchKernelGGL((poa2_ckpt_sweep_kernel<uint32_t, 4>), dim3(ch.count), dim3(64), 0, stream, kp);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark()) return rc;
         if (narrow) hipLaunchKernelGGL((poa2_ckpt_trace_kernel<uint16_t, 2>), dim3(ch.count), dim3(64), 0, stream, kp);
         else hipLaunchKernelGGL((poa2_ckpt_trace_kernel<uint32_t, 4>), dim3(ch.count), dim3(64), 0, stream, kp);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark(2)) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
 int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
@@ -1831,44 +1804,23 @@ int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_co
     if (b->ckpt) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: the batch was created for POA_MODE_CHECKPOINT (it holds no full score planes)");
     HIP_TRY(hipSetDevice(b->device));
     const FlatGraph& fg = b->graph->g;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs");
-    // cell width: the rule of run_two_piece (the first piece's costs bound the optimum; wide_planes forces u32)
-    const uint64_t ub = (b->max_len ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * b->max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * fg.min_path_nodes : 0);
-    const bool narrow = ub <= 65534 && !costs->wide_planes;
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
+    // cell width: the first piece's costs bound the optimum; wide_planes forces u32
+    const bool narrow = u16_cells_suffice(costs->gap_open1, costs->gap_extend1, b->max_len, fg) && !costs->wide_planes;
     if (!narrow && b->n_queries && b->plan[3].chunks.empty()) {
         const int rc = prepare_two_piece_u32(b);
         if (rc != POA_OK) return rc;
     }
+    // u16: five 2-byte planes inside the query's region of the 4-byte plan (2.5 of its 3 x rows x pitch elements)
+    const int plan = narrow ? 0 : 3;
+    if (const int rc = run.begin(stream, b->plan[plan].chunks.size())) return rc;
     b->last_mode = POA_MODE_DENSE;
     b->two_piece = true;
-    b->last_stream = stream;
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
-    // u16: five 2-byte planes inside the query's region of the 4-byte plan (2.5 of its 3 x rows x pitch elements)
-    b->active_plan = narrow ? 0 : 3;
+    set_layout(b, narrow);
+    b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * PL.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     TwoPieceBatchParams P;
     P.rows = b->d_rows.p; P.pred_rows = b->d_pred_rows.p; P.n_rows = fg.n; P.start_row = fg.start_row; P.end_row = fg.end_row;
     P.qseq = b->d_qseq.p; P.qoff = b->d_qoff.p; P.pitch = 0; P.planes = b->d_planes.p;
@@ -1878,28 +1830,19 @@ int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_co
     P.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p); P.scratch_stride = 0;
     P.exact_pass = 0; P.ex_status = nullptr; P.ex_end = nullptr;
     P.q_pitch = b->d_pitch.p; P.plane_off = PL.d_off.p; P.off_scale = narrow ? 2u : 1u; P.scratch_off = b->d_scratch_off.p;
-    size_t ev = 1;
     for (const auto& ch : PL.chunks) {
         P.first_query = ch.first; P.n_queries = ch.count;
         // one wave per query, previous row in registers for up to 1024 columns: the launch shapes of run_two_piece
         if (narrow) hipLaunchKernelGGL((poa2_forward_kernel<uint16_t, 2, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
         else hipLaunchKernelGGL((poa2_forward_kernel<uint32_t, 4, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark()) return rc;
         if (narrow) hipLaunchKernelGGL((poa2_traceback_kernel<uint16_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
         else hipLaunchKernelGGL((poa2_traceback_kernel<uint32_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark(2)) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
 int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2) {
@@ -2008,10 +1951,8 @@ int poa_align_batch_ex(const poa_graph_t* g, const poa_costs_t* costs, const poa
             max_len = std::max(max_len, L);
             elems += 3ull * g->g.n * (((L + 1 + 63) / 64) * 64);
         }
-        const uint64_t ub = (max_len ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * max_len : 0) +
-                            (g->g.min_path_nodes ? (uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * g->g.min_path_nodes : 0);
         const bool dense = !cfg || (cfg->mode == POA_MODE_DENSE && cfg->span == POA_SPAN_GLOBAL);
-        if (dense && ub <= 65534 && !T.ptr(POA_TUNE_PLANES)) {
+        if (dense && u16_cells_suffice(costs->gap_open, costs->gap_extend, max_len, g->g) && !T.ptr(POA_TUNE_PLANES)) {
             size_t free_b = 0, total_b = 0;
             if (hipSetDevice(device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess && elems * 2 < free_b / 2)
                 ws_hint = elems * 2;
@@ -2131,12 +2072,8 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
     const uint64_t per_query = 5ull * fg.n * pitch;   // plane elements
     if (per_query >= (1ull << 34)) return fail(POA_ERR_UNSUPPORTED, "two-piece pass: planes of one query too large");
     if (exact && per_query >= (1ull << 32)) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: the visited table of one query exceeds 2^32 cells");
-    // u16 planes under the bound of the one-piece pass (poa_batch_run_ex) taken with the first piece's costs: a gap never
-    // costs more than its first-piece price, so [o1 + e1 L] + [o1 + e1 (shortest path)] bounds the optimum here too
-    const uint64_t ub = (max_len ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * max_len : 0) +
-                        (fg.min_path_nodes ? (uint64_t)costs->gap_open1 + (uint64_t)costs->gap_extend1 * fg.min_path_nodes : 0);
-    bool narrow = ub <= 65534;
-    if (costs->wide_planes || exact) narrow = false;   // (the replayed table is u32)
+    // u16 planes under the bound of the one-piece pass taken with the first piece's costs (the replayed table is u32)
+    const bool narrow = u16_cells_suffice(costs->gap_open1, costs->gap_extend1, max_len, fg) && !costs->wide_planes && !exact;
     const uint64_t elem = narrow ? 2 : 4;
     // replay workspace per query slot (prepare_exact's sizes with five stacks per priority; the pool holds the entries live
     // at once — popped slots are reused — at cfg->queue_entries_per_cell entries per cell, default 0.5)
@@ -2607,7 +2544,7 @@ int poa_multi_create_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs,
 }
 
 // per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2), over the queries of all graphs; scan and
-// compaction of the pairs over all queries, as run_ckpt does for one graph
+// compaction of the pairs over all queries
 int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: null argument");
     // (the batch's model first: whatever the mode, this entry point cannot run a two-piece batch)
@@ -2618,42 +2555,20 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     poa_batch* b = &m->core;
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(b->device));
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_multi_run: call poa_multi_stats/fetch at least every 256 runs")) return rc;
+    // u16 cells only if every graph's own bound (that graph's longest query and shortest path) allows them
+    bool narrow = !planes32(T);
+    for (size_t g = 0; g < m->ub_open.size(); ++g)
+        narrow = narrow && u16_cells_suffice(costs->gap_open, costs->gap_extend, m->ub_open[g], m->ub_extend[g]);
+    const MultiPlan& pl = m->plan;
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT;
     b->two_piece = false;
-    b->last_stream = stream;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_multi_run: call poa_multi_stats/fetch at least every 256 runs");
-    // u16 cells only if every graph's own bound (run_ckpt's ub, with that graph's longest query and shortest path) allows them
-    bool narrow = true;
-    for (size_t g = 0; g < m->ub_open.size(); ++g)
-        narrow = narrow && (uint64_t)costs->gap_open * m->ub_open[g] + (uint64_t)costs->gap_extend * m->ub_extend[g] <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    set_layout(b, narrow);
     b->active_plan = 0;
-    const MultiPlan& pl = m->plan;
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * pl.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     b->sweep_bytes_written = m->stored_rows_pitch * (narrow ? 2 : 4);
-    size_t ev = 1;
     for (const auto& ch : pl.chunks) {
         MultiLaunch ml;
         ml.graphs = m->d_params.p; ml.graph_of = m->d_graph_of.p; ml.carry_off = m->d_carry_off.p; ml.carry = b->d_carry.p;
@@ -2661,39 +2576,22 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
         ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
         const uint32_t max_pitch = ch.max_pitch;
         const dim3 grid((ch.count + 3) / 4), block(256);
-        // Q follows the chunk's largest pitch, as LAUNCH_CKPT does for a single graph
-#define LAUNCH_CKPT_MULTI(KERNEL)                                                                        \
-    do {                                                                                                \
-        if (narrow) {                                                                                   \
-            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<1, uint16_t>), grid, block, 0, stream, ml); \
-            else hipLaunchKernelGGL((KERNEL<2, uint16_t>), grid, block, 0, stream, ml);                  \
-        } else {                                                                                        \
-            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<1, uint32_t>), grid, block, 0, stream, ml); \
-            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<2, uint32_t>), grid, block, 0, stream, ml); \
-            else hipLaunchKernelGGL((KERNEL<4, uint32_t>), grid, block, 0, stream, ml);                  \
-        }                                                                                               \
-    } while (0)
-        LAUNCH_CKPT_MULTI(poa_ckpt_sweep_multi_kernel);
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto q) {
+            hipLaunchKernelGGL((poa_ckpt_sweep_multi_kernel<decltype(q)::value, decltype(cell)>), grid, block, 0, stream, ml);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        LAUNCH_CKPT_MULTI(poa_ckpt_trace_multi_kernel);
+        if (const int rc = run.mark()) return rc;
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto q) {
+            hipLaunchKernelGGL((poa_ckpt_trace_multi_kernel<decltype(q)::value, decltype(cell)>), grid, block, 0, stream, ml);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-#undef LAUNCH_CKPT_MULTI
+        if (const int rc = run.mark(2)) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
-// The same run under the two-piece model (poa_multi2.hpp), on a batch of poa_multi_create_2piece: the cell width by run_ckpt2's
-// bound for every graph that has queries, the chunks of the batch under either width.
+// The same run under the two-piece model (poa_multi2.hpp), on a batch of poa_multi_create_2piece: the cell width by the first
+// piece's bound for every graph that has queries, the chunks of the batch under either width.
 int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");
     if (!m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create (a two-piece run needs poa_multi_create_2piece: its footprint differs)");
@@ -2705,43 +2603,21 @@ int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_co
         return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(b->device));
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_2piece: call poa_multi_stats/fetch at least every 256 runs");
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_multi_run_2piece: call poa_multi_stats/fetch at least every 256 runs")) return rc;
+    // u16 cells only if every graph's own bound (the first piece's costs, that graph's longest query and shortest path) allows
+    // them, and neither wide_planes nor the planes tunable asks for u32
+    bool narrow = !costs->wide_planes && !planes32(T);
+    for (size_t g = 0; g < m->ub_open.size(); ++g)
+        narrow = narrow && u16_cells_suffice(costs->gap_open1, costs->gap_extend1, m->ub_open[g], m->ub_extend[g]);
+    const MultiPlan& pl = m->plan;
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT2;
     b->two_piece = false;   // (no full planes to fetch)
-    b->last_stream = stream;
-    // u16 cells only if every graph's own bound (run_ckpt2's ub: the first piece's costs, that graph's longest query and shortest
-    // path) allows them, and neither wide_planes nor the planes tunable asks for u32
-    bool narrow = !costs->wide_planes;
-    for (size_t g = 0; g < m->ub_open.size(); ++g)
-        narrow = narrow && (uint64_t)costs->gap_open1 * m->ub_open[g] + (uint64_t)costs->gap_extend1 * m->ub_extend[g] <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
+    set_layout(b, narrow);
     b->active_plan = 0;
-    const MultiPlan& pl = m->plan;
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * pl.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipMemsetAsync(b->d_pair_off.p, 0, 8, stream));
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (b->n_queries == 0) return run.end_empty(true);
     b->sweep_bytes_written = m->stored_rows_pitch * (narrow ? 2 : 4);
-    size_t ev = 1;
     for (const auto& ch : pl.chunks) {
         Multi2Launch ml;
         ml.graphs = m->d_params2.p; ml.graph_of = m->d_graph_of.p; ml.carry_off = m->d_carry_off.p; ml.carry = b->d_carry.p;
@@ -2751,34 +2627,18 @@ int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_co
         const uint32_t max_pitch = ch.max_pitch;
         const dim3 grid((ch.count + 3) / 4), block(256);
         // NP follows the chunk's largest pitch: a strip of 64 x K x NP columns (K 8 for u16, 4 for u32) covers it up to 1024 columns
-#define LAUNCH_CKPT2_MULTI(KERNEL)                                                                       \
-    do {                                                                                                \
-        if (narrow) {                                                                                   \
-            if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<uint16_t, 1>), grid, block, 0, stream, ml); \
-            else hipLaunchKernelGGL((KERNEL<uint16_t, 2>), grid, block, 0, stream, ml);                  \
-        } else {                                                                                        \
-            if (max_pitch <= 256) hipLaunchKernelGGL((KERNEL<uint32_t, 1>), grid, block, 0, stream, ml); \
-            else if (max_pitch <= 512) hipLaunchKernelGGL((KERNEL<uint32_t, 2>), grid, block, 0, stream, ml); \
-            else hipLaunchKernelGGL((KERNEL<uint32_t, 4>), grid, block, 0, stream, ml);                  \
-        }                                                                                               \
-    } while (0)
-        LAUNCH_CKPT2_MULTI(poa2_ckpt_sweep_multi_kernel);
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto np) {
+            hipLaunchKernelGGL((poa2_ckpt_sweep_multi_kernel<decltype(cell), decltype(np)::value>), grid, block, 0, stream, ml);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        LAUNCH_CKPT2_MULTI(poa2_ckpt_trace_multi_kernel);
+        if (const int rc = run.mark()) return rc;
+        launch_by_pitch(narrow, max_pitch, [&](auto cell, auto np) {
+            hipLaunchKernelGGL((poa2_ckpt_trace_multi_kernel<decltype(cell), decltype(np)::value>), grid, block, 0, stream, ml);
+        });
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-#undef LAUNCH_CKPT2_MULTI
+        if (const int rc = run.mark(2)) return rc;
     }
-    hipLaunchKernelGGL(poa_scan_kernel, dim3(1), dim3(1024), 0, stream, b->d_npairs.p, b->d_pair_off.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(poa_compact_kernel, dim3((b->n_queries + 3) / 4), dim3(256), 0, stream, b->d_scratch.p,
-                       b->d_scratch_off.p, b->d_npairs.p, b->d_pair_off.p, b->d_pairs.p, b->n_queries);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end_pairs();
 }
 
 int poa_multi_fetch(poa_multi_t* m, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
@@ -2884,46 +2744,25 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
     const TuneView T(cfg);
     poa_batch* b = &s->core;
     HIP_TRY(hipSetDevice(b->device));
-    b->last_mode = POA_MODE_SCORE;
-    b->two_piece = false;
-    b->last_stream = stream;
-    if (b->runs.size() >= 256) return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": call poa_scoreset_stats/fetch at least every 256 runs");
-    // u16 cells only if every graph's own bound (run_sweep's ub, with the longest query paired with it and its shortest path) allows them
-    bool narrow = true;
+    RunFrame run;
+    if (const int rc = run.open(b, std::string(who) + ": call poa_scoreset_stats/fetch at least every 256 runs")) return rc;
+    // u16 cells only if every graph's own bound (the longest query paired with it and its shortest path) allows them
+    bool narrow = !planes32(T);
     for (size_t g = 0; g < s->ub_open.size(); ++g)
-        narrow = narrow && (uint64_t)cost_o * s->ub_open[g] + (uint64_t)cost_e * s->ub_extend[g] <= 65534;
-    if (const int* pv = T.ptr(POA_TUNE_PLANES)) { if ((*pv) == 32) narrow = false; }
+        narrow = narrow && u16_cells_suffice(cost_o, cost_e, s->ub_open[g], s->ub_extend[g]);
     bool want_px = true;
     if (const int* xv = T.ptr(POA_TUNE_PX)) want_px = (*xv) != 0;
-    b->narrow = narrow; b->compact = false; b->relative = false;
-    b->dense_narrow = narrow; b->dense_compact = false; b->dense_relative = false; b->dense_derived_gaps = false;
-    b->active_plan = 0;
     const ScoreSetPlan& pl = s->plan;
     const uint32_t variant = narrow ? (want_px ? SS_VAR_U16_PX : SS_VAR_U16) : SS_VAR_U32;
-    std::vector<hipEvent_t> events;
-    const size_t n_events = 2 + 3 * pl.chunks.size();
-    for (size_t k = 0; k < b->free_sets.size(); ++k) {
-        if (b->free_sets[k].size() == n_events) {
-            events = std::move(b->free_sets[k]);
-            b->free_sets.erase(b->free_sets.begin() + (long)k);
-            break;
-        }
-    }
-    if (events.empty()) {
-        events.resize(n_events);
-        for (auto& e : events) HIP_TRY(hipEventCreate(&e));
-    }
-    b->runs.push_back(events);
-    HIP_TRY(hipEventRecord(events[0], stream));
-    if (b->n_queries == 0) {
-        HIP_TRY(hipEventRecord(events[1], stream));
-        b->ran = true;
-        return POA_OK;
-    }
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
+    b->last_mode = POA_MODE_SCORE;
+    b->two_piece = false;
+    set_layout(b, narrow);
+    b->active_plan = 0;
+    if (b->n_queries == 0) return run.end_empty(false);
     // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
     b->sweep_bytes_written = variant == SS_VAR_U16_PX ? 2ull * (pl.slotted_px * 2048ull + pl.slotted_pitch * 2ull)
                                                       : 2ull * pl.slotted_pitch_all * (narrow ? 2ull : 4ull);
-    size_t ev = 1;
     for (const auto& ch : pl.chunks) {
         ScoreSetLaunch sl;
         sl.graphs = s->d_params.p; sl.pair_graph = s->d_pair_graph.p; sl.pair_query = s->d_pair_query.p;
@@ -2946,13 +2785,9 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
             }
             HIP_TRY(hipGetLastError());
         }
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
-        HIP_TRY(hipEventRecord(events[ev++], stream));
+        if (const int rc = run.mark(3)) return rc;
     }
-    HIP_TRY(hipEventRecord(events[ev], stream));
-    b->ran = true;
-    return POA_OK;
+    return run.end();
 }
 }  // namespace
 
