@@ -392,6 +392,24 @@ int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout);
  * smallest band distance D among the queries it ran on (a query is certified when its score is <= e * (D - 4)).
  * Synchronises with the run's stream. */
 int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]);
+/* what the dense one-piece pass launched for chunk `chunk` of the last run (tests: did the kernel an override names really run?):
+ *   out[0] forward kernel, POA_KERNEL_*      out[1] column groups per lane ("quads": 512 u16 / 256 u32 columns each)
+ *   out[2] POA_LAUNCH_* bits                 out[3] waves per workgroup
+ *   out[4] TbParams::code_fmt of the cells   out[5] lanes per walk of the separate traceback launch (0: none, the walk was fused)
+ *   out[6] traceback speculation depth       out[7] queries in the chunk
+ * The cell type and layout are the run's (poa_batch_last_layout).  POA_ERR_INVALID_ARG: no run yet, or no such chunk;
+ * POA_ERR_UNSUPPORTED: the last run was not a dense one-piece run (another mode, or the two-piece model).  Host side only. */
+enum {
+    POA_KERNEL_NONE = 0,
+    POA_KERNEL_FORWARD,   /* poa_forward_kernel<quads, u16 | u32, fuse, compact, MW> */
+    POA_KERNEL_PACKED,    /* poa_forward_packed_kernel<quads, fuse, MW> */
+    POA_KERNEL_PX,        /* poa_forward_px_kernel<0..3> (code_fmt 1..4) */
+    POA_KERNEL_PXMW,      /* poa_forward_pxmw_kernel */
+    POA_KERNEL_BAND       /* poa_forward_band_kernel<false>, then <true> over the queries it could not certify */
+};
+#define POA_LAUNCH_FUSE 1u   /* the forward kernel walked the traceback of its queries in its epilogue */
+#define POA_LAUNCH_MW 2u     /* one workgroup per query, its strips pipelined over the waves */
+int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);

@@ -175,6 +175,9 @@ def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, que
     return cfg
 
 
+LAUNCH_KERNELS = ("none", "forward", "packed", "px", "pxmw", "band")   # POA_KERNEL_* of include/poasta_amd.h
+
+
 class AlignedPair:
     __slots__ = ("rpos", "qpos")
 
@@ -390,6 +393,20 @@ class ResidentBatch:
         out = (C.c_uint32 * 4)()
         _lib.check(_lib.lib().poa_batch_band_info(self.handle, out))
         return {"used": bool(out[0]), "banded": int(out[1]), "fell_back": int(out[2]), "min_d": int(out[3])}
+
+    def launches(self):
+        """What the dense one-piece pass of the last run launched, one dict per chunk (poa_batch_last_launch): "kernel" in
+        {"forward", "packed", "px", "pxmw", "band"}, "quads", "fuse", "mw", "waves", "code_fmt", "tb_lanes" (0: no separate
+        traceback launch), "tb_depth", "queries"."""
+        out = []
+        while True:
+            v = (C.c_uint32 * 8)()
+            rc = _lib.lib().poa_batch_last_launch(self.handle, len(out), v)
+            if rc == -1 and (out or self.n == 0):   # past the last chunk (a batch without queries launches nothing)
+                return out
+            _lib.check(rc)
+            out.append({"kernel": LAUNCH_KERNELS[v[0]], "quads": int(v[1]), "fuse": bool(v[2] & 1), "mw": bool(v[2] & 2),
+                        "waves": int(v[3]), "code_fmt": int(v[4]), "tb_lanes": int(v[5]), "tb_depth": int(v[6]), "queries": int(v[7])})
 
     def device_results(self):
         ptrs = [C.c_void_p() for _ in range(4)]

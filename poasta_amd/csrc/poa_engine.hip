@@ -272,6 +272,9 @@ struct poa_batch {
     // the last run (poa_batch_band_info)
     bool band_used = false;
     uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
+    // what the dense one-piece path launched per chunk of the last run (poa_batch_last_launch); empty after any other run
+    struct Launch { uint32_t v[8]; };
+    std::vector<Launch> launches;
 
     // one event set per run since the last stats call, written by RunFrame and read by collect_stats
     std::vector<std::vector<hipEvent_t>> runs;
@@ -1092,6 +1095,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     b->last_mode = mode;
     b->two_piece = false;
     set_layout(b, narrow, compact, relative);
+    b->launches.clear();
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
@@ -1148,7 +1152,11 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     do {                                                                                                               \
         if (fuse_tb) hipLaunchKernelGGL((poa_forward_kernel<QQ, TT, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);  \
         else hipLaunchKernelGGL((poa_forward_kernel<QQ, TT, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);         \
+        lk = POA_KERNEL_FORWARD; lq = QQ; lfuse = fuse_tb;                                                              \
     } while (0)
+        // the launch record of this chunk (poa_batch_last_launch): kernel family, quads, fused walk, multi-wave, waves per workgroup
+        uint32_t lk = POA_KERNEL_NONE, lq = 0, lwaves = 4;
+        bool lfuse = false, lmw = false;
         uint32_t max_pitch = 0;
         for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) max_pitch = std::max(max_pitch, b->h_pitch[i]);
         // strip width: as narrow as the widest plane row of the chunk allows, at most 1024 columns
@@ -1189,15 +1197,19 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                         for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) min_d = std::min(min_d, std::min(b->h_band_d[b->h_band_cls[i]], band_cap));
                         b->band_min_d = b->band_used ? std::min(b->band_min_d, min_d) : min_d;
                         b->band_used = true; b->band_queries += ch.count; b->band_chunks = (uint32_t)ci + 1;
+                        lk = POA_KERNEL_BAND;
                     } else if (mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, dim3(blocks), dim3(256), 0, stream, fp);
                     else if (mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, dim3(blocks), dim3(256), 0, stream, fp);
                     else if (mf == 1) hipLaunchKernelGGL(poa_forward_px_kernel<1>, dim3(blocks), dim3(256), 0, stream, fp);
                     else hipLaunchKernelGGL(poa_forward_px_kernel<0>, dim3(blocks), dim3(256), 0, stream, fp);
+                    if (lk == POA_KERNEL_NONE) lk = POA_KERNEL_PX;
+                    lq = 2;
                 } else if (mw && (relative || pxmw_ok(T, ch.count, max_pitch))) {
                     // pairs-across-quads mapping, 1024-column strips pipelined over the waves of a workgroup
                     tp.code_fmt = 1;
                     const uint32_t waves = mw_waves((max_pitch + 1023) / 1024);
                     hipLaunchKernelGGL(poa_forward_pxmw_kernel, dim3(ch.count), dim3(64 * waves), 0, stream, fp);
+                    lk = POA_KERNEL_PXMW; lq = 2; lmw = true; lwaves = waves;
                 } else if (mw) {
                     // narrow strips (more waves) until the chunk alone fills the chip
                     if (!quads_override) quads = ((uint64_t)ch.count * ((max_pitch + 1023) / 1024) >= 8192) ? 2 : 1;
@@ -1205,16 +1217,20 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                     const uint32_t waves = mw_waves(strips);
                     if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
                     else hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
+                    lk = POA_KERNEL_PACKED; lq = quads; lmw = true; lwaves = waves;
                 } else if (quads == 1) {
                     if (fuse_tb) hipLaunchKernelGGL((poa_forward_packed_kernel<1, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
                     else hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
+                    lk = POA_KERNEL_PACKED; lq = 1; lfuse = fuse_tb;
                 } else {
                     if (fuse_tb) hipLaunchKernelGGL((poa_forward_packed_kernel<2, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
                     else hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
+                    lk = POA_KERNEL_PACKED; lq = 2; lfuse = fuse_tb;
                 }
             } else if (compact) {
                 if (quads == 1) hipLaunchKernelGGL((poa_forward_kernel<1, uint16_t, false, true>), dim3(blocks), dim3(256), 0, stream, fp, tp);
                 else hipLaunchKernelGGL((poa_forward_kernel<2, uint16_t, false, true>), dim3(blocks), dim3(256), 0, stream, fp, tp);
+                lk = POA_KERNEL_FORWARD; lq = quads;
             } else if (quads == 1) LAUNCH_FWD(1, uint16_t);
             else LAUNCH_FWD(2, uint16_t);
         } else {
@@ -1235,9 +1251,11 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                 if (wide) {
                     const uint32_t waves = (s4 + g4 - 1) / g4;
                     hipLaunchKernelGGL((poa_forward_kernel<4, uint32_t, false, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
+                    lk = POA_KERNEL_FORWARD; lq = 4; lmw = true; lwaves = waves;
                 } else {
                     const uint32_t waves = (s2 + g2 - 1) / g2;
                     hipLaunchKernelGGL((poa_forward_kernel<2, uint32_t, false, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
+                    lk = POA_KERNEL_FORWARD; lq = 2; lmw = true; lwaves = waves;
                 }
             } else if (quads == 1) LAUNCH_FWD(1, uint32_t);
             else if (quads == 2) LAUNCH_FWD(2, uint32_t);
@@ -1246,6 +1264,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
 
+        uint32_t ltb = 0, ldepth = tp.spec_depth;   // lanes per walk of the separate traceback launch (0: none), speculation depth
         if (!(fuse_tb && !relative && max_pitch <= 1024 && (!compact || packed))) {
             // Lanes per walk: as many as keep the launch within ~6 000 waves (what the chip holds at this kernel's occupancy
             // with room to spare), and a speculation depth to match.  Measured on config 2 after the insertion-run speculation
@@ -1266,7 +1285,11 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
             else if (narrow) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
             else hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
             HIP_TRY(hipGetLastError());
+            ltb = compact ? (uint32_t)tbg : 64u;
+            ldepth = compact ? tpg.spec_depth : tp.spec_depth;
         }
+        if (mode == POA_MODE_DENSE)
+            b->launches.push_back({{lk, lq, (lfuse ? POA_LAUNCH_FUSE : 0u) | (lmw ? POA_LAUNCH_MW : 0u), lwaves, tp.code_fmt, ltb, ldepth, ch.count}});
         if (const int rc = run.mark()) return rc;
 
         if (mode != POA_MODE_DENSE) {
@@ -1614,6 +1637,16 @@ int poa_batch_last_layout(poa_batch_t* b, uint32_t* layout) {
     if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_layout: poa_batch_run has not been called");
     *layout = (b->dense_narrow ? POA_LAYOUT_U16 : 0u) | (b->dense_compact ? POA_LAYOUT_COMPACT : 0u) | (b->dense_relative ? POA_LAYOUT_RELATIVE : 0u) |
               (b->dense_derived_gaps ? POA_LAYOUT_DERIVED_GAPS : 0u);
+    return POA_OK;
+}
+
+int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_launch: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_launch: poa_batch_run has not been called");
+    if (b->two_piece || b->sweep || b->ckpt || b->last_mode != POA_MODE_DENSE)
+        return fail(POA_ERR_UNSUPPORTED, "poa_batch_last_launch: the last run was not a dense one-piece run");
+    if (chunk >= b->launches.size()) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_launch: the last run had no such chunk");
+    for (int k = 0; k < 8; ++k) out[k] = b->launches[chunk].v[k];
     return POA_OK;
 }
 
