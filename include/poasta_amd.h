@@ -154,6 +154,7 @@ enum {
     POA_TUNE_CKPT_ROWS,       /* checkpointed mode: rows per segment (read when the batch is created; 0 / unset: the engine's choice) */
     POA_TUNE_BAND,            /* 0: the one-strip dense kernel computes every cell instead of an exact band (poa_batch_band_info) */
     POA_TUNE_BAND_DELTA,      /* banded kernel: cap of the band distance D (tests: a small cap sends every query to the full kernel) */
+    POA_TUNE_BAND_PAIR,       /* banded kernel, two queries of one length per wave: 0 never, 1 whatever the chunk's count (default: from a count on, poa_batch_band_pair_info) */
     POA_TUNE_COUNT = 32
 };
 
@@ -405,11 +406,16 @@ enum {
     POA_KERNEL_PACKED,    /* poa_forward_packed_kernel<quads, fuse, MW> */
     POA_KERNEL_PX,        /* poa_forward_px_kernel<0..3> (code_fmt 1..4) */
     POA_KERNEL_PXMW,      /* poa_forward_pxmw_kernel */
-    POA_KERNEL_BAND       /* poa_forward_band_kernel<false>, then <true> over the queries it could not certify */
+    POA_KERNEL_BAND       /* poa_forward_band_kernel<false> (and / or poa_forward_band2_kernel: poa_batch_band_pair_info), then <true> over the queries it could not certify */
 };
 #define POA_LAUNCH_FUSE 1u   /* the forward kernel walked the traceback of its queries in its epilogue */
 #define POA_LAUNCH_MW 2u     /* one workgroup per query, its strips pipelined over the waves */
 int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
+/* the paired banded pass of the last dense run (two queries of one length per wave, one per 16-bit half of every register):
+ * out[0] = queries that ran paired, out[1] = queries of banded chunks that ran one per wave, out[2] = the default rule's
+ * count (a chunk pairs from that many queries in pairs on; POA_TUNE_BAND_PAIR overrides), out[3] = 1 if the run paired.
+ * poa_batch_band_info and poa_batch_last_launch say the same for both ways.  Host side only. */
+int poa_batch_band_pair_info(poa_batch_t* b, uint32_t out[4]);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);

@@ -21,7 +21,7 @@ FLAG_AMBIGUOUS, FLAG_START_QUIRK, FLAG_REF_PANIC, FLAG_SHORT_QUERY, FLAG_TRUNCAT
 EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_create", "poa_graph_destroy",
            "poa_graph_rows", "poa_graph_node_rows", "poa_graph_update", "poa_align_batch", "poa_align_batch_ex", "poa_align_batch_2piece", "poa_align_batch_2piece_ex", "poa_planes_2piece", "poa_release_cache", "poa_batch_create", "poa_batch_run",
            "poa_batch_run_ex",
-           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_last_launch", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
+           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_band_pair_info", "poa_batch_last_launch", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
            "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
            "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
@@ -55,7 +55,7 @@ class PoaConfig(C.Structure):
 # sweep set POA_<NAME> and this binding copies them into the config of every call (tune_from_env).
 TUNE_KEYS = ("PLANES", "COMPACT", "PACKED", "RELATIVE", "PX", "MF", "MW", "PXMW", "FWD_QUADS", "FUSE_TB", "TB_GROUP", "TB_DEPTH",
              "EXACT_IMPL", "EXACT_LANES", "EXACT_LDS", "WS_LANES", "WS_GROUP", "WS_WAVES", "WS_RING_GLOBAL", "WS_STATIC",
-             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC", "CKPT_ROWS", "BAND", "BAND_DELTA")
+             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC", "CKPT_ROWS", "BAND", "BAND_DELTA", "BAND_PAIR")
 EXACT_IMPLS = {"lane": 1, "wave": 2, "flat": 3}
 
 
@@ -176,6 +176,9 @@ def lib():
     if hasattr(L, "poa_batch_band_info"):   # (POA_LIB_PATH may name the build of an older tree: A/B runs)
         L.poa_batch_band_info.restype = C.c_int
         L.poa_batch_band_info.argtypes = [vp, vp]
+    if hasattr(L, "poa_batch_band_pair_info"):
+        L.poa_batch_band_pair_info.restype = C.c_int
+        L.poa_batch_band_pair_info.argtypes = [vp, vp]
     if hasattr(L, "poa_batch_last_launch"):
         L.poa_batch_last_launch.restype = C.c_int
         L.poa_batch_last_launch.argtypes = [vp, C.c_uint32, vp]

@@ -394,6 +394,12 @@ class ResidentBatch:
         _lib.check(_lib.lib().poa_batch_band_info(self.handle, out))
         return {"used": bool(out[0]), "banded": int(out[1]), "fell_back": int(out[2]), "min_d": int(out[3])}
 
+    def band_pair_info(self):
+        """The paired banded pass of the last dense run: {"paired", "single", "rule_count", "ran_paired"} (poa_batch_band_pair_info)."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.lib().poa_batch_band_pair_info(self.handle, out))
+        return {"paired": int(out[0]), "single": int(out[1]), "rule_count": int(out[2]), "ran_paired": bool(out[3])}
+
     def launches(self):
         """What the dense one-piece pass of the last run launched, one dict per chunk (poa_batch_last_launch): "kernel" in
         {"forward", "packed", "px", "pxmw", "band"}, "quads", "fuse", "mw", "waves", "code_fmt", "tb_lanes" (0: no separate

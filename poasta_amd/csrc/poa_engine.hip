@@ -269,6 +269,12 @@ struct poa_batch {
     std::vector<uint32_t> h_band_cls, h_band_d;          // per query: class; per class: band distance D
     DevBuf<uint32_t> d_band_cls, d_band_d, d_band_base;  // the same on the device, and the window bases [class][segment]
     DevBuf<uint32_t> d_band_list, d_band_count;          // queries the full kernel redoes: [n_queries], and their number per chunk
+    // paired banded pass (poa_forward_band2_kernel): per chunk of plan[band_pair_plan] the queries in launch order - the pairs
+    // (A, B, A, B, ...), then the singles - built from the lengths alone at the first run that may pair and kept
+    int band_pair_plan = -1;
+    std::vector<uint32_t> h_band_npair;                  // per chunk: its pairs
+    DevBuf<uint32_t> d_band_order;                       // [n_queries], a chunk's part at its first query
+    uint32_t pair_paired = 0, pair_single = 0;           // the last run (poa_batch_band_pair_info)
     // the last run (poa_batch_band_info)
     bool band_used = false;
     uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
@@ -491,6 +497,39 @@ static int prepare_band(poa_batch* b) {
     HIP_TRY(hipMemcpy(b->d_band_d.p, b->h_band_d.data(), b->h_band_d.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_band_base.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice));
     b->band_ready = true;
+    return POA_OK;
+}
+
+// who pairs (poa_forward_band2_kernel): within a chunk, in query order, every second query of a band class with D >= 4 joins
+// the class's waiting one; what is left over - odd members, classes of one, classes without a band - runs as singles.
+// Depends on the lengths and the chunk plan alone: uploaded once per chunk plan.
+static int prepare_band_pairs(poa_batch* b) {
+    if (b->band_pair_plan == b->active_plan) return POA_OK;
+    const poa_batch::Plan& PL = b->cur();
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    std::vector<uint32_t> order(b->n_queries), waiting(b->h_band_d.size(), NONE), singles;
+    b->h_band_npair.assign(PL.chunks.size(), 0);
+    for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
+        const auto& ch = PL.chunks[ci];
+        uint32_t at = ch.first;
+        singles.clear();
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) {
+            const uint32_t cl = b->h_band_cls[i];
+            if (b->h_band_d[cl] < 4) singles.push_back(i);
+            else if (waiting[cl] == NONE) waiting[cl] = i;
+            else { order[at++] = waiting[cl]; order[at++] = i; waiting[cl] = NONE; }
+        }
+        b->h_band_npair[ci] = (at - ch.first) / 2;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) {
+            uint32_t& w = waiting[b->h_band_cls[i]];
+            if (w == i) { singles.push_back(i); w = NONE; }
+        }
+        std::sort(singles.begin(), singles.end());
+        for (uint32_t i : singles) order[at++] = i;
+    }
+    if (b->d_band_order.n < b->n_queries) HIP_TRY(b->d_band_order.alloc(b->n_queries));
+    HIP_TRY(hipMemcpy(b->d_band_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+    b->band_pair_plan = b->active_plan;
     return POA_OK;
 }
 
@@ -1097,6 +1136,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     set_layout(b, narrow, compact, relative);
     b->launches.clear();
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
+    b->pair_paired = 0; b->pair_single = 0;
     b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
     if (b->n_queries == 0) return run.end_empty(true);
@@ -1114,6 +1154,9 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     if (const int* bv = T.ptr(POA_TUNE_BAND)) want_band = want_band && (*bv) != 0;
     uint32_t band_cap = 0xFFFFFFFFu;
     if (const int* dv = T.ptr(POA_TUNE_BAND_DELTA)) band_cap = (*dv) > 0 ? (uint32_t)(*dv) : 0u;
+    // two queries of one length per wave (poa_forward_band2_kernel): POA_BAND_PAIR=0 never, 1 whatever the count, else the rule
+    int band_pair = -1;
+    if (const int* pv = T.ptr(POA_TUNE_BAND_PAIR)) band_pair = (*pv) != 0 ? 1 : 0;
     if (want_band && !PL.chunks.empty()) {   // one fallback counter per chunk, cleared per run
         if (b->d_band_count.n < PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(PL.chunks.size()));
         HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, PL.chunks.size() * 4, stream));
@@ -1190,7 +1233,31 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
                         BandParams bp;
                         bp.cls = b->d_band_cls.p; bp.cls_d = b->d_band_d.p; bp.cls_base = b->d_band_base.p; bp.n_seg = b->band_n_seg;
                         bp.d_cap = band_cap; bp.list = b->d_band_list.p; bp.count = b->d_band_count.p + ci;
-                        hipLaunchKernelGGL(poa_forward_band_kernel<false>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+                        bp.order = nullptr;
+                        uint32_t n_pairs = 0;
+                        if (band_pair != 0) {
+                            rc = prepare_band_pairs(b);
+                            if (rc != POA_OK) return rc;
+                            n_pairs = b->h_band_npair[ci];
+                            if (band_pair < 0 && !band_pair_rule(2 * n_pairs)) n_pairs = 0;
+                        }
+                        if (n_pairs) {
+                            // the pairs, then the singles one per wave: grids sized on the host, nothing read back
+                            const uint32_t n_single = ch.count - 2 * n_pairs;
+                            FwdParams fq = fp;
+                            BandParams bq = bp;
+                            fq.n_queries = n_pairs; bq.order = b->d_band_order.p + ch.first;
+                            hipLaunchKernelGGL(poa_forward_band2_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, stream, fq, bq);
+                            if (n_single) {
+                                HIP_TRY(hipGetLastError());
+                                fq.n_queries = n_single; bq.order = b->d_band_order.p + ch.first + 2 * n_pairs;
+                                hipLaunchKernelGGL((poa_forward_band_kernel<false, true>), dim3((n_single + 3) / 4), dim3(256), 0, stream, fq, bq);
+                            }
+                            b->pair_paired += 2 * n_pairs; b->pair_single += n_single;
+                        } else {
+                            hipLaunchKernelGGL(poa_forward_band_kernel<false>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+                            b->pair_single += ch.count;
+                        }
                         HIP_TRY(hipGetLastError());
                         hipLaunchKernelGGL(poa_forward_band_kernel<true>, dim3(blocks), dim3(256), 0, stream, fp, bp);
                         uint32_t min_d = 0xFFFFFFFFu;
@@ -1662,6 +1729,13 @@ int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]) {
     uint32_t fell = 0;
     for (uint32_t c : counts) fell += c;
     out[2] = fell; out[1] = b->band_queries - std::min(fell, b->band_queries);
+    return POA_OK;
+}
+
+int poa_batch_band_pair_info(poa_batch_t* b, uint32_t out[4]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_pair_info: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_pair_info: poa_batch_run has not been called");
+    out[0] = b->pair_paired; out[1] = b->pair_single; out[2] = BAND_PAIR_MIN_QUERIES; out[3] = b->pair_paired ? 1u : 0u;
     return POA_OK;
 }
 

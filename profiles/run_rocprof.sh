@@ -27,7 +27,9 @@ json.dump(out, open("$OUT/pmc_summary.json", "w"), indent=1, sort_keys=True)
 for f in glob.glob("$OUT/trace/*/*kernel_stats.csv"):
     open("$OUT/kernel_stats.csv", "w").write(open(f).read())
 # the headline's forward kernel: the banded one where it ran, else the full one-strip kernel
-kname, k = next(((n, v) for n, v in out.items() if "poa_forward_band_kernel" in n), (None, None))
+kname, k = next(((n, v) for n, v in out.items() if "poa_forward_band2_kernel" in n), (None, None))
+if not k:
+    kname, k = next(((n, v) for n, v in out.items() if "poa_forward_band_kernel<false" in n), (None, None))
 if not k:
     kname, k = next(((n, v) for n, v in out.items() if "poa_forward_px_kernel" in n), (None, None))
 if k and "WRITE_SIZE" in k and "FETCH_SIZE" in k:
