@@ -48,6 +48,7 @@ extern "C" {
 #define POA_FLAG_TRUNCATED 0x10u    /* backtrace ended before the start node (as the reference's would) */
 #define POA_FLAG_EMPTY_GRAPH 0x20u  /* no real nodes: PoastaAligner::align shortcut (mod.rs:124-142), score 4*len */
 #define POA_FLAG_EXACT_OVERFLOW 0x40u /* exact replay ran out of workspace: the dense result (and its flags) was kept */
+#define POA_FLAG_CAPPED 0x80u       /* capped score-set run: the score is above the pair's cap and was not returned */
 
 /* modes (poa_config_t.mode) */
 #define POA_MODE_DENSE 0u   /* dense planes + traceback: scores exact, alignment certified-or-flagged */
@@ -155,6 +156,7 @@ enum {
     POA_TUNE_BAND,            /* 0: the one-strip dense kernel computes every cell instead of an exact band (poa_batch_band_info) */
     POA_TUNE_BAND_DELTA,      /* banded kernel: cap of the band distance D (tests: a small cap sends every query to the full kernel) */
     POA_TUNE_BAND_PAIR,       /* banded kernel, two queries of one length per wave: 0 never, 1 whatever the chunk's count (default: from a count on, poa_batch_band_pair_info) */
+    POA_TUNE_CAP_STRIDE,      /* capped score-set run: least distance in rows between two check rows (default: poa_graph_sweep_checks) */
     POA_TUNE_COUNT = 32
 };
 
@@ -239,6 +241,13 @@ uint32_t poa_graph_rows(const poa_graph_t* g);           /* == n */
  * A row has a slot iff some successor is not the chain row directly below it; it is live from its own row to its last
  * reader.  Host-side table, recomputed by poa_graph_update; needs no device. */
 int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot /* may be NULL */, uint32_t* n_slots);
+/* check rows of a capped score-set run (poa_scoreset_run_capped): check[n] by ROW, 1 where a wave compares the row's smallest M
+ * value with its cap; *n_checks = how many.  Row r is a CUT row if no edge (u, v) has row(u) < r < row(v): every start-to-end
+ * path passes through it, and once it has run no earlier row is live in the sweep.  Row 0 and the end row are cut rows.  The
+ * check rows are the cut rows without the end row (the result is written there anyway), thinned greedily in row order so that
+ * two consecutive check rows are at least `stride` rows apart; stride 0: the engine's default, 8.  Host-side table, recomputed
+ * by poa_graph_update; needs no device. */
+int poa_graph_sweep_checks(const poa_graph_t* g, uint32_t stride, uint8_t* check /* [rows], may be NULL */, uint32_t* n_checks);
 /* segment plan of the checkpointed mode (POA_MODE_CHECKPOINT): the rows are cut into *n_segments segments of segment_rows rows
  * (0: the engine's choice — the length that holds the fewest rows; a graph of a few rows is one segment), boundary[0] = 0 <
  * ... < boundary[*n_segments] = rows.  The snapshot of a boundary b > 0 holds every row < b that has a sweep slot and a reader
@@ -563,6 +572,8 @@ int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int
                         const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out);
 int poa_scoreset_run(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);
 int poa_scoreset_run_2piece(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream);
+/* Capped runs — a score cap per pair and an exact early exit in the sweep (poa_scoreset_run_capped, poa_scoreset_run_2piece_capped,
+ * poa_scoreset_fetch_swept) — are declared in poasta_amd_scoreset_cap.h, which this header includes at its end. */
 /* synchronises; score[n_pairs], flags[n_pairs] (may be NULL) in pair order */
 int poa_scoreset_fetch(poa_scoreset_t* s, uint32_t* score, uint32_t* flags, poa_stats_t* stats);
 int poa_scoreset_stats(poa_scoreset_t* s, poa_stats_t* stats);
@@ -582,4 +593,5 @@ int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 #ifdef __cplusplus
 }
 #endif
+#include "poasta_amd_scoreset_cap.h"
 #endif /* POASTA_AMD_H */

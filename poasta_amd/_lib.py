@@ -16,6 +16,7 @@ ERRORS = {-1: "POA_ERR_INVALID_ARG", -2: "POA_ERR_NOT_A_DAG", -3: "POA_ERR_NO_DE
           -5: "POA_ERR_CAPACITY", -6: "POA_ERR_OUT_OF_MEMORY", -7: "POA_ERR_UNSUPPORTED"}
 POA_NONE = 0xFFFFFFFF
 FLAG_AMBIGUOUS, FLAG_START_QUIRK, FLAG_REF_PANIC, FLAG_SHORT_QUERY, FLAG_TRUNCATED, FLAG_EMPTY_GRAPH = 1, 2, 4, 8, 16, 32
+FLAG_CAPPED = 0x80
 
 # every symbol include/poasta_amd.h declares (checked by tests/test_abi.py)
 EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_create", "poa_graph_destroy",
@@ -29,7 +30,10 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_multi_footprint_2piece", "poa_multi_create_2piece", "poa_multi_run_2piece", "poa_align_multi_2piece",
            "poa_scoreset_footprint", "poa_scoreset_create", "poa_scoreset_run", "poa_scoreset_run_2piece", "poa_scoreset_fetch",
            "poa_scoreset_stats", "poa_scoreset_device_results", "poa_scoreset_workspace_bytes", "poa_scoreset_destroy",
-           "poa_score_pairs", "poa_score_pairs_2piece"]
+           "poa_score_pairs", "poa_score_pairs_2piece",
+           "poa_graph_sweep_checks"]
+# every symbol include/poasta_amd_scoreset_cap.h declares (checked by tests/test_sweep_checks.py)
+EXPORTS_SCORESET_CAP = ["poa_scoreset_run_capped", "poa_scoreset_run_2piece_capped", "poa_scoreset_fetch_swept"]
 
 
 class PoaCosts2(C.Structure):
@@ -55,7 +59,7 @@ class PoaConfig(C.Structure):
 # sweep set POA_<NAME> and this binding copies them into the config of every call (tune_from_env).
 TUNE_KEYS = ("PLANES", "COMPACT", "PACKED", "RELATIVE", "PX", "MF", "MW", "PXMW", "FWD_QUADS", "FUSE_TB", "TB_GROUP", "TB_DEPTH",
              "EXACT_IMPL", "EXACT_LANES", "EXACT_LDS", "WS_LANES", "WS_GROUP", "WS_WAVES", "WS_RING_GLOBAL", "WS_STATIC",
-             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC", "CKPT_ROWS", "BAND", "BAND_DELTA", "BAND_PAIR")
+             "WS_CHUNK_CAP", "WS_PROF", "PS_LANES", "PS_LEAN", "TIMING", "WS_ADAPT", "WS_REC", "CKPT_ROWS", "BAND", "BAND_DELTA", "BAND_PAIR", "CAP_STRIDE")
 EXACT_IMPLS = {"lane": 1, "wave": 2, "flat": 3}
 
 
@@ -105,7 +109,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", "poasta_amd.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -155,6 +159,15 @@ def lib():
     L.poa_batch_create.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint64, C.POINTER(vp)]
     L.poa_graph_sweep_slots.restype = C.c_int
     L.poa_graph_sweep_slots.argtypes = [vp, vp, vp]
+    if hasattr(L, "poa_graph_sweep_checks"):   # (POA_LIB_PATH may name the build of an older tree: A/B runs)
+        L.poa_graph_sweep_checks.restype = C.c_int
+        L.poa_graph_sweep_checks.argtypes = [vp, C.c_uint32, vp, vp]
+        L.poa_scoreset_run_capped.restype = C.c_int
+        L.poa_scoreset_run_capped.argtypes = [vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), vp, vp]
+        L.poa_scoreset_run_2piece_capped.restype = C.c_int
+        L.poa_scoreset_run_2piece_capped.argtypes = [vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp, vp]
+        L.poa_scoreset_fetch_swept.restype = C.c_int
+        L.poa_scoreset_fetch_swept.argtypes = [vp, vp]
     L.poa_graph_checkpoint_plan.restype = C.c_int
     L.poa_graph_checkpoint_plan.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.poa_graph_checkpoint_plan2.restype = C.c_int

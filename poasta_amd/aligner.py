@@ -258,6 +258,15 @@ class DeviceGraph:
         _lib.check(_lib.lib().poa_graph_sweep_slots(self.handle, _p(slot), C.byref(n)))
         return slot[:self.graph.n], int(n.value)
 
+    def sweep_checks(self, stride=0):
+        """check[row] of a capped score-set run (poa_graph_sweep_checks): 1 where a wave compares the row's smallest M value with
+        its cap — the cut rows (no edge skips them) without the end row, at least `stride` rows apart (0: the engine's default)."""
+        check = np.zeros(max(self.graph.n, 1), np.uint8)
+        n = C.c_uint32(0)
+        _lib.check(_lib.lib().poa_graph_sweep_checks(self.handle, int(stride), _p(check), C.byref(n)))
+        assert int(check[:self.graph.n].sum()) == n.value
+        return check[:self.graph.n]
+
     def checkpoint_plan(self, segment_rows=0, two_piece=False):
         """(boundary, rows_per_query) of the checkpointed mode: boundary[0] = 0 < ... < boundary[-1] = rows cut the rows into
         segments of segment_rows rows (0: the engine's choice); rows_per_query = plane rows of `pitch` cells a query holds.
@@ -276,6 +285,11 @@ class DeviceGraph:
                 self.handle = None
         except Exception:
             pass
+
+
+def sweep_checks(graph, stride=0):
+    """The check rows of `graph` in a capped score-set run, a u8 array by row (DeviceGraph.sweep_checks)."""
+    return _device_graph(graph).sweep_checks(stride)
 
 
 def _device_graph(graph):
@@ -614,14 +628,33 @@ class ScoreSet:
                                                   C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
 
-    def run(self, costs, stream=None, config=None):
+    def run(self, costs, stream=None, config=None, cap=None):
         """Launch on `stream` without synchronising.  costs: GapAffine (poa_scoreset_run) or GapAffine2Piece
-        (poa_scoreset_run_2piece); config: None or make_config("score", ...)."""
+        (poa_scoreset_run_2piece); config: None or make_config("score", ...).
+        cap: None, or a score cap — a scalar, or one value per pair in pair order; POA_NONE: no cap for that pair — for
+        poa_scoreset_run_capped / _run_2piece_capped: a pair whose score is above its cap comes back as POA_NONE with
+        FLAG_CAPPED set, and its wave stops as soon as a row proves it."""
         c = costs._c()
         if config is None:
             config = make_config("score")   # (carries the POA_<NAME> overrides, if any are set)
-        fn = _lib.lib().poa_scoreset_run_2piece if isinstance(costs, GapAffine2Piece) else _lib.lib().poa_scoreset_run
-        _lib.check(fn(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+        two_piece = isinstance(costs, GapAffine2Piece)
+        if cap is None:
+            fn = _lib.lib().poa_scoreset_run_2piece if two_piece else _lib.lib().poa_scoreset_run
+            _lib.check(fn(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+            return
+        caps = np.full(self.n, cap, np.uint32) if np.ndim(cap) == 0 else np.ascontiguousarray(cap, np.uint32)
+        if caps.shape != (self.n,):
+            raise ValueError("cap: a scalar or one value per pair (%d), got shape %s" % (self.n, caps.shape))
+        if self.n == 0:
+            caps = np.zeros(1, np.uint32)   # (a non-null pointer)
+        fn = _lib.lib().poa_scoreset_run_2piece_capped if two_piece else _lib.lib().poa_scoreset_run_capped
+        _lib.check(fn(self.handle, C.byref(c), C.byref(config), _p(caps), C.c_void_p(stream or 0)))
+
+    def swept_rows(self):
+        """Synchronise; the row bodies each pair's wave executed in the last run (poa_scoreset_fetch_swept), in pair order."""
+        swept = np.zeros(max(self.n, 1), np.uint32)
+        _lib.check(_lib.lib().poa_scoreset_fetch_swept(self.handle, _p(swept)))
+        return swept[:self.n]
 
     def fetch(self):
         """Synchronise; (score, flags, stats): u32 arrays in pair order and the poa_stats_t of the runs since the last call."""
@@ -775,12 +808,23 @@ class PoastaAligner:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())
 
-    def score_pairs(self, graphs, seqs, pairs):
+    def score_pairs(self, graphs, seqs, pairs, max_score=None):
         """Scores of (query, graph) pairs over many graphs in one score-only run (poa_score_pairs): pairs is an [n, 2] array of
         (index into seqs, index into graphs), None for the full matrix.  Returns (score, flags) in pair order: what score_batch
-        gives for that query against that graph alone."""
+        gives for that query against that graph alone.
+        max_score: None, or a cap — a scalar or one value per pair: a pair that scores above it comes back as POA_NONE with
+        FLAG_CAPPED set, without its sweep being finished (a ScoreSet run with cap=max_score)."""
         if self.aln_type != AlignmentType.Global:
             raise ValueError("score_pairs: AlignmentType.Global only")
+        if max_score is not None:
+            ss = ScoreSet(graphs, seqs, pairs=pairs, device=self.device)
+            try:
+                ss.run(self.config.costs, config=make_config("score", self.config.heuristic), cap=max_score)
+                score, flags, st = ss.fetch()
+            finally:
+                ss.close()
+            self.last_stats = st
+            return score, flags
         si = _ScoreSetInput(graphs, seqs, pairs=pairs)
         score, flags = np.zeros(si.n, np.uint32), np.zeros(si.n, np.uint32)
         st = _lib.PoaStats()
@@ -792,7 +836,13 @@ class PoastaAligner:
         self.last_stats = st.as_dict()
         return score, flags
 
-    def score_matrix(self, graphs, seqs):
-        """The full queries x graphs matrix of scores, a [n_queries, n_graphs] u32 array (score_pairs with pairs=None)."""
-        score, _ = self.score_pairs(graphs, seqs, None)
+    def score_matrix(self, graphs, seqs, max_score=None):
+        """The full queries x graphs matrix of scores, a [n_queries, n_graphs] u32 array (score_pairs with pairs=None).
+        max_score: None, or a cap — a scalar or one value per query; entries above it are POA_NONE."""
+        if max_score is not None and np.ndim(max_score) != 0:
+            max_score = np.asarray(max_score, np.uint32)
+            if max_score.shape != (len(seqs),):
+                raise ValueError("max_score: a scalar or one value per query (%d)" % len(seqs))
+            max_score = np.repeat(max_score, len(graphs))
+        score, _ = self.score_pairs(graphs, seqs, None, max_score=max_score)
         return score.reshape(len(seqs), len(graphs))

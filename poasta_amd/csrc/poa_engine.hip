@@ -638,6 +638,20 @@ int poa_graph_update(poa_graph_t* g, uint32_t n, uint32_t start, uint32_t end, c
     return POA_OK;
 }
 
+int poa_graph_sweep_checks(const poa_graph_t* g, uint32_t stride, uint8_t* check, uint32_t* n_checks) {
+    if (!g || !n_checks) return fail(POA_ERR_INVALID_ARG, "poa_graph_sweep_checks: null argument");
+    std::vector<uint32_t> rows;
+    try {
+        build_sweep_checks(g->sweep.cut.data(), (uint32_t)g->sweep.cut.size(), stride, rows);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_graph_sweep_checks: host allocation failed"); }
+    if (check) {
+        std::memset(check, 0, g->sweep.cut.size());
+        for (uint32_t r : rows) check[r] = 1;
+    }
+    *n_checks = (uint32_t)rows.size();
+    return POA_OK;
+}
+
 int poa_graph_sweep_slots(const poa_graph_t* g, uint32_t* slot, uint32_t* n_slots) {
     if (!g || !n_slots) return fail(POA_ERR_INVALID_ARG, "poa_graph_sweep_slots: null argument");
     if (slot && !g->sweep.slot.empty()) std::memcpy(slot, g->sweep.slot.data(), g->sweep.slot.size() * sizeof(uint32_t));
@@ -2821,6 +2835,18 @@ struct poa_scoreset {
     std::vector<uint64_t> ub_open, ub_extend;   // per graph with pairs: the u16 bound is open * ub_open + extend * ub_extend
     DevBuf<uint32_t> d_slot, d_pred_slot, d_pair_graph, d_pair_query, d_carry_off, d_class_list[SS_N_VARIANTS];
     DevBuf<ScoreGraphParams> d_params;
+    // capped runs (poa_scoreset_run_capped): the device buffers and the pinned staging area are made by the set's first one
+    std::vector<uint8_t> cut;          // [n_rows_total] SweepRows::cut of every graph, concatenated like the row tables
+    DevBuf<uint32_t> d_cap, d_swept, d_check_rows;
+    uint32_t* h_stage = nullptr;       // pinned: [n_pairs] caps, then [n_rows_total] check rows
+    hipEvent_t stage_done = nullptr;   // the copies out of h_stage of the last capped run
+    bool stage_busy = false;
+    uint32_t check_stride = 0;         // the stride d_check_rows was built for (0: not built)
+    bool last_capped = false;          // the last run wrote d_swept
+    ~poa_scoreset() {
+        if (h_stage) (void)hipHostFree(h_stage);
+        if (stage_done) (void)hipEventDestroy(stage_done);
+    }
 };
 
 namespace {
@@ -2846,13 +2872,56 @@ int scoreset_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32
     return POA_OK;
 }
 
+// what a capped run needs beyond the set's own buffers; made once
+int scoreset_cap_buffers(poa_scoreset* s) {
+    const size_t n = s->core.n_queries, n_rows = s->plan.n_rows_total;
+    if (!s->d_cap.p) HIP_TRY(s->d_cap.alloc(std::max<size_t>(n, 1)));
+    if (!s->d_swept.p) HIP_TRY(s->d_swept.alloc(std::max<size_t>(n, 1)));
+    if (!s->d_check_rows.p) HIP_TRY(s->d_check_rows.alloc(std::max<size_t>(n_rows, 1)));
+    if (!s->h_stage) HIP_TRY(hipHostMalloc((void**)&s->h_stage, (n + n_rows + 1) * sizeof(uint32_t), hipHostMallocDefault));
+    if (!s->stage_done) HIP_TRY(hipEventCreateWithFlags(&s->stage_done, hipEventDisableTiming));
+    return POA_OK;
+}
+
+// the caps of this run and, if the stride changed, the check rows: through the pinned staging area, on the run's stream
+int scoreset_cap_upload(poa_scoreset* s, const uint32_t* cap, uint32_t stride, hipStream_t stream) {
+    const size_t n = s->core.n_queries;
+    if (s->stage_busy) HIP_TRY(hipEventSynchronize(s->stage_done));   // the previous capped run's copies, not its kernels
+    s->stage_busy = false;
+    std::memcpy(s->h_stage, cap, n * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(s->d_cap.p, s->h_stage, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (s->check_stride != stride && s->plan.n_rows_total) {
+        uint32_t* h_check = s->h_stage + n;
+        std::fill(h_check, h_check + s->plan.n_rows_total, 0xFFFFFFFFu);
+        std::vector<uint32_t> rows;
+        for (uint32_t g = 0; g < s->plan.graphs.size(); ++g) {
+            const ScoreSetGraphPlan& gp = s->plan.graphs[g];
+            if (gp.table_of != g) continue;
+            build_sweep_checks(s->cut.data() + gp.row_base, gp.n_rows, stride, rows);   // fewer than n_rows: a 0xFFFFFFFF follows
+            std::copy(rows.begin(), rows.end(), h_check + gp.row_base);
+        }
+        HIP_TRY(hipMemcpyAsync(s->d_check_rows.p, h_check, s->plan.n_rows_total * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        s->check_stride = stride;
+    }
+    HIP_TRY(hipEventRecord(s->stage_done, stream));
+    s->stage_busy = true;
+    return POA_OK;
+}
+
 // one sweep launch per chunk and non-empty kernel class, nothing else.  Costs are 32-bit, as in run_sweep.
-int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const poa_config_t* cfg, hipStream_t stream, const char* who) {
+// cap: nullptr, or the caps of a capped run in pair order (the capped kernels, which also write the swept-row counts).
+int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const poa_config_t* cfg, hipStream_t stream, const char* who,
+                 const uint32_t* cap = nullptr) {
     const TuneView T(cfg);
     poa_batch* b = &s->core;
     HIP_TRY(hipSetDevice(b->device));
     RunFrame run;
     if (const int rc = run.open(b, std::string(who) + ": call poa_scoreset_stats/fetch at least every 256 runs")) return rc;
+    uint32_t cap_stride = SWEEP_CHECK_STRIDE;
+    if (cap) {
+        if (const int* sv = T.ptr(POA_TUNE_CAP_STRIDE)) { if ((*sv) > 0) cap_stride = (uint32_t)(*sv); }
+        if (const int rc = scoreset_cap_buffers(s)) return rc;
+    }
     // u16 cells only if every graph's own bound (the longest query paired with it and its shortest path) allows them
     bool narrow = !planes32(T);
     for (size_t g = 0; g < s->ub_open.size(); ++g)
@@ -2866,7 +2935,13 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
     b->two_piece = false;
     set_layout(b, narrow);
     b->active_plan = 0;
+    s->last_capped = cap != nullptr;
     if (b->n_queries == 0) return run.end_empty(false);
+    if (cap) {
+        try {
+            if (const int rc = scoreset_cap_upload(s, cap, cap_stride, stream)) return rc;
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
+    }
     // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
     b->sweep_bytes_written = variant == SS_VAR_U16_PX ? 2ull * (pl.slotted_px * 2048ull + pl.slotted_pitch * 2ull)
                                                       : 2ull * pl.slotted_pitch_all * (narrow ? 2ull : 4ull);
@@ -2881,7 +2956,18 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
             if (!count) continue;
             sl.list = s->d_class_list[variant].p + begin; sl.n = count;
             const dim3 grid((count + 3) / 4), block(256);
-            if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_kernel, grid, block, 0, stream, sl);
+            if (cap) {
+                const ScoreSetCapLaunch cl{sl, s->d_cap.p, s->d_swept.p, s->d_check_rows.p, b->d_rows.p};
+                if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_capped_kernel, grid, block, 0, stream, cl);
+                else if (narrow) {
+                    if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_capped_kernel<1, uint16_t>), grid, block, 0, stream, cl);
+                    else hipLaunchKernelGGL((poa_scoreset_sweep_capped_kernel<2, uint16_t>), grid, block, 0, stream, cl);
+                } else {
+                    if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_capped_kernel<1, uint32_t>), grid, block, 0, stream, cl);
+                    else if (c == SS_CLASS_Q2) hipLaunchKernelGGL((poa_scoreset_sweep_capped_kernel<2, uint32_t>), grid, block, 0, stream, cl);
+                    else hipLaunchKernelGGL((poa_scoreset_sweep_capped_kernel<4, uint32_t>), grid, block, 0, stream, cl);
+                }
+            } else if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_kernel, grid, block, 0, stream, sl);
             else if (narrow) {
                 if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_kernel<1, uint16_t>), grid, block, 0, stream, sl);
                 else hipLaunchKernelGGL((poa_scoreset_sweep_kernel<2, uint16_t>), grid, block, 0, stream, sl);
@@ -2974,6 +3060,11 @@ int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int
     // concatenated tables, one copy per distinct handle, and the parameter block of every listed graph
     std::vector<RowMeta> h_rows(pl.n_rows_total);
     std::vector<uint32_t> h_slot(pl.n_rows_total), h_pred_rows(pl.n_edges_total), h_pred_slot(pl.n_edges_total);
+    try {
+        s->cut.assign(pl.n_rows_total, 0);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    for (uint32_t g = 0; g < n_graphs; ++g)
+        if (pl.graphs[g].table_of == g) std::copy(graphs[g]->sweep.cut.begin(), graphs[g]->sweep.cut.end(), s->cut.begin() + pl.graphs[g].row_base);
     for (uint32_t g = 0; g < n_graphs; ++g) {
         const ScoreSetGraphPlan& gp = pl.graphs[g];
         if (gp.n_pairs) {
@@ -3072,6 +3163,46 @@ int poa_scoreset_run_2piece(poa_scoreset_t* s, const poa_costs2_t* costs, const 
     // the two-piece optimum is the one-piece optimum under open' = open1 + extend1 - extend2, extend' = extend2
     return scoreset_run(s, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
                         (hipStream_t)stream, "poa_scoreset_run_2piece");
+}
+
+int poa_scoreset_run_capped(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, const uint32_t* cap, void* stream) {
+    if (!s || !costs || !cap) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run_capped: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run_capped");
+    if (rc != POA_OK) return rc;
+    return scoreset_run(s, costs->mismatch, costs->gap_open, costs->gap_extend, cfg, (hipStream_t)stream, "poa_scoreset_run_capped", cap);
+}
+
+int poa_scoreset_run_2piece_capped(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, const uint32_t* cap, void* stream) {
+    if (!s || !costs || !cap) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run_2piece_capped: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run_2piece_capped");
+    if (rc != POA_OK) return rc;
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    // the cap is compared with the score under the reduced costs, which is the two-piece score
+    return scoreset_run(s, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
+                        (hipStream_t)stream, "poa_scoreset_run_2piece_capped", cap);
+}
+
+int poa_scoreset_fetch_swept(poa_scoreset_t* s, uint32_t* swept) {
+    if (!s || !swept) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch_swept: null argument");
+    poa_batch* b = &s->core;
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch_swept: poa_scoreset_run has not been called");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const uint32_t n = b->n_queries;
+    if (!n) return POA_OK;
+    if (s->last_capped) {
+        HIP_TRY(hipMemcpy(swept, s->d_swept.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    } else {
+        // an uncapped run executes every row of every strip (strips of SCORESET_STRIP_COLUMNS columns: only a pair wider than
+        // that has more than one, whatever its kernel class)
+        const ScoreSetPlan& pl = s->plan;
+        for (uint32_t p = 0; p < n; ++p) {
+            const ScoreSetGraphPlan& gp = pl.graphs[pl.pair_graph[p]];
+            swept[p] = gp.empty ? 0u : gp.n_rows * ((pl.pitch[p] + SCORESET_STRIP_COLUMNS - 1) / SCORESET_STRIP_COLUMNS);
+        }
+    }
+    return POA_OK;
 }
 
 int poa_scoreset_fetch(poa_scoreset_t* s, uint32_t* score, uint32_t* flags, poa_stats_t* stats) {

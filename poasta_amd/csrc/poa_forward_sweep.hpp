@@ -49,6 +49,43 @@ struct SweepParams {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Capped form of the row bodies (score sets: poa_scoreset_run_capped, poa_scoreset.hpp).  The caller is interested in the score
+// only if it is at most `cap`.  At a CHECK row (poa_sweep_rows.hpp: a row every start-to-end path passes, after which no
+// earlier row is live) the wave reduces the row's M cells of columns 0..L to one minimum; scores never decrease along a
+// path, so that minimum is a lower bound on M[end row][L], and a wave whose minimum is above the cap writes its result and
+// returns.  The result does not depend on where a wave stops: the final write applies the same rule to the score itself.
+// Everything in here is wave-uniform (the callers pass it through readfirstlane): the test is a scalar compare and branch.
+struct SweepCap {
+    static constexpr bool on = true;
+    uint32_t cap;            // POA_SCORE_UNVISITED: no cap (no check can fire, the final write changes nothing)
+    const uint32_t* check;   // the graph's check rows, ascending, 0xFFFFFFFF behind the last one
+    uint32_t* swept;         // [n_pairs] row bodies the pair's wave executed
+};
+struct SweepNoCap { static constexpr bool on = false; };   // the uncapped form: nothing is passed, nothing is compiled in
+
+// minimum over the 64 lanes, uniform: the DPP steps of wave_scan_min_plus without the weights, lane 63 ends with the total
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+    v = umin(v, dpp_or_inf<0x111, 0xF>(v));
+    v = umin(v, dpp_or_inf<0x112, 0xF>(v));
+    v = umin(v, dpp_or_inf<0x114, 0xF>(v));
+    v = umin(v, dpp_or_inf<0x118, 0xF>(v));
+    v = umin(v, dpp_or_inf<0x142, 0xA>(v));
+    v = umin(v, dpp_or_inf<0x143, 0xC>(v));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// the same on both 16-bit halves at once, then the smaller half
+__device__ __forceinline__ uint32_t wave_min_pk(uint32_t v) {
+    v = pk_min(v, dpp_or_inf<0x111, 0xF>(v));
+    v = pk_min(v, dpp_or_inf<0x112, 0xF>(v));
+    v = pk_min(v, dpp_or_inf<0x114, 0xF>(v));
+    v = pk_min(v, dpp_or_inf<0x118, 0xF>(v));
+    v = pk_min(v, dpp_or_inf<0x142, 0xA>(v));
+    v = pk_min(v, dpp_or_inf<0x143, 0xC>(v));
+    const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    return umin(t & 0xFFFFu, t >> 16);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // General path: any pitch (strips of W = Q * 64 * K columns, one after the other), u16 cells where the engine's bound on
 // the optimal score allows them (arithmetic in 32-bit registers, as in poa_forward_kernel), else u32.
 //
@@ -56,10 +93,16 @@ struct SweepParams {
 // hand it the tables of the pair's own graph in P.  Of P it reads the graph tables, n_rows, n_slots, the costs and score /
 // flags; the query (L symbols at q, `pitch` columns), its slot region (M at Mp, D behind it), its carries (4 x n_rows words,
 // touched only by a query wider than one strip) and the index `out` of its result come from the caller.
-template <int Q, typename T>
+//
+// CapT = SweepCap: the capped form (CAP).  A query of one strip tests at its graph's check rows.  A row of one strip of a wider query
+// is not a cut of the cell grid, so such a query tests at the end of every strip but the last instead: the query extends
+// beyond the strip, every path to column L crosses from the strip's last column to the next one, and the minimum over all
+// rows of M in that column — the carry word, which also bounds the insertion carry from below — is a lower bound again.
+template <int Q, typename T, typename CapT = SweepNoCap>
 __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t out, const uint32_t lane, const uint32_t L,
                                            const uint8_t* __restrict__ q, const uint32_t pitch, T* __restrict__ Mp,
-                                           uint32_t* __restrict__ carry) {
+                                           uint32_t* __restrict__ carry, const CapT cap = CapT{}) {
+    constexpr bool CAP = CapT::on;
     using IO = PlaneIO<T>;
     constexpr int K = IO::K;
     constexpr int C = K * Q;
@@ -78,6 +121,14 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
         const uint32_t* __restrict__ cin_row = carry + (uint64_t)((s + 1u) & 1u) * 2u * P.n_rows;   // written by strip s - 1
         uint32_t* __restrict__ cout_row = carry + (uint64_t)(s & 1u) * 2u * P.n_rows;
         const bool from_prev = s > 0, to_next = s + 1 < n_strips;
+        const CU32* check = nullptr;   // (CAP only, like the next two) the next entry of the graph's check rows
+        uint32_t next_check = 0xFFFFFFFFu, last_col_min = INF;
+        if constexpr (CAP) {
+            check = (const CU32*)cap.check;
+            if (n_strips == 1) next_check = *check++;
+        } else {
+            (void)check; (void)next_check; (void)last_col_min;
+        }
         bool act[Q];
         uint32_t qcp[C / 4], ql[Q];
 #pragma unroll
@@ -202,6 +253,32 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
                 for (int k = 0; k < C; ++k) Mc[k] = umin(H[k], Ic[k]);
             }
             if (to_next && lane == 63) cout_row[2 * r + 1] = Mc[C - 1];  // M[r][(s + 1) * W - 1]
+            if constexpr (CAP) {
+                if (to_next) last_col_min = umin(last_col_min, Mc[C - 1]);
+                if (r == next_check) {
+                    // columns beyond L are left out: they hold real values of cells no path to column L uses, which could
+                    // only weaken the bound.  The lane's last valid column is worked out here, at the check row, and hidden
+                    // from the optimiser: as a loop invariant the C column tests would be hoisted into C scalar register
+                    // pairs, which the row loop does not have to spare (it would pay for them with spills on every row).
+                    uint32_t mn = INF;
+#pragma unroll
+                    for (int m = 0; m < Q; ++m) {
+                        int32_t last = (int32_t)(L - (sbase + m * QW + K * lane));   // columns k <= last of this lane's K are real
+                        asm volatile("" : "+v"(last));
+#pragma unroll
+                        for (int k = 0; k < K; ++k) mn = umin(mn, k <= last ? Mc[K * m + k] : INF);
+                    }
+                    if (wave_min(mn) > cap.cap) {
+                        if (lane == 0) {
+                            P.score[out] = INF;
+                            P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
+                            cap.swept[out] = r + 1;
+                        }
+                        return;
+                    }
+                    next_check = *check++;
+                }
+            }
             if (my_slot != 0xFFFFFFFFu) {
                 const uint64_t sb = (uint64_t)my_slot * pitch + sbase + K * lane;
 #pragma unroll
@@ -222,12 +299,30 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
                         if (sbase + m * QW + K * lane + k == L) v = Mc[K * m + k];
                 const uint32_t owner = ((L - sbase) % QW) / K;
                 if (lane == owner) {
-                    P.score[out] = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
-                    P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+                    if constexpr (CAP) {
+                        const uint32_t sc = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
+                        const bool over = sc > cap.cap;
+                        P.score[out] = over ? INF : sc;
+                        P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | (over ? POA_FLAG_CAPPED : 0u);
+                        cap.swept[out] = n_strips * P.n_rows;
+                    } else {
+                        P.score[out] = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
+                        P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+                    }
                 }
             }
 #pragma unroll
             for (int k = 0; k < C; ++k) { Mprev[k] = Mc[k]; Dprev[k] = Dc[k]; }
+        }
+        if constexpr (CAP) {
+            if (to_next && (uint32_t)__builtin_amdgcn_readlane((int)last_col_min, 63) > cap.cap) {
+                if (lane == 0) {
+                    P.score[out] = INF;
+                    P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
+                    cap.swept[out] = (s + 1u) * P.n_rows;
+                }
+                return;
+            }
         }
         if (n_strips > 1) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the carries of this strip, read by the next
     }
@@ -255,9 +350,11 @@ __global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
 //
 // The rows of one query: the body of poa_sweep_px_kernel, shared with the score-set kernels (poa_scoreset.hpp) as sweep_rows
 // is.  L <= 1023 symbols at q; Mp is the calling lane's place in the query's region, [M: n_slots x 128 uint4 | D: n_slots x
-// 128 uint4] + lane; the result goes to index `out`.
+// 128 uint4] + lane; the result goes to index `out`.  CapT = SweepCap: the capped form (CAP), tested at the graph's check rows.
+template <typename CapT = SweepNoCap>
 __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32_t out, const uint32_t lane, const uint32_t L,
-                                              const uint8_t* __restrict__ q, uint4* __restrict__ Mp) {
+                                              const uint8_t* __restrict__ q, uint4* __restrict__ Mp, const CapT cap = CapT{}) {
+    constexpr bool CAP = CapT::on;
     constexpr int K = 8;
     constexpr uint32_t QW = 64 * K;
     constexpr uint32_t I16 = 0xFFFFu, INF2 = 0xFFFFFFFFu;
@@ -308,6 +405,15 @@ __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32
     uint32_t PMc[K], PDc[K], PMlc = INF2;   // predecessor minima of the last multi-predecessor row (ROW_SAME_PREDS reuses them)
 #pragma unroll
     for (int k = 0; k < K; ++k) { PMc[k] = INF2; PDc[k] = INF2; }
+
+    // (CAP) 0xFFFF in every half whose column lies beyond L: those cells stay out of a check row's minimum
+    uint32_t pad[K];
+    uint32_t ci = 0, next_check = 0xFFFFFFFFu;
+    if constexpr (CAP) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) pad[k] = (c_lo + k <= L ? 0u : I16) | (c_hi + k <= L ? 0u : 0xFFFF0000u);
+        next_check = ((const CU32*)cap.check)[0];
+    }
 
     poa_u32x4 mw_ahead = crows[0];   // row record and slot, read one row ahead
     uint32_t slot_ahead = cslot[0];
@@ -456,6 +562,22 @@ __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32
             for (int k = 0; k < K; ++k) { PMc[k] = PM[k]; PDc[k] = PD[k]; }
         }
         row_body(PM, PD);
+        if constexpr (CAP) {
+            if (r == next_check) {
+                // register min tree over the lane's eight packed cells, both halves being columns, then across the lanes
+                const uint32_t a = pk_min(pk_min(Mc[0] | pad[0], Mc[1] | pad[1]), pk_min(Mc[2] | pad[2], Mc[3] | pad[3]));
+                const uint32_t b = pk_min(pk_min(Mc[4] | pad[4], Mc[5] | pad[5]), pk_min(Mc[6] | pad[6], Mc[7] | pad[7]));
+                if (wave_min_pk(pk_min(a, b)) > cap.cap) {   // (0xFFFF is INF: a cap of 0xFFFF or more never fires)
+                    if (lane == 0) {
+                        P.score[out] = INF;
+                        P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
+                        cap.swept[out] = r + 1;
+                    }
+                    return;
+                }
+                next_check = ((const CU32*)cap.check)[++ci];
+            }
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) { Mprev[k] = Mc[k]; Dprev[k] = Dc[k]; }
     }
@@ -470,8 +592,16 @@ __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32
         const uint32_t kk = col & 7u;
         uint32_t v = reinterpret_cast<const uint32_t*>(&my_tab[(kk >> 2) * 64])[kk & 3u];
         v = L >= QW ? v >> 16 : v & 0xFFFFu;
-        P.score[out] = v == I16 ? INF : v;
-        P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+        if constexpr (CAP) {
+            const uint32_t sc = v == I16 ? INF : v;
+            const bool over = sc > cap.cap;
+            P.score[out] = over ? INF : sc;
+            P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | (over ? POA_FLAG_CAPPED : 0u);
+            cap.swept[out] = P.n_rows;
+        } else {
+            P.score[out] = v == I16 ? INF : v;
+            P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
+        }
     }
 }
 

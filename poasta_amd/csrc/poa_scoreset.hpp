@@ -13,6 +13,9 @@
 // A pair's slot region starts at its own offset into the chunk's workspace (4-byte cells, whatever the cell type of the run: a
 // u16 run and the packed kernel's 2048-byte slot rows use the front of a region sized for u32), its strip carries at
 // carry_off[p] (4 x n_rows(graph) words, only for a pair wider than 1024 columns).
+//
+// Capped runs (poa_scoreset_run_capped): kernels of their own, which call the capped form of the same row bodies (SweepCap) with
+// the pair's cap and its graph's check rows.  The uncapped kernels and their argument block are untouched by them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,6 +46,15 @@ struct ScoreSetLaunch {
     uint32_t cost_x, cost_oe, cost_e;
 };
 
+// what a capped run adds to a launch
+struct ScoreSetCapLaunch {
+    ScoreSetLaunch A;
+    const uint32_t* cap;              // [n_pairs] POA_SCORE_UNVISITED: no cap
+    uint32_t* swept;                  // [n_pairs] row bodies executed
+    const uint32_t* check_rows;       // concatenated like the row tables: per graph its check rows, ascending, then 0xFFFFFFFF
+    const RowMeta* rows_base;         // start of the concatenated row tables: a graph's rows - rows_base is its base in check_rows
+};
+
 __device__ __forceinline__ uint32_t scoreset_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // the wave's pair, its query and its graph's parameter block; false: nothing to compute for this wave (no pair, or a pair
@@ -68,6 +80,40 @@ __device__ __forceinline__ bool scoreset_load(const ScoreSetLaunch& A, uint32_t 
     return true;
 }
 
+// the same for a capped run (a function of its own, so that the uncapped kernels are compiled from the text they had): the
+// pair's cap applies to the shortcut result as to any other, and no row body runs for it
+__device__ __forceinline__ bool scoreset_load_capped(const ScoreSetCapLaunch& C, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
+                                                     const uint8_t*& q) {
+    const ScoreSetLaunch& A = C.A;
+    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (w >= A.n) return false;
+    p = scoreset_uni(A.list[w]);
+    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
+    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
+    P = gp->P;
+    const uint32_t empty = gp->empty;
+    P.cost_x = A.cost_x; P.cost_oe = A.cost_oe; P.cost_e = A.cost_e;
+    const uint64_t qbeg = A.qoff[qid];
+    L = (uint32_t)(A.qoff[qid + 1] - qbeg);
+    q = A.qseq + qbeg;
+    if (empty) {
+        const bool over = L * 4u > C.cap[p];
+        if (lane == 0) {
+            P.score[p] = over ? 0xFFFFFFFFu : L * 4u;
+            P.flags[p] = POA_FLAG_EMPTY_GRAPH | (over ? POA_FLAG_CAPPED : 0u);
+            C.swept[p] = 0;
+        }
+        return false;
+    }
+    return true;
+}
+
+// the pair's cap and its graph's check rows, uniform like the pair's ids
+__device__ __forceinline__ SweepCap scoreset_cap(const ScoreSetCapLaunch& C, const SweepParams& P, uint32_t p) {
+    return SweepCap{scoreset_uni(C.cap[p]), C.check_rows + (P.rows - C.rows_base), C.swept};
+}
+
 template <int Q, typename T>
 __global__ __launch_bounds__(256) void poa_scoreset_sweep_kernel(ScoreSetLaunch A) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -87,6 +133,28 @@ __global__ __launch_bounds__(256) void poa_scoreset_sweep_px_kernel(ScoreSetLaun
     SweepParams P;
     if (!scoreset_load(A, lane, p, P, L, q)) return;
     sweep_px_rows(P, p, lane, L, q, reinterpret_cast<uint4*>(A.planes + A.region_off[p]) + lane);
+}
+
+template <int Q, typename T>
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_capped_kernel(ScoreSetCapLaunch C) {
+    const ScoreSetLaunch& A = C.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    if (!scoreset_load_capped(C, lane, p, P, L, q)) return;
+    sweep_rows<Q, T, SweepCap>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                           A.carry + scoreset_uni(A.carry_off[p]), scoreset_cap(C, P, p));
+}
+
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_px_capped_kernel(ScoreSetCapLaunch C) {
+    const ScoreSetLaunch& A = C.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    if (!scoreset_load_capped(C, lane, p, P, L, q)) return;
+    sweep_px_rows<SweepCap>(P, p, lane, L, q, reinterpret_cast<uint4*>(A.planes + A.region_off[p]) + lane, scoreset_cap(C, P, p));
 }
 
 }  // namespace poa_amd

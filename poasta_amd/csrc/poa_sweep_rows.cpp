@@ -43,6 +43,28 @@ void build_sweep_rows(const FlatGraph& g, SweepRows& out) {
         busy.push(Busy(out.last_reader[r], s));
     }
     for (size_t k = 0; k < g.pred_rows.size(); ++k) out.pred_slot[k] = out.slot[g.pred_rows[k]];
+    // cut rows: an edge (p, r) covers the rows strictly between its ends (every edge counts, the chain rows' too)
+    std::vector<int32_t> cover((size_t)n + 1, 0);
+    for (uint32_t r = 0; r < n; ++r) {
+        const RowMeta& m = g.rows[r];
+        for (uint32_t pe = 0; pe < m.pred_count; ++pe) {
+            const uint32_t p = g.pred_rows[m.pred_begin + pe];
+            if (p + 1 < r) { cover[p + 1]++; cover[r]--; }
+        }
+    }
+    out.cut.assign(n, 0);
+    int32_t depth = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        depth += cover[r];
+        out.cut[r] = depth == 0;
+    }
+}
+
+void build_sweep_checks(const uint8_t* cut, uint32_t n_rows, uint32_t stride, std::vector<uint32_t>& check_rows) {
+    check_rows.clear();
+    if (stride == 0) stride = SWEEP_CHECK_STRIDE;
+    for (uint32_t r = 0; r + 1 < n_rows; ++r)
+        if (cut[r] && (check_rows.empty() || r - check_rows.back() >= stride)) check_rows.push_back(r);
 }
 
 // rows p < b of boundary b's snapshot that the slot table knows: slotted, read by some row >= b

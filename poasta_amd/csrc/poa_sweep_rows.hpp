@@ -25,9 +25,19 @@ struct SweepRows {
     std::vector<uint32_t> last_reader; // [n] largest row that reads the row (rows with a slot only; else the row itself)
     uint32_t n_slots = 0;              // rows live at once
     uint32_t n_slotted = 0;            // rows that have a slot (what a sweep stores per query and plane)
+    std::vector<uint8_t> cut;          // [n] 1: a cut row (see build_sweep_checks)
 };
 
 void build_sweep_rows(const FlatGraph& g, SweepRows& out);
+
+// Check rows of a capped sweep (poa_scoreset_run_capped).  Row r is a CUT row if no edge (u, v) has row(u) < r < row(v): every
+// start-to-end path of the graph then passes through row r, and once row r has run no row before it is still live — neither in
+// the slot table nor as the chain row handed over in registers, which is row r itself.  Costs are non-negative, so the score
+// of a path never decreases along it: the smallest M value of a cut row is a lower bound on M[end row][len].  Row 0 and the
+// end row are cut rows.  The CHECK rows are the cut rows without the end row (the result is written there anyway), thinned
+// greedily in row order so that two consecutive check rows lie at least `stride` rows apart (0: SWEEP_CHECK_STRIDE).
+constexpr uint32_t SWEEP_CHECK_STRIDE = 8;
+void build_sweep_checks(const uint8_t* cut, uint32_t n_rows, uint32_t stride, std::vector<uint32_t>& check_rows);
 
 // Segment plan of the checkpointed mode (POA_MODE_CHECKPOINT, poa_checkpoint.hpp).  Host code, no device needed.
 //
