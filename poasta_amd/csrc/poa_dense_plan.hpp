@@ -1,0 +1,42 @@
+// What the dense one-piece pass (poa_batch_run_ex) runs: one decision per run (cell width, layout, chunk plan, overrides) and one per
+// chunk (forward kernel, column groups, waves, cell encoding, traceback lanes and depth).  Host code, no device dependency: the
+// launcher in poa_engine.hip only carries the records out, and tests/dense_plan_host checks the rule on the CPU.
+#pragma once
+#include <cstdint>
+
+#include "../../include/poasta_amd.h"
+
+// poa_config_t.tune: what a call overrides (the library reads no environment variable)
+struct TuneView {
+    int val[POA_TUNE_COUNT]; bool set[POA_TUNE_COUNT];
+    explicit TuneView(const poa_config_t* cfg) { for (int k = 0; k < POA_TUNE_COUNT; ++k) { set[k] = cfg && cfg->tune[k] != 0; val[k] = set[k] ? (int)cfg->tune[k] - 1 : 0; } }
+    const int* ptr(int k) const { return set[k] ? &val[k] : nullptr; }
+};
+
+namespace poa_amd {
+constexpr uint32_t DENSE_MW_MAX_WAVES = 16;   // waves per workgroup of a multi-wave kernel at most (MW_MAX_WAVES, poa_kernels.hpp)
+uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend);
+bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend);
+bool planes32(const TuneView& T);
+uint32_t mw_waves(uint32_t strips);
+bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch);
+
+struct DenseRunPlan {
+    uint64_t ub;                             // bound on the optimal score of any query of the batch
+    bool narrow, compact, relative, packed;  // u16 cells; compact layout; relative encoding; packed-u16 arithmetic kernels
+    int plan;                                // chunk plan of the batch: 0 (4-byte elements), 1 (u16 full planes), 2 (compact)
+    bool fuse_tb, want_band;
+    int quads_override, band_pair, tb_group; // 0: no override; -1: by the rule; 0: by the chunk's count
+    uint32_t band_cap, spec_depth;
+};
+DenseRunPlan plan_dense_run(uint32_t gap_open, uint32_t gap_extend, uint64_t max_len, uint64_t min_path_nodes, uint32_t mode, bool full_planes,
+                            bool plan16_same, const TuneView& T);
+
+struct DenseChunkPlan {
+    uint32_t v[8];     // poa_batch_last_launch: kernel, quads, POA_LAUNCH_* bits, waves per workgroup, code_fmt, traceback lanes (0: fused), depth, queries
+    int mf;            // flag variant of the px kernel and of the banded pair, -1 where another kernel runs
+    bool band;         // the banded pair runs (v[0] == POA_KERNEL_BAND)
+    bool separate_tb;  // the traceback is a launch of its own (v[5] != 0)
+};
+DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T);
+}  // namespace poa_amd

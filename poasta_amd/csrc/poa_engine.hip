@@ -22,12 +22,7 @@
 #include "poa_wsearch.hpp"
 #include "poa_fsearch.hpp"
 
-// poa_config_t.tune: what a call overrides (the library reads no environment variable)
-struct TuneView {
-    int val[POA_TUNE_COUNT]; bool set[POA_TUNE_COUNT];
-    explicit TuneView(const poa_config_t* cfg) { for (int k = 0; k < POA_TUNE_COUNT; ++k) { set[k] = cfg && cfg->tune[k] != 0; val[k] = set[k] ? (int)cfg->tune[k] - 1 : 0; } }
-    const int* ptr(int k) const { return set[k] ? &val[k] : nullptr; }
-};
+#include "poa_dense_plan.hpp"
 #include "poa_kernels.hpp"
 #include "poa_forward_packed.hpp"
 #include "poa_forward_px.hpp"
@@ -279,8 +274,7 @@ struct poa_batch {
     bool band_used = false;
     uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
     // what the dense one-piece path launched per chunk of the last run (poa_batch_last_launch); empty after any other run
-    struct Launch { uint32_t v[8]; };
-    std::vector<Launch> launches;
+    std::vector<DenseChunkPlan> launches;
 
     // one event set per run since the last stats call, written by RunFrame and read by collect_stats
     std::vector<std::vector<hipEvent_t>> runs;
@@ -416,26 +410,11 @@ struct RunFrame {
     }
 };
 
-// u16 cells whenever every value that can matter fits.  u16 arithmetic saturates at 0xFFFF = INF, so every stored value is
-// min(true value, 0xFFFF); costs are non-negative, hence every cell on an optimal path — and every predecessor candidate the
-// traceback can accept — has a value <= the final score, and the final score is at most
-//     ub = [o + e*L] + [o + e*(nodes on the shortest start->end path)]      (insert the query, delete that path),
-// each bracket counted only if its length is not zero: ub = o * n_open + e * n_extend.  ub <= 0xFFFE  =>  everything the result
-// depends on is exact in u16.  (The cruder bound (rows + L + 2) * max(x, o+e) on ANY finite value is always >= ub.)  The
-// two-piece model takes the first piece's costs: a gap never costs more than its first-piece price.
-static uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend) { return open * n_open + extend * n_extend; }
-static bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend) {
-    return score_bound(open, extend, n_open, n_extend) <= 65534;
-}
-// the same for one graph and the longest query that meets it
-static uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t max_len, const FlatGraph& fg) {
-    return score_bound(open, extend, (max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0), max_len + fg.min_path_nodes);
-}
+// u16_cells_suffice (poa_dense_plan.cpp) for one graph and the longest query that meets it
 static bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t max_len, const FlatGraph& fg) {
     return u16_cells_suffice(open, extend, (max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0), max_len + fg.min_path_nodes);
 }
-// POA_PLANES=32 forces u32 cells (debug / A-B)
-static bool planes32(const TuneView& T) { const int* pv = T.ptr(POA_TUNE_PLANES); return pv && *pv == 32; }
+static_assert(DENSE_MW_MAX_WAVES == MW_MAX_WAVES, "the plan's waves per workgroup are the kernels'");
 
 // the layout of the last run, as poa_batch_last_layout and the plane fetches read it
 static void set_layout(poa_batch* b, bool narrow, bool compact = false, bool relative = false) {
@@ -457,15 +436,6 @@ static void launch_by_pitch(bool narrow, uint32_t max_pitch, Launch&& launch) {
         else if (max_pitch <= 512) launch(uint32_t{}, integral_constant<int, 2>{});
         else launch(uint32_t{}, integral_constant<int, 4>{});
     }
-}
-
-// the 1024-column multi-wave kernel when the chunk fills the chip with one wave per 1024 columns (else 512-column strips of
-// the adjacent-pairs kernel give twice the waves)
-// waves per workgroup of a multi-wave launch: all strips at once when they fit, else the strips spread evenly over the
-// groups that run one after the other (16 + 4 strips would leave twelve waves idle in the second group)
-static uint32_t mw_waves(uint32_t strips) {
-    const uint32_t groups = (strips + MW_MAX_WAVES - 1) / MW_MAX_WAVES;
-    return (strips + groups - 1) / groups;
 }
 
 // the band plan of a resident batch: classes by query length, their band distances and window bases, uploaded once
@@ -533,11 +503,6 @@ static int prepare_band_pairs(poa_batch* b) {
     return POA_OK;
 }
 
-static bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch) {
-    if (const int* v = T.ptr(POA_TUNE_PXMW)) return (*v) != 0;
-    return (uint64_t)count * ((max_pitch + 1023) / 1024) >= 1024;
-}
-
 // Greedy chunking of the queries over `ws` bytes of workspace (elems_of(i) elements of elem_bytes each), with the chunks evened
 // out: the forward kernels that take a workgroup per query finish with their most loaded CU, so 2 000 queries that fit 527 at
 // a time run as 4 x 500, not 3 x 527 + 419 (measured on configs[4]: 434 -> 320 ms).
@@ -576,6 +541,359 @@ static void build_chunk_plan(poa_batch::Plan& pl, uint32_t n_queries, uint64_t w
     pl.max_chunk = 0;
     for (auto& c : pl.chunks) pl.max_chunk = std::max(pl.max_chunk, c.count);
 }
+
+// ---- the dense one-piece pass (poa_batch_run_ex): the records of poa_dense_plan.cpp, carried out ---------------------------
+namespace {
+// every forward launch of a chunk but the banded pair: the kernel and its template arguments as the chunk's record names them
+void launch_forward(const DenseRunPlan& R, const DenseChunkPlan& c, const FwdParams& fp, const TbParams& tp, hipStream_t stream) {
+    using std::integral_constant;
+    const uint32_t quads = c.v[1];
+    const bool fuse = c.v[2] & POA_LAUNCH_FUSE, mw = c.v[2] & POA_LAUNCH_MW;
+    // multi-wave: one workgroup per query, a wave per strip at a time; else four queries per workgroup
+    const dim3 grid(mw ? c.v[7] : (c.v[7] + 3) / 4), block(mw ? 64 * c.v[3] : 256);
+    auto plain = [&](auto cell, auto q) {   // full planes: fused walk or not
+        if (fuse) hipLaunchKernelGGL((poa_forward_kernel<decltype(q)::value, decltype(cell), true, false>), grid, block, 0, stream, fp, tp);
+        else hipLaunchKernelGGL((poa_forward_kernel<decltype(q)::value, decltype(cell), false, false>), grid, block, 0, stream, fp, tp);
+    };
+    switch (c.v[0]) {
+    case POA_KERNEL_PX:
+        if (c.mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, grid, block, 0, stream, fp);
+        else if (c.mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, grid, block, 0, stream, fp);
+        else if (c.mf == 1) hipLaunchKernelGGL(poa_forward_px_kernel<1>, grid, block, 0, stream, fp);
+        else hipLaunchKernelGGL(poa_forward_px_kernel<0>, grid, block, 0, stream, fp);
+        break;
+    case POA_KERNEL_PXMW:
+        hipLaunchKernelGGL(poa_forward_pxmw_kernel, grid, block, 0, stream, fp);
+        break;
+    case POA_KERNEL_PACKED:
+        if (mw && quads == 1) hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, true>), grid, block, 0, stream, fp, tp);
+        else if (mw) hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, true>), grid, block, 0, stream, fp, tp);
+        else if (quads == 1 && fuse) hipLaunchKernelGGL((poa_forward_packed_kernel<1, true, false>), grid, block, 0, stream, fp, tp);
+        else if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, false>), grid, block, 0, stream, fp, tp);
+        else if (fuse) hipLaunchKernelGGL((poa_forward_packed_kernel<2, true, false>), grid, block, 0, stream, fp, tp);
+        else hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, false>), grid, block, 0, stream, fp, tp);
+        break;
+    default:   // POA_KERNEL_FORWARD
+        if (mw && quads == 4) hipLaunchKernelGGL((poa_forward_kernel<4, uint32_t, false, false, true>), grid, block, 0, stream, fp, tp);
+        else if (mw) hipLaunchKernelGGL((poa_forward_kernel<2, uint32_t, false, false, true>), grid, block, 0, stream, fp, tp);
+        else if (R.compact && quads == 1) hipLaunchKernelGGL((poa_forward_kernel<1, uint16_t, false, true>), grid, block, 0, stream, fp, tp);
+        else if (R.compact) hipLaunchKernelGGL((poa_forward_kernel<2, uint16_t, false, true>), grid, block, 0, stream, fp, tp);
+        else if (R.narrow && quads == 1) plain(uint16_t{}, integral_constant<int, 1>{});
+        else if (R.narrow) plain(uint16_t{}, integral_constant<int, 2>{});
+        else if (quads == 1) plain(uint32_t{}, integral_constant<int, 1>{});
+        else if (quads == 2) plain(uint32_t{}, integral_constant<int, 2>{});
+        else plain(uint32_t{}, integral_constant<int, 4>{});
+    }
+}
+
+// the banded pass, then the full pass (the same kernel with eight registers per row array and one window of 1024 columns) over
+// the queries it could not certify: the grid is sized for the chunk and the waves past the device-side count return at once,
+// so the host never waits for the count
+int launch_band(poa_batch* b, size_t ci, const DenseRunPlan& R, const FwdParams& fp, hipStream_t stream) {
+    const poa_batch::Chunk& ch = b->cur().chunks[ci];
+    const uint32_t blocks = (ch.count + 3) / 4;
+    if (const int rc = prepare_band(b)) return rc;
+    BandParams bp;
+    bp.cls = b->d_band_cls.p; bp.cls_d = b->d_band_d.p; bp.cls_base = b->d_band_base.p; bp.n_seg = b->band_n_seg;
+    bp.d_cap = R.band_cap; bp.list = b->d_band_list.p; bp.count = b->d_band_count.p + ci; bp.order = nullptr;
+    uint32_t n_pairs = 0;
+    if (R.band_pair != 0) {
+        if (const int rc = prepare_band_pairs(b)) return rc;
+        n_pairs = b->h_band_npair[ci];
+        if (R.band_pair < 0 && !band_pair_rule(2 * n_pairs)) n_pairs = 0;
+    }
+    if (n_pairs) {
+        // the pairs, then the singles one per wave: grids sized on the host, nothing read back
+        const uint32_t n_single = ch.count - 2 * n_pairs;
+        FwdParams fq = fp;
+        BandParams bq = bp;
+        fq.n_queries = n_pairs; bq.order = b->d_band_order.p + ch.first;
+        hipLaunchKernelGGL(poa_forward_band2_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, stream, fq, bq);
+        if (n_single) {
+            HIP_TRY(hipGetLastError());
+            fq.n_queries = n_single; bq.order = b->d_band_order.p + ch.first + 2 * n_pairs;
+            hipLaunchKernelGGL((poa_forward_band_kernel<false, true>), dim3((n_single + 3) / 4), dim3(256), 0, stream, fq, bq);
+        }
+        b->pair_paired += 2 * n_pairs; b->pair_single += n_single;
+    } else {
+        hipLaunchKernelGGL(poa_forward_band_kernel<false>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+        b->pair_single += ch.count;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(poa_forward_band_kernel<true>, dim3(blocks), dim3(256), 0, stream, fp, bp);
+    uint32_t min_d = 0xFFFFFFFFu;
+    for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) min_d = std::min(min_d, std::min(b->h_band_d[b->h_band_cls[i]], R.band_cap));
+    b->band_min_d = b->band_used ? std::min(b->band_min_d, min_d) : min_d;
+    b->band_used = true; b->band_queries += ch.count; b->band_chunks = (uint32_t)ci + 1;
+    return POA_OK;
+}
+
+// the separate traceback launch of a chunk: 256 / lanes walks per workgroup; the compact layout at the depth that goes with its lanes
+void launch_traceback(const DenseRunPlan& R, const DenseChunkPlan& c, const TbParams& tp, hipStream_t stream) {
+    const uint32_t lanes = c.v[5], per_block = 256 / lanes;
+    const dim3 grid((c.v[7] + per_block - 1) / per_block), block(256);
+    TbParams tpg = tp;
+    tpg.spec_depth = c.v[6];
+    if (R.compact && lanes == 16) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 16>), grid, block, 0, stream, tpg);
+    else if (R.compact && lanes == 32) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 32>), grid, block, 0, stream, tpg);
+    else if (R.compact && lanes == 8) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 8>), grid, block, 0, stream, tpg);
+    else if (R.compact) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true>), grid, block, 0, stream, tpg);
+    else if (R.narrow) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, false>), grid, block, 0, stream, tp);
+    else hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), grid, block, 0, stream, tp);
+}
+
+// ---- exact replay of the reference's search on the (re-initialised, u32) planes of a chunk ---------------------------------
+// what the wave and the flat search take alike: the chunked queues in the pool (POA_WS_CHUNK_CAP caps them), the descriptor ring's
+// size, the counters, the per-phase cycle counts (POA_WS_PROF: diagnostics) and, until a persistent schedule says otherwise, no order
+template <typename SearchParams>
+void fill_search_params(SearchParams& sp, poa_batch* b, const ExactParams& ep, const TuneView& T) {
+    sp.E = ep;
+    sp.chunks = reinterpret_cast<ExU4*>(b->d_ex_pool.p);
+    sp.chunk_cap = b->ex_pool_cap / BQ_CHUNK;
+    if (const int* cv = T.ptr(POA_TUNE_WS_CHUNK_CAP)) { const int v = (*cv); if (v >= 1 && (uint32_t)v < sp.chunk_cap) sp.chunk_cap = (uint32_t)v; }
+    sp.win = b->ex_win;
+    sp.counters = b->d_ex_counters.p;
+    sp.prof = T.ptr(POA_TUNE_WS_PROF) ? b->d_ex_prof.p : nullptr;
+    sp.work_counter = nullptr; sp.order = nullptr;
+}
+
+// blocks of a replay kernel that are resident on the device at once
+uint32_t resident_blocks(poa_batch* b, const void* kfn, uint32_t wpb, uint32_t lds_bytes) {
+    int per_cu = 1, cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, (int)(64 * wpb), lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
+    return (uint32_t)cus * (uint32_t)per_cu;
+}
+
+// persistent waves: as many blocks as are resident at once; queries handed out longest-expected-search first (by the dense
+// pass's score: more edits, more buckets).  The sort needs the scores on the host: one small copy behind the dense pass of
+// this chunk.  Sets the work counter and the order of `sp` and cuts n_blocks to `resident`.
+template <typename SearchParams>
+int persistent_schedule(poa_batch* b, const poa_batch::Chunk& ch, uint32_t resident, hipStream_t stream, SearchParams& sp, uint32_t& n_blocks) {
+    std::vector<uint32_t> sc(ch.count), ord(ch.count);
+    HIP_TRY(hipMemcpyAsync(sc.data(), b->d_score.p + ch.first, (size_t)ch.count * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (uint32_t i = 0; i < ch.count; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t c2) { return sc[a] > sc[c2]; });
+    HIP_TRY(b->d_ex_order.alloc(ch.count + 1));
+    HIP_TRY(hipMemcpyAsync(b->d_ex_order.p + 1, ord.data(), (size_t)ch.count * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(b->d_ex_order.p, 0, 4, stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // `ord` is a host temporary
+    sp.work_counter = b->d_ex_order.p; sp.order = b->d_ex_order.p + 1;
+    n_blocks = resident;
+    return POA_OK;
+}
+
+// "flat": the parallel-step kernel (poa_fsearch.hpp) — bit-identical like the others, not the fastest yet.
+// The next entries in pop order expanded at once, one per lane, several queries per wave.
+int replay_flat(poa_batch* b, const poa_batch::Chunk& ch, const ExactParams& ep, const TuneView& T, bool ends_free, int lds_cap, hipStream_t stream) {
+    const FlatGraph& fg = b->graph->g;
+    const uint32_t win = b->ex_win, graph_lds = exact_lds_bytes(fg.n, ep.n_succ, ep.n_nbm);
+    FSearchParams pp;
+    fill_search_params(pp, b, ep, T);
+    pp.max_lanes = 63;   // (capped at the group's lanes below)
+    if (const int* lv = T.ptr(POA_TUNE_PS_LANES)) { const int v = (*lv); if (v >= 1 && v <= 63) pp.max_lanes = (uint32_t)v; }
+    // Lanes per query: a step commits a dozen lanes on the benchmark's reads, and the kernel waits for memory more than it
+    // issues — so four searches share a wave (16 lanes each), all stepping through one instruction stream.
+    pp.lean = (!fg.row_rec.empty() && !ends_free) ? 1u : 0u;
+    if (const int* lv = T.ptr(POA_TUNE_PS_LEAN)) pp.lean = (pp.lean && (*lv) != 0) ? 1u : 0u;
+    const uint32_t group = pp.lean ? 8u : 16u;   // (the group sizes poa_fsearch.hpp is built for)
+    const uint32_t qpw = 64 / group;
+    pp.group = group;
+    if (pp.max_lanes > group) pp.max_lanes = group;
+    // LDS of a block: the staged graph (shared by its waves) + per wave the descriptor rings of its queries and the
+    // logs / read sets / conflict tables of the step.  As many waves per block as fit 160 KB, at most 8 (two per SIMD:
+    // the kernel keeps a lane's search state in ~250 registers).
+    const uint64_t lds_budget = std::min<uint64_t>((uint64_t)lds_cap, 160u * 1024u);
+    const uint64_t ring_b = ((uint64_t)qpw * 3 * win * 4 + 15) & ~15ull;
+    // the lean step reads one 32-byte record per row: those are staged (the arrays of the generic code, which it
+    // falls back to for a row in a thousand, stay in global memory); without records the generic code runs in log mode
+    const uint64_t rec_b = pp.lean ? ((sizeof(FlatGraph::RowRec) * (uint64_t)fg.n + 15) & ~15ull) : 0;
+    const uint64_t stage_b = pp.lean ? rec_b : graph_lds;
+    bool ring_lds = ring_b + ps_lds_bytes() <= lds_budget && !T.ptr(POA_TUNE_WS_RING_GLOBAL);
+    uint64_t per_wave = (ring_lds ? ring_b : 0) + ps_lds_bytes();
+    bool stage = stage_b + per_wave <= lds_budget;
+    if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) stage = stage && (*gv) != 0;
+    uint32_t wpb = (uint32_t)std::min<uint64_t>(8, (lds_budget - (stage ? stage_b : 0)) / per_wave);
+    if (const int* wv = T.ptr(POA_TUNE_WS_WAVES)) { const int v = (*wv); if (v >= 1 && (uint32_t)v <= wpb) wpb = (uint32_t)v; }
+    if (wpb < 1) return fail(POA_ERR_UNSUPPORTED, "exact replay: the step's logs do not fit the LDS");
+    pp.graph_lds = (stage && !pp.lean) ? graph_lds : 0;
+    pp.rec_lds = (stage && pp.lean) ? (uint32_t)rec_b : 0;
+    pp.waves_per_block = wpb;
+    pp.ring_global = ring_lds ? nullptr : b->d_ex_head.p;   // [slots * 3 * ex_n_prio] holds slots * 3 * win
+    const uint32_t lds_bytes = pp.graph_lds + pp.rec_lds + (uint32_t)(wpb * per_wave);
+    const void* kfn = pp.lean ? reinterpret_cast<const void*>(poa_fsearch_lean_kernel) : reinterpret_cast<const void*>(poa_fsearch_kernel);
+    if (lds_bytes > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const uint32_t per_block = wpb * qpw;
+    uint32_t n_blocks = (ch.count + per_block - 1) / per_block;
+    const uint32_t resident = resident_blocks(b, kfn, wpb, lds_bytes);
+    if (n_blocks > resident && !T.ptr(POA_TUNE_WS_STATIC)) {   // persistent waves, longest expected search first
+        if (const int rc = persistent_schedule(b, ch, resident, stream, pp, n_blocks)) return rc;
+    }
+    HIP_TRY(b->d_ex_logs.alloc((size_t)n_blocks * wpb * ps_scratch_words()));
+    pp.scratch = b->d_ex_logs.p;
+    if (pp.lean) hipLaunchKernelGGL(poa_fsearch_lean_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, pp);
+    else hipLaunchKernelGGL(poa_fsearch_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, pp);
+    return POA_OK;
+}
+
+// wave-per-query search (poa_wsearch.hpp)
+int replay_wave(poa_batch* b, const poa_batch::Chunk& ch, const ExactParams& ep, const TuneView& T, int lds_cap, hipStream_t stream) {
+    const FlatGraph& fg = b->graph->g;
+    const uint32_t win = b->ex_win, graph_lds = exact_lds_bytes(fg.n, ep.n_succ, ep.n_nbm);
+    WSearchParams wp;
+    fill_search_params(wp, b, ep, T);
+    wp.max_lanes = 32;   // entries tested per step at most: runs of stale / pruned entries are short (1.85 pops per step)
+    if (const int* lv = T.ptr(POA_TUNE_WS_LANES)) { const int v = (*lv); if (v >= 1 && v <= 63) wp.max_lanes = (uint32_t)v; }
+    wp.adapt_lanes = 4;   // after an expansion the top of the stack is fresh: few entries tested; a run that used up its lanes widens
+    if (const int* av = T.ptr(POA_TUNE_WS_ADAPT)) { const int v = (*av); if (v >= 0 && v <= 63) wp.adapt_lanes = (uint32_t)v; }
+    // Lanes per query.  One query per wave (64) with persistent scheduling is the default.  Several queries per wave
+    // (POA_WS_GROUP = 32 / 16 / 8 lanes each, all through one instruction stream) issue fewer instructions in
+    // all but lose: the iteration takes the union of the groups' code paths and every wave waits for its slowest
+    // query (measured on config 2, 10 000 queries: 1.09 s at 64 persistent, 1.83 s at 64 static, 1.49 / 1.85 /
+    // 2.53 s at 32 / 16 / 8).  Waves per block: as many as share one staged copy of the graph, at most 16.
+    uint32_t group = 64;
+    if (const int* gv = T.ptr(POA_TUNE_WS_GROUP)) { const int v = (*gv); if (v == 8 || v == 16 || v == 32 || v == 64) group = (uint32_t)v; }
+    uint32_t wpb = 16;
+    if (const int* wv = T.ptr(POA_TUNE_WS_WAVES)) { const int v = (*wv); if (v >= 1 && v <= 16) wpb = (uint32_t)v; }
+    const uint64_t lds_budget = std::min<uint64_t>((uint64_t)lds_cap, 80u * 1024u);
+    bool ring_lds = false, stage = false;
+    // per-row records of the one-round-trip path (one query per wave: a block of 16 waves has the CU to itself)
+    uint32_t rec_lds = 0;
+    for (;;) {
+        const uint64_t rb = (uint64_t)wpb * (64 / group) * win * 12;
+        ring_lds = rb <= lds_budget && !T.ptr(POA_TUNE_WS_RING_GLOBAL);
+        stage = graph_lds + (ring_lds ? rb : 0) <= lds_budget;
+        if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) stage = stage && (*gv) != 0;
+        if (group == 64 || (ring_lds && stage)) break;
+        // several queries per wave need everything in LDS: fewer waves per block first, then fewer queries per wave
+        if (wpb > 2 && !T.ptr(POA_TUNE_WS_WAVES)) wpb /= 2; else { group *= 2; if (!T.ptr(POA_TUNE_WS_WAVES)) wpb = 16; }
+    }
+    const uint64_t ring_bytes = ring_lds ? (uint64_t)wpb * (64 / group) * win * 12 : 0;
+    if (group == 64 && stage && ring_lds && !fg.row_rec.empty() && !(T.ptr(POA_TUNE_WS_REC) && *T.ptr(POA_TUNE_WS_REC) == 0)) {
+        const uint64_t rb = (fg.row_rec.size() * sizeof(FlatGraph::RowRec) + 15) & ~15ull;
+        if (graph_lds + rb + ring_bytes <= std::min<uint64_t>((uint64_t)lds_cap, 150u * 1024u)) rec_lds = (uint32_t)rb;
+    }
+    wp.rec_lds = rec_lds;
+    wp.graph_lds = stage ? graph_lds : 0;
+    wp.waves_per_block = wpb;
+    wp.group = group;
+    wp.ring_global = nullptr;
+    if (!ring_lds) wp.ring_global = b->d_ex_head.p;  // [slots * 3 * ex_n_prio] holds slots * 3 * win
+    const uint32_t lds_bytes = wp.graph_lds + wp.rec_lds + (uint32_t)ring_bytes;
+    const bool lds_all = wp.graph_lds && !wp.ring_global;   // (else the kernel whose search reads through generic pointers)
+    const void* kfn = group != 64 ? reinterpret_cast<const void*>(poa_wsearch_groups_kernel)
+                                  : (lds_all ? reinterpret_cast<const void*>(poa_wsearch_kernel) : reinterpret_cast<const void*>(poa_wsearch_global_kernel));
+    if (lds_bytes > 48u * 1024u)
+        HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const uint32_t per_block = wpb * (64 / group);
+    uint32_t n_blocks = (ch.count + per_block - 1) / per_block;
+    if (group == 64 && !T.ptr(POA_TUNE_WS_STATIC)) {
+        const uint32_t resident = resident_blocks(b, kfn, wpb, lds_bytes);
+        if (n_blocks > resident) { if (const int rc = persistent_schedule(b, ch, resident, stream, wp, n_blocks)) return rc; }
+    }
+    if (group != 64) hipLaunchKernelGGL(poa_wsearch_groups_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
+    else if (lds_all) hipLaunchKernelGGL(poa_wsearch_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
+    else hipLaunchKernelGGL(poa_wsearch_global_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
+    return POA_OK;
+}
+
+// one sequential search per lane (poa_exact_kernel)
+int replay_lane(poa_batch* b, const poa_batch::Chunk& ch, ExactParams ep, const TuneView& T, hipStream_t stream) {
+    const FlatGraph& fg = b->graph->g;
+    // active lanes per wave: one sequential search per lane.  Few lanes = little divergence but many
+    // waves; enough waves to fill the chip (~16 per CU) first, then more lanes per wave.
+    uint32_t lanes = (ch.count + 4095) / 4096;
+    if (lanes > 64) lanes = 64;
+    if (const int* lv = T.ptr(POA_TUNE_EXACT_LANES)) { const int v = (*lv); if (v >= 1 && v <= 64) lanes = (uint32_t)v; }
+    ep.lanes_per_wave = lanes;
+    // graph arrays in LDS when they fit beside three other blocks of the same CU (160 KB per CU)
+    uint32_t lds_bytes = exact_lds_bytes(fg.n, ep.n_succ, ep.n_nbm);
+    bool lds_graph = lds_bytes <= 160u * 1024u / 3u;
+    if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) lds_graph = lds_graph && (*gv) != 0;
+    if (lds_graph && lds_bytes > 48u * 1024u)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(poa_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    ep.lds_graph = lds_graph ? 1u : 0u;
+    if (lds_graph && !T.ptr(POA_TUNE_EXACT_LANES)) {
+        // all blocks resident at once (no tail round): LDS bounds the blocks per CU
+        int cus = 256;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
+        const uint32_t per_cu = std::max(1u, std::min(8u, 160u * 1024u / std::max(lds_bytes, 1u)));
+        const uint32_t cap_waves = (uint32_t)cus * per_cu * (EXACT_BLOCK / 64);
+        lanes = std::min(64u, std::max(lanes, (ch.count + cap_waves - 1) / cap_waves));
+        ep.lanes_per_wave = lanes;
+    }
+    const uint32_t per_block = lanes * (EXACT_BLOCK / 64);
+    hipLaunchKernelGGL(poa_exact_kernel, dim3((ch.count + per_block - 1) / per_block), dim3(EXACT_BLOCK), lds_graph ? lds_bytes : 0, stream, ep);
+    return POA_OK;
+}
+
+// the replay's view of a chunk: graph tables, queries, planes, queues, costs and the ends-free bounds
+ExactParams exact_params(poa_batch* b, const poa_batch::Chunk& ch, const poa_costs_t* costs, const poa_config_t* cfg, uint32_t hybrid, bool ends_free) {
+    const FlatGraph& fg = b->graph->g;
+    ExactParams ep;
+    ep.G = ExactGraph{fg.n, fg.start_row, fg.end_row, b->d_ex_sym.p, b->d_succ_off.p, b->d_succ_rows.p, b->d_dist_min.p,
+                      b->d_dist_max.p, b->d_exit_idx.p, fg.n_exit, b->d_nbm_off.p, b->d_nbm.p, b->d_node_row.p, b->d_sp_to_end.p,
+                      fg.row_rec.empty() ? nullptr : b->d_ex_rec.p};
+    ep.first_query = ch.first; ep.n_queries = ch.count; ep.hybrid = hybrid; ep.dense_flags = b->d_flags.p;
+    ep.qseq = b->d_qseq.p; ep.qoff = b->d_qoff.p; ep.pitch = b->d_pitch.p; ep.plane_off = b->cur().d_off.p;
+    ep.planes = b->d_planes.p;
+    ep.reached = b->d_ex_reached.p; ep.rsum = b->d_ex_rsum.p; ep.wpn = b->ex_wpn; ep.swpn = b->ex_swpn;
+    ep.head = b->d_ex_head.p; ep.n_prio = b->ex_n_prio; ep.pool = b->d_ex_pool.p; ep.pool_cap = b->ex_pool_cap;
+    ep.stack = b->d_ex_stack.p; ep.stack_cap = b->ex_stack_cap;
+    ep.C = ExactCosts{costs->mismatch, costs->gap_open, costs->gap_extend, cfg ? cfg->heuristic : POA_HEURISTIC_MINGAP,
+                      cfg ? cfg->pruning : 1u, 0, 0, 0, 0, 0, 0};
+    if (ends_free) {
+        ep.C.ends_free = 1;
+        ep.C.qfe_kind = cfg->qry_free_end.kind; ep.C.qfe_val = cfg->qry_free_end.value;
+        ep.C.gfb_kind = cfg->graph_free_begin.kind;
+        ep.C.gfe_kind = cfg->graph_free_end.kind; ep.C.gfe_val = cfg->graph_free_end.value;
+    }
+    ep.status = b->d_ex_status.p;
+    ep.end_cell = b->d_ex_end.p;
+    ep.n_succ = (uint32_t)fg.succ_rows.size(); ep.n_nbm = (uint32_t)fg.nbm.size();
+    return ep;
+}
+
+// exact / hybrid mode: the replay of one chunk behind its dense pass, then the u32 traceback over what it left (`tp`: the dense
+// pass's traceback parameters)
+int replay_chunk(poa_batch* b, const poa_batch::Chunk& ch, const poa_costs_t* costs, const poa_config_t* cfg, const TuneView& T, uint32_t hybrid,
+                 bool ends_free, TbParams tp, hipStream_t stream) {
+    const FlatGraph& fg = b->graph->g;
+    HIP_TRY(hipMemsetAsync(b->d_ex_status.p + ch.first, 0xFF, (size_t)ch.count * 4, stream));
+    HIP_TRY(hipMemsetAsync(b->d_ex_counters.p + 4 * (size_t)ch.first, 0, (size_t)ch.count * 16, stream));
+    hipLaunchKernelGGL(poa_fill_planes_kernel, dim3(64, ch.count), dim3(256), 0, stream, b->d_planes.p, b->cur().d_off.p,
+                       b->d_pitch.p, fg.n, ch.first, hybrid, b->d_flags.p);
+    HIP_TRY(hipGetLastError());
+    if (fg.n_exit) {
+        HIP_TRY(hipMemsetAsync(b->d_ex_reached.p, 0, (size_t)ch.count * fg.n_exit * b->ex_wpn * 8, stream));
+        HIP_TRY(hipMemsetAsync(b->d_ex_rsum.p, 0, (size_t)ch.count * fg.n_exit * b->ex_swpn * 8, stream));
+    }
+    HIP_TRY(hipMemsetAsync(b->d_ex_head.p, 0xFF, (size_t)ch.count * 3 * b->ex_n_prio * 4, stream));
+    const ExactParams ep = exact_params(b, ch, costs, cfg, hybrid, ends_free);
+    // Wave-per-query search (poa_wsearch.hpp) unless its descriptor ring cannot hold the priorities that are live
+    // at once: one pop pushes at most max(x, o+e) above its own priority plus what the heuristic can jump along
+    // one edge and a state change (o), and the greedy extension walks that jump once more.
+    // live priority range: a pop at priority f pushes at most max(x, o+e) + o + e * (spread + 3) above f, where
+    // spread = max over nodes of dist_max - dist_min (the heuristic's gap length grows by at most that along any
+    // greedy extension: heuristic.rs:70-102)
+    int lds_cap = 64 * 1024;
+    (void)hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device);
+    const int* impl = T.ptr(POA_TUNE_EXACT_IMPL);   // 1 lane, 2 wave, 3 flat
+    const bool wave_search = !(impl && *impl == 1) && b->ex_win <= b->ex_n_prio;
+    int rc;
+    if (wave_search && impl && *impl == 3) rc = replay_flat(b, ch, ep, T, ends_free, lds_cap, stream);
+    else if (wave_search) rc = replay_wave(b, ch, ep, T, lds_cap, stream);
+    else rc = replay_lane(b, ch, ep, T, stream);
+    if (rc != POA_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    tp.exact_pass = 1; tp.ex_status = b->d_ex_status.p; tp.ex_end = b->d_ex_end.p; tp.row_depth = nullptr;
+    hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
+    HIP_TRY(hipGetLastError());
+    b->narrow = false; b->compact = false; b->relative = false;  // the planes now hold the replayed u32 table
+    return POA_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1118,65 +1436,28 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     }
     RunFrame run;
     if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
-    // u16 planes under the bound of u16_cells_suffice; the flag variants of the px kernel below take the bound itself
-    const uint64_t ub = score_bound(costs->gap_open, costs->gap_extend, b->max_len, fg);
-    bool narrow = u16_cells_suffice(costs->gap_open, costs->gap_extend, b->max_len, fg) && !planes32(T);
-    // compact layout (u16 only): 4-bit codes instead of the I plane, D rows only where they are read back.
-    // POA_CFG_FULL_PLANES (or POA_COMPACT=0) keeps all three planes, e.g. for poa_batch_fetch_planes.
-    const bool want_full = cfg && (cfg->flags & POA_CFG_FULL_PLANES);
-    bool compact = narrow && !want_full;
-    if (const int* cv = T.ptr(POA_TUNE_COMPACT)) { if ((*cv) == 0) compact = false; }
-    bool packed = true;  // packed-u16 arithmetic kernel for the compact layout (POA_PACKED=0: scalar u32 arithmetic)
-    if (const int* pv2 = T.ptr(POA_TUNE_PACKED)) packed = (*pv2) != 0;
-    // Scores beyond u16 (a read against a much longer graph, Global): store every cell relative to the depth potential
-    // e * (row_depth - column) (FlatGraph::row_depth).  All moves keep non-negative costs there, so the saturation argument
-    // of u16_cells_suffice holds for the relative values, and the largest one on an optimal path is the end cell's:
-    //     S* - e * (shortest path nodes - L)  <=  ub - e * min_path_nodes + e * L  =  2 * (o + e * L).
-    // Only the pairs-across-quads kernels (compact layout) implement it; POA_RELATIVE=0 keeps u32 planes, =1 forces it
-    // wherever the bound allows (A-B against the absolute encodings).
-    const uint64_t rel_ub = 2 * ((uint64_t)costs->gap_open + (uint64_t)costs->gap_extend * b->max_len);
-    bool relative = !narrow && rel_ub <= 65534 && !want_full && packed && !T.ptr(POA_TUNE_PLANES) && !T.ptr(POA_TUNE_COMPACT);
-    if (const int* rv = T.ptr(POA_TUNE_RELATIVE)) {
-        if ((*rv) == 0) relative = false;
-        else relative = rel_ub <= 65534 && !want_full && packed;
-    }
-    if (relative) { narrow = true; compact = true; }
-    // 2-byte elements let twice the queries share the workspace; the exact replay needs the u32 plan
-    const int plan = (narrow && mode == POA_MODE_DENSE && !b->plan16_same) ? (compact ? 2 : 1) : 0;
-    if (const int rc = run.begin(stream, b->plan[plan].chunks.size())) return rc;
+    const DenseRunPlan R = plan_dense_run(costs->gap_open, costs->gap_extend, b->max_len, fg.min_path_nodes, mode,
+                                          cfg && (cfg->flags & POA_CFG_FULL_PLANES), b->plan16_same, T);
+    if (const int rc = run.begin(stream, b->plan[R.plan].chunks.size())) return rc;
     b->prof_on = T.ptr(POA_TUNE_WS_PROF) != nullptr;
     b->last_mode = mode;
     b->two_piece = false;
-    set_layout(b, narrow, compact, relative);
+    set_layout(b, R.narrow, R.compact, R.relative);
     b->launches.clear();
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->pair_paired = 0; b->pair_single = 0;
-    b->active_plan = plan;
+    b->active_plan = R.plan;
     const poa_batch::Plan& PL = b->cur();
     if (b->n_queries == 0) return run.end_empty(true);
-    uint32_t spec_depth = 12;  // traceback speculation depth (lanes per round) of the full-plane layouts; the compact one: see the launch below
-    if (const int* sv = T.ptr(POA_TUNE_TB_DEPTH)) { const int v = (*sv); if (v >= 1 && v <= 64) spec_depth = (uint32_t)v; }
-    int tb_group = 16;   // POA_TB_GROUP override (lanes per walk); default: chosen per chunk at the launch below
-    if (const int* gv = T.ptr(POA_TUNE_TB_GROUP)) { const int v = (*gv); if (v == 8 || v == 16 || v == 32 || v == 64) tb_group = v; }
-    bool fuse_tb = false;  // measured slower (16.0 vs 13.4 ms): tracing waves hold slots without HBM traffic. trace each query in the epilogue of its forward wave (POA_FUSE_TB=0: separate launch)
-    if (const int* fv = T.ptr(POA_TUNE_FUSE_TB)) fuse_tb = (*fv) != 0;
-    int quads_override = 0;
-    if (const int* ov = T.ptr(POA_TUNE_FWD_QUADS)) quads_override = (*ov);  // tuning override
-    // the banded one-strip kernel (poa_forward_band.hpp) wherever poa_forward_px_kernel<3> would run in a dense run; its bound
-    // needs e > 0.  POA_BAND=0 switches it off, POA_BAND_DELTA caps the band distance (tests)
-    bool want_band = mode == POA_MODE_DENSE && costs->gap_extend > 0;
-    if (const int* bv = T.ptr(POA_TUNE_BAND)) want_band = want_band && (*bv) != 0;
-    uint32_t band_cap = 0xFFFFFFFFu;
-    if (const int* dv = T.ptr(POA_TUNE_BAND_DELTA)) band_cap = (*dv) > 0 ? (uint32_t)(*dv) : 0u;
-    // two queries of one length per wave (poa_forward_band2_kernel): POA_BAND_PAIR=0 never, 1 whatever the count, else the rule
-    int band_pair = -1;
-    if (const int* pv = T.ptr(POA_TUNE_BAND_PAIR)) band_pair = (*pv) != 0 ? 1 : 0;
-    if (want_band && !PL.chunks.empty()) {   // one fallback counter per chunk, cleared per run
+    if (R.want_band && !PL.chunks.empty()) {   // one fallback counter per chunk, cleared per run
         if (b->d_band_count.n < PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(PL.chunks.size()));
         HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, PL.chunks.size() * 4, stream));
     }
     for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
         const auto& ch = PL.chunks[ci];
+        uint32_t max_pitch = 0;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) max_pitch = std::max(max_pitch, b->h_pitch[i]);
+        const DenseChunkPlan C = plan_dense_chunk(R, ch.count, max_pitch, T);
         TbParams tp;
         tp.rows = b->d_rows.p; tp.pred_rows = b->d_pred_rows.p; tp.n_rows = fg.n;
         tp.start_row = fg.start_row; tp.end_row = fg.end_row;
@@ -1185,9 +1466,9 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         tp.planes = b->d_planes.p; tp.scratch_off = b->d_scratch_off.p; tp.scratch = b->d_scratch.p;
         tp.score = b->d_score.p; tp.flags = b->d_flags.p; tp.n_pairs = b->d_npairs.p;
         tp.cost_x = costs->mismatch; tp.cost_o = costs->gap_open; tp.cost_e = costs->gap_extend;
-        tp.spec_depth = spec_depth;
-        tp.exact_pass = 0; tp.ex_status = nullptr; tp.ex_end = nullptr; tp.code_fmt = 0;
-        tp.row_depth = relative ? b->d_row_depth.p : nullptr;
+        tp.spec_depth = R.spec_depth;
+        tp.exact_pass = 0; tp.ex_status = nullptr; tp.ex_end = nullptr; tp.code_fmt = C.v[4];
+        tp.row_depth = R.relative ? b->d_row_depth.p : nullptr;
         tp.d_slot = fg.d_slot.empty() ? nullptr : b->d_dslot.p; tp.pred_dslot = fg.d_slot.empty() ? nullptr : b->d_pred_dslot.p;
         FwdParams fp;
         fp.rows = b->d_rows.p; fp.pred_rows = b->d_pred_rows.p; fp.n_rows = fg.n;
@@ -1197,411 +1478,28 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         fp.cost_x = costs->mismatch; fp.cost_oe = (uint32_t)costs->gap_open + costs->gap_extend; fp.cost_e = costs->gap_extend;
         // the same recurrences under the depth potential: deletions lose the e the potential already charges per row,
         // insertions pay it twice, every predecessor edge adds e * pred_k
-        fp.cost_de = relative ? 0u : fp.cost_e;
-        fp.cost_doe = relative ? (uint32_t)costs->gap_open : fp.cost_oe;
-        fp.cost_ie = relative ? 2u * fp.cost_e : fp.cost_e;
-        fp.cost_ioe = relative ? fp.cost_oe + fp.cost_e : fp.cost_oe;
-        fp.pred_k = relative ? b->d_pred_k.p : nullptr;
+        fp.cost_de = R.relative ? 0u : fp.cost_e;
+        fp.cost_doe = R.relative ? (uint32_t)costs->gap_open : fp.cost_oe;
+        fp.cost_ie = R.relative ? 2u * fp.cost_e : fp.cost_e;
+        fp.cost_ioe = R.relative ? fp.cost_oe + fp.cost_e : fp.cost_oe;
+        fp.pred_k = R.relative ? b->d_pred_k.p : nullptr;
         fp.d_slot = fg.d_slot.empty() ? nullptr : b->d_dslot.p; fp.pred_dslot = fg.d_slot.empty() ? nullptr : b->d_pred_dslot.p;
         fp.pipeline_error = b->d_pipeline_error.p;
-        const uint32_t blocks = (ch.count + 3) / 4;
-#define LAUNCH_FWD(QQ, TT)                                                                                              \
-    do {                                                                                                               \
-        if (fuse_tb) hipLaunchKernelGGL((poa_forward_kernel<QQ, TT, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);  \
-        else hipLaunchKernelGGL((poa_forward_kernel<QQ, TT, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);         \
-        lk = POA_KERNEL_FORWARD; lq = QQ; lfuse = fuse_tb;                                                              \
-    } while (0)
-        // the launch record of this chunk (poa_batch_last_launch): kernel family, quads, fused walk, multi-wave, waves per workgroup
-        uint32_t lk = POA_KERNEL_NONE, lq = 0, lwaves = 4;
-        bool lfuse = false, lmw = false;
-        uint32_t max_pitch = 0;
-        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) max_pitch = std::max(max_pitch, b->h_pitch[i]);
-        // strip width: as narrow as the widest plane row of the chunk allows, at most 1024 columns
-        if (narrow) {
-            uint32_t quads = max_pitch <= 512 ? 1 : 2;  // 512 columns per quad (8 x u16 per lane)
-            if (quads_override == 1 || quads_override == 2) quads = (uint32_t)quads_override;
-            if (relative) quads = 2;  // the relative encoding lives in the pairs-across-quads kernels only
-            if (compact && packed) {
-                // queries longer than one strip: one workgroup per query, its strips pipelined over the waves (MW)
-                bool mw = max_pitch > 512 * quads;
-                if (const int* mv = T.ptr(POA_TUNE_MW)) mw = mw && ((*mv) != 0 || relative);
-                bool px = max_pitch <= 1024 && quads == 2 && (!fuse_tb || relative);  // one strip of up to 1024 columns: the pairs-across-quads kernel
-                if (const int* xv = T.ptr(POA_TUNE_PX)) px = (px && (*xv) != 0) || (px && relative);
-                if (px) {
-                    // scores below 0x3FFF (same bound as for u16, one power lower): two flags ride in the stored M value
-                    // (below 0x0FFF: all four; POA_MF = 0 / 1 / 2 caps the variant for A-B runs).  Wherever flags fit beside the
-                    // score the engine takes variant 3: the two Match-state flags in the score and no gap-state flags at all (the
-                    // traceback derives them, poa_tb_derive.hpp) - the forward pass is instruction-issue bound and they are a
-                    // fifth of its instructions
-                    int mf = relative ? 0 : (ub <= 4094 ? 2 : (ub <= 16382 ? 1 : 0));
-                    if (const int* fv2 = T.ptr(POA_TUNE_MF)) mf = (*fv2) == 3 ? (mf >= 1 ? 3 : 0) : std::min(mf, std::max(0, (*fv2)));
-                    else if (mf >= 1) mf = 3;
-                    tp.code_fmt = mf == 3 ? 4u : (mf == 2 ? 3u : (mf == 1 ? 2u : 1u));
-                    b->dense_derived_gaps = mf == 3;
-                    if (mf == 3 && want_band && max_pitch > 512) {
-                        // the banded pass, then the full pass (the same kernel with eight registers per row array and one window of
-                        // 1024 columns) over the queries it could not certify: the grid is sized for the chunk and the waves past the
-                        // device-side count return at once, so the host never waits for the count
-                        int rc = prepare_band(b);
-                        if (rc != POA_OK) return rc;
-                        BandParams bp;
-                        bp.cls = b->d_band_cls.p; bp.cls_d = b->d_band_d.p; bp.cls_base = b->d_band_base.p; bp.n_seg = b->band_n_seg;
-                        bp.d_cap = band_cap; bp.list = b->d_band_list.p; bp.count = b->d_band_count.p + ci;
-                        bp.order = nullptr;
-                        uint32_t n_pairs = 0;
-                        if (band_pair != 0) {
-                            rc = prepare_band_pairs(b);
-                            if (rc != POA_OK) return rc;
-                            n_pairs = b->h_band_npair[ci];
-                            if (band_pair < 0 && !band_pair_rule(2 * n_pairs)) n_pairs = 0;
-                        }
-                        if (n_pairs) {
-                            // the pairs, then the singles one per wave: grids sized on the host, nothing read back
-                            const uint32_t n_single = ch.count - 2 * n_pairs;
-                            FwdParams fq = fp;
-                            BandParams bq = bp;
-                            fq.n_queries = n_pairs; bq.order = b->d_band_order.p + ch.first;
-                            hipLaunchKernelGGL(poa_forward_band2_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, stream, fq, bq);
-                            if (n_single) {
-                                HIP_TRY(hipGetLastError());
-                                fq.n_queries = n_single; bq.order = b->d_band_order.p + ch.first + 2 * n_pairs;
-                                hipLaunchKernelGGL((poa_forward_band_kernel<false, true>), dim3((n_single + 3) / 4), dim3(256), 0, stream, fq, bq);
-                            }
-                            b->pair_paired += 2 * n_pairs; b->pair_single += n_single;
-                        } else {
-                            hipLaunchKernelGGL(poa_forward_band_kernel<false>, dim3(blocks), dim3(256), 0, stream, fp, bp);
-                            b->pair_single += ch.count;
-                        }
-                        HIP_TRY(hipGetLastError());
-                        hipLaunchKernelGGL(poa_forward_band_kernel<true>, dim3(blocks), dim3(256), 0, stream, fp, bp);
-                        uint32_t min_d = 0xFFFFFFFFu;
-                        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) min_d = std::min(min_d, std::min(b->h_band_d[b->h_band_cls[i]], band_cap));
-                        b->band_min_d = b->band_used ? std::min(b->band_min_d, min_d) : min_d;
-                        b->band_used = true; b->band_queries += ch.count; b->band_chunks = (uint32_t)ci + 1;
-                        lk = POA_KERNEL_BAND;
-                    } else if (mf == 3) hipLaunchKernelGGL(poa_forward_px_kernel<3>, dim3(blocks), dim3(256), 0, stream, fp);
-                    else if (mf == 2) hipLaunchKernelGGL(poa_forward_px_kernel<2>, dim3(blocks), dim3(256), 0, stream, fp);
-                    else if (mf == 1) hipLaunchKernelGGL(poa_forward_px_kernel<1>, dim3(blocks), dim3(256), 0, stream, fp);
-                    else hipLaunchKernelGGL(poa_forward_px_kernel<0>, dim3(blocks), dim3(256), 0, stream, fp);
-                    if (lk == POA_KERNEL_NONE) lk = POA_KERNEL_PX;
-                    lq = 2;
-                } else if (mw && (relative || pxmw_ok(T, ch.count, max_pitch))) {
-                    // pairs-across-quads mapping, 1024-column strips pipelined over the waves of a workgroup
-                    tp.code_fmt = 1;
-                    const uint32_t waves = mw_waves((max_pitch + 1023) / 1024);
-                    hipLaunchKernelGGL(poa_forward_pxmw_kernel, dim3(ch.count), dim3(64 * waves), 0, stream, fp);
-                    lk = POA_KERNEL_PXMW; lq = 2; lmw = true; lwaves = waves;
-                } else if (mw) {
-                    // narrow strips (more waves) until the chunk alone fills the chip
-                    if (!quads_override) quads = ((uint64_t)ch.count * ((max_pitch + 1023) / 1024) >= 8192) ? 2 : 1;
-                    const uint32_t strips = (max_pitch + 512 * quads - 1) / (512 * quads);
-                    const uint32_t waves = mw_waves(strips);
-                    if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
-                    else hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
-                    lk = POA_KERNEL_PACKED; lq = quads; lmw = true; lwaves = waves;
-                } else if (quads == 1) {
-                    if (fuse_tb) hipLaunchKernelGGL((poa_forward_packed_kernel<1, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                    else hipLaunchKernelGGL((poa_forward_packed_kernel<1, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                    lk = POA_KERNEL_PACKED; lq = 1; lfuse = fuse_tb;
-                } else {
-                    if (fuse_tb) hipLaunchKernelGGL((poa_forward_packed_kernel<2, true, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                    else hipLaunchKernelGGL((poa_forward_packed_kernel<2, false, false>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                    lk = POA_KERNEL_PACKED; lq = 2; lfuse = fuse_tb;
-                }
-            } else if (compact) {
-                if (quads == 1) hipLaunchKernelGGL((poa_forward_kernel<1, uint16_t, false, true>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                else hipLaunchKernelGGL((poa_forward_kernel<2, uint16_t, false, true>), dim3(blocks), dim3(256), 0, stream, fp, tp);
-                lk = POA_KERNEL_FORWARD; lq = quads;
-            } else if (quads == 1) LAUNCH_FWD(1, uint16_t);
-            else LAUNCH_FWD(2, uint16_t);
-        } else {
-            uint32_t quads = max_pitch <= 256 ? 1 : (max_pitch <= 512 ? 2 : 4);  // 256 columns per quad (4 x u32 per lane)
-            if (quads_override == 1 || quads_override == 2 || quads_override == 4) quads = (uint32_t)quads_override;
-            bool mw = max_pitch > 1024;  // longer than the widest strip: pipeline the strips over the waves of a workgroup
-            if (const int* mv = T.ptr(POA_TUNE_MW)) mw = mw && (*mv) != 0;
-            if (mw) {
-                // 512-column strips (up to 16 waves per query) or 1024-column ones (up to 10): a query whose strips do not all
-                // fit one workgroup runs as several groups one after the other, and few long queries are latency bound per
-                // row (a 1024-column row costs ~1.4x a 512-column one), so take the variant with the least groups x row cost;
-                // the waves per workgroup are balanced over the groups
-                const uint32_t s2 = (max_pitch + 511) / 512, s4 = (max_pitch + 1023) / 1024;
-                const uint32_t g2 = (s2 + MW_MAX_WAVES - 1) / MW_MAX_WAVES, g4 = (s4 + 9) / 10;
-                bool wide = 14 * g4 < 10 * g2 || (uint64_t)ch.count * s4 >= 8192;
-                if (quads_override == 4) wide = true;
-                if (quads_override == 2) wide = false;
-                if (wide) {
-                    const uint32_t waves = (s4 + g4 - 1) / g4;
-                    hipLaunchKernelGGL((poa_forward_kernel<4, uint32_t, false, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
-                    lk = POA_KERNEL_FORWARD; lq = 4; lmw = true; lwaves = waves;
-                } else {
-                    const uint32_t waves = (s2 + g2 - 1) / g2;
-                    hipLaunchKernelGGL((poa_forward_kernel<2, uint32_t, false, false, true>), dim3(ch.count), dim3(64 * waves), 0, stream, fp, tp);
-                    lk = POA_KERNEL_FORWARD; lq = 2; lmw = true; lwaves = waves;
-                }
-            } else if (quads == 1) LAUNCH_FWD(1, uint32_t);
-            else if (quads == 2) LAUNCH_FWD(2, uint32_t);
-            else LAUNCH_FWD(4, uint32_t);
-        }
+        if (C.mf >= 0) b->dense_derived_gaps = C.mf == 3;   // the px branch: the gap-state flags are the traceback's to derive
+        if (C.band) { if (const int rc = launch_band(b, ci, R, fp, stream)) return rc; }
+        else launch_forward(R, C, fp, tp, stream);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
 
-        uint32_t ltb = 0, ldepth = tp.spec_depth;   // lanes per walk of the separate traceback launch (0: none), speculation depth
-        if (!(fuse_tb && !relative && max_pitch <= 1024 && (!compact || packed))) {
-            // Lanes per walk: as many as keep the launch within ~6 000 waves (what the chip holds at this kernel's occupancy
-            // with room to spare), and a speculation depth to match.  Measured on config 2 after the insertion-run speculation
-            // (ms per batch; 64 lanes x depth 32 / 32 x 32 / 16 x 16): 1 024 walks 0.44 / 0.57 / 0.74, 4 096 walks 0.68 / 0.77 /
-            // 0.84, 10 000 walks 1.22 / 0.97 / 1.05, 20 000 walks 2.22 / 1.79 / 1.35.
-            int tbg = ch.count <= 6144 ? 64 : (ch.count <= 12288 ? 32 : 16);
-            if (T.ptr(POA_TUNE_TB_GROUP)) tbg = tb_group;
-            TbParams tpg = tp;
-            if (!T.ptr(POA_TUNE_TB_DEPTH)) tpg.spec_depth = tbg == 16 ? 16u : (compact ? 32u : spec_depth);
-            if (compact && tbg == 16) {
-                hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 16>), dim3((ch.count + 15) / 16), dim3(256), 0, stream, tpg);
-            } else if (compact && tbg == 32) {
-                hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 32>), dim3((ch.count + 7) / 8), dim3(256), 0, stream, tpg);
-            } else if (compact && tbg == 8) {
-                hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 8>), dim3((ch.count + 31) / 32), dim3(256), 0, stream, tpg);
-            }
-            else if (compact) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tpg);
-            else if (narrow) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
-            else hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
+        if (C.separate_tb) {
+            launch_traceback(R, C, tp, stream);
             HIP_TRY(hipGetLastError());
-            ltb = compact ? (uint32_t)tbg : 64u;
-            ldepth = compact ? tpg.spec_depth : tp.spec_depth;
         }
-        if (mode == POA_MODE_DENSE)
-            b->launches.push_back({{lk, lq, (lfuse ? POA_LAUNCH_FUSE : 0u) | (lmw ? POA_LAUNCH_MW : 0u), lwaves, tp.code_fmt, ltb, ldepth, ch.count}});
+        if (mode == POA_MODE_DENSE) b->launches.push_back(C);
         if (const int rc = run.mark()) return rc;
 
         if (mode != POA_MODE_DENSE) {
-            // exact replay of the reference's search on the (re-initialised, u32) planes of this chunk
-            const uint32_t hybrid = mode == POA_MODE_HYBRID ? 1u : 0u;
-            HIP_TRY(hipMemsetAsync(b->d_ex_status.p + ch.first, 0xFF, (size_t)ch.count * 4, stream));
-            HIP_TRY(hipMemsetAsync(b->d_ex_counters.p + 4 * (size_t)ch.first, 0, (size_t)ch.count * 16, stream));
-            hipLaunchKernelGGL(poa_fill_planes_kernel, dim3(64, ch.count), dim3(256), 0, stream, b->d_planes.p, PL.d_off.p,
-                               b->d_pitch.p, fg.n, ch.first, hybrid, b->d_flags.p);
-            HIP_TRY(hipGetLastError());
-            if (fg.n_exit) {
-                HIP_TRY(hipMemsetAsync(b->d_ex_reached.p, 0, (size_t)ch.count * fg.n_exit * b->ex_wpn * 8, stream));
-                HIP_TRY(hipMemsetAsync(b->d_ex_rsum.p, 0, (size_t)ch.count * fg.n_exit * b->ex_swpn * 8, stream));
-            }
-            HIP_TRY(hipMemsetAsync(b->d_ex_head.p, 0xFF, (size_t)ch.count * 3 * b->ex_n_prio * 4, stream));
-            ExactParams ep;
-            ep.G = ExactGraph{fg.n, fg.start_row, fg.end_row, b->d_ex_sym.p, b->d_succ_off.p, b->d_succ_rows.p, b->d_dist_min.p,
-                              b->d_dist_max.p, b->d_exit_idx.p, fg.n_exit, b->d_nbm_off.p, b->d_nbm.p, b->d_node_row.p, b->d_sp_to_end.p,
-                              fg.row_rec.empty() ? nullptr : b->d_ex_rec.p};
-            ep.first_query = ch.first; ep.n_queries = ch.count; ep.hybrid = hybrid; ep.dense_flags = b->d_flags.p;
-            ep.qseq = b->d_qseq.p; ep.qoff = b->d_qoff.p; ep.pitch = b->d_pitch.p; ep.plane_off = PL.d_off.p;
-            ep.planes = b->d_planes.p;
-            ep.reached = b->d_ex_reached.p; ep.rsum = b->d_ex_rsum.p; ep.wpn = b->ex_wpn; ep.swpn = b->ex_swpn;
-            ep.head = b->d_ex_head.p; ep.n_prio = b->ex_n_prio; ep.pool = b->d_ex_pool.p; ep.pool_cap = b->ex_pool_cap;
-            ep.stack = b->d_ex_stack.p; ep.stack_cap = b->ex_stack_cap;
-            ep.C = ExactCosts{costs->mismatch, costs->gap_open, costs->gap_extend, cfg ? cfg->heuristic : POA_HEURISTIC_MINGAP,
-                              cfg ? cfg->pruning : 1u, 0, 0, 0, 0, 0, 0};
-            if (ends_free) {
-                ep.C.ends_free = 1;
-                ep.C.qfe_kind = cfg->qry_free_end.kind; ep.C.qfe_val = cfg->qry_free_end.value;
-                ep.C.gfb_kind = cfg->graph_free_begin.kind;
-                ep.C.gfe_kind = cfg->graph_free_end.kind; ep.C.gfe_val = cfg->graph_free_end.value;
-            }
-            ep.status = b->d_ex_status.p;
-            ep.end_cell = b->d_ex_end.p;
-            ep.n_succ = (uint32_t)fg.succ_rows.size(); ep.n_nbm = (uint32_t)fg.nbm.size();
-            // Wave-per-query search (poa_wsearch.hpp) unless its descriptor ring cannot hold the priorities that are live
-            // at once: one pop pushes at most max(x, o+e) above its own priority plus what the heuristic can jump along
-            // one edge and a state change (o), and the greedy extension walks that jump once more.
-            // live priority range: a pop at priority f pushes at most max(x, o+e) + o + e * (spread + 3) above f, where
-            // spread = max over nodes of dist_max - dist_min (the heuristic's gap length grows by at most that along any
-            // greedy extension: heuristic.rs:70-102)
-            const uint32_t win = b->ex_win;
-            int lds_cap = 64 * 1024;
-            (void)hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device);
-            const uint32_t graph_lds = exact_lds_bytes(fg.n, ep.n_succ, ep.n_nbm);
-            const int* impl = T.ptr(POA_TUNE_EXACT_IMPL);   // 1 lane, 2 wave, 3 flat
-            const bool wave_search = !(impl && *impl == 1) && win <= b->ex_n_prio;
-            // "flat": the parallel-step kernel (poa_fsearch.hpp) — bit-identical like the others, not the fastest yet
-            const bool par_search = wave_search && impl && *impl == 3;
-            if (par_search) {
-                // the next entries in pop order expanded at once, one per lane, several queries per wave (poa_fsearch.hpp)
-                FSearchParams pp;
-                pp.E = ep;
-                pp.chunks = reinterpret_cast<ExU4*>(b->d_ex_pool.p);
-                pp.chunk_cap = b->ex_pool_cap / BQ_CHUNK;
-                if (const int* cv = T.ptr(POA_TUNE_WS_CHUNK_CAP)) { const int v = (*cv); if (v >= 1 && (uint32_t)v < pp.chunk_cap) pp.chunk_cap = (uint32_t)v; }
-                pp.win = win;
-                pp.counters = b->d_ex_counters.p;
-                pp.max_lanes = 63;   // (capped at the group's lanes below)
-                if (const int* lv = T.ptr(POA_TUNE_PS_LANES)) { const int v = (*lv); if (v >= 1 && v <= 63) pp.max_lanes = (uint32_t)v; }
-                pp.prof = nullptr;
-                if (T.ptr(POA_TUNE_WS_PROF)) pp.prof = b->d_ex_prof.p;
-                // Lanes per query: a step commits a dozen lanes on the benchmark's reads, and the kernel waits for memory more than it
-                // issues — so four searches share a wave (16 lanes each), all stepping through one instruction stream.
-                pp.lean = (!fg.row_rec.empty() && !ends_free) ? 1u : 0u;
-                if (const int* lv = T.ptr(POA_TUNE_PS_LEAN)) pp.lean = (pp.lean && (*lv) != 0) ? 1u : 0u;
-                const uint32_t group = pp.lean ? 8u : 16u;   // (the group sizes poa_fsearch.hpp is built for)
-                const uint32_t qpw = 64 / group;
-                pp.group = group;
-                if (pp.max_lanes > group) pp.max_lanes = group;
-                // LDS of a block: the staged graph (shared by its waves) + per wave the descriptor rings of its queries and the
-                // logs / read sets / conflict tables of the step.  As many waves per block as fit 160 KB, at most 8 (two per SIMD:
-                // the kernel keeps a lane's search state in ~250 registers).
-                const uint64_t lds_budget = std::min<uint64_t>((uint64_t)lds_cap, 160u * 1024u);
-                const uint64_t ring_b = ((uint64_t)qpw * 3 * win * 4 + 15) & ~15ull;
-                // the lean step reads one 32-byte record per row: those are staged (the arrays of the generic code, which it
-                // falls back to for a row in a thousand, stay in global memory); without records the generic code runs in log mode
-                const uint64_t rec_b = pp.lean ? ((sizeof(FlatGraph::RowRec) * (uint64_t)fg.n + 15) & ~15ull) : 0;
-                const uint64_t stage_b = pp.lean ? rec_b : graph_lds;
-                bool ring_lds = ring_b + ps_lds_bytes() <= lds_budget && !T.ptr(POA_TUNE_WS_RING_GLOBAL);
-                uint64_t per_wave = (ring_lds ? ring_b : 0) + ps_lds_bytes();
-                bool stage = stage_b + per_wave <= lds_budget;
-                if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) stage = stage && (*gv) != 0;
-                uint32_t wpb = (uint32_t)std::min<uint64_t>(8, (lds_budget - (stage ? stage_b : 0)) / per_wave);
-                if (const int* wv = T.ptr(POA_TUNE_WS_WAVES)) { const int v = (*wv); if (v >= 1 && (uint32_t)v <= wpb) wpb = (uint32_t)v; }
-                if (wpb < 1) return fail(POA_ERR_UNSUPPORTED, "exact replay: the step's logs do not fit the LDS");
-                pp.graph_lds = (stage && !pp.lean) ? graph_lds : 0;
-                pp.rec_lds = (stage && pp.lean) ? (uint32_t)rec_b : 0;
-                pp.waves_per_block = wpb;
-                pp.ring_global = ring_lds ? nullptr : b->d_ex_head.p;   // [slots * 3 * ex_n_prio] holds slots * 3 * win
-                const uint32_t lds_bytes = pp.graph_lds + pp.rec_lds + (uint32_t)(wpb * per_wave);
-                const void* kfn = pp.lean ? reinterpret_cast<const void*>(poa_fsearch_lean_kernel) : reinterpret_cast<const void*>(poa_fsearch_kernel);
-                if (lds_bytes > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                const uint32_t per_block = wpb * qpw;
-                uint32_t n_blocks = (ch.count + per_block - 1) / per_block;
-                pp.work_counter = nullptr; pp.order = nullptr;
-                int per_cu = 1, cus = 256;
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, (int)(64 * wpb), lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
-                const uint32_t resident = (uint32_t)cus * (uint32_t)per_cu;
-                if (n_blocks > resident && !T.ptr(POA_TUNE_WS_STATIC)) {
-                    // persistent waves, longest expected search first (see the wave search below)
-                    std::vector<uint32_t> sc(ch.count), ord(ch.count);
-                    HIP_TRY(hipMemcpyAsync(sc.data(), b->d_score.p + ch.first, (size_t)ch.count * 4, hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    for (uint32_t i = 0; i < ch.count; ++i) ord[i] = i;
-                    std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t c2) { return sc[a] > sc[c2]; });
-                    HIP_TRY(b->d_ex_order.alloc(ch.count + 1));
-                    HIP_TRY(hipMemcpyAsync(b->d_ex_order.p + 1, ord.data(), (size_t)ch.count * 4, hipMemcpyHostToDevice, stream));
-                    HIP_TRY(hipMemsetAsync(b->d_ex_order.p, 0, 4, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));   // `ord` is a host temporary
-                    pp.work_counter = b->d_ex_order.p; pp.order = b->d_ex_order.p + 1;
-                    n_blocks = resident;
-                }
-                HIP_TRY(b->d_ex_logs.alloc((size_t)n_blocks * wpb * ps_scratch_words()));
-                pp.scratch = b->d_ex_logs.p;
-                if (pp.lean) hipLaunchKernelGGL(poa_fsearch_lean_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, pp);
-                else hipLaunchKernelGGL(poa_fsearch_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, pp);
-            } else if (wave_search) {
-                WSearchParams wp;
-                wp.E = ep;
-                wp.chunks = reinterpret_cast<ExU4*>(b->d_ex_pool.p);
-                wp.chunk_cap = b->ex_pool_cap / BQ_CHUNK;
-                if (const int* cv = T.ptr(POA_TUNE_WS_CHUNK_CAP)) { const int v = (*cv); if (v >= 1 && (uint32_t)v < wp.chunk_cap) wp.chunk_cap = (uint32_t)v; }
-                wp.win = win;
-                wp.counters = b->d_ex_counters.p;
-                wp.max_lanes = 32;   // entries tested per step at most: runs of stale / pruned entries are short (1.85 pops per step)
-                if (const int* lv = T.ptr(POA_TUNE_WS_LANES)) { const int v = (*lv); if (v >= 1 && v <= 63) wp.max_lanes = (uint32_t)v; }
-                wp.adapt_lanes = 4;   // after an expansion the top of the stack is fresh: few entries tested; a run that used up its lanes widens
-                if (const int* av = T.ptr(POA_TUNE_WS_ADAPT)) { const int v = (*av); if (v >= 0 && v <= 63) wp.adapt_lanes = (uint32_t)v; }
-                wp.prof = nullptr;
-                if (T.ptr(POA_TUNE_WS_PROF)) wp.prof = b->d_ex_prof.p;  // per-phase cycle counts of the wave search (diagnostics)
-                // Lanes per query.  One query per wave (64) with persistent scheduling is the default.  Several queries per wave
-                // (POA_WS_GROUP = 32 / 16 / 8 lanes each, all through one instruction stream) issue fewer instructions in
-                // all but lose: the iteration takes the union of the groups' code paths and every wave waits for its slowest
-                // query (measured on config 2, 10 000 queries: 1.09 s at 64 persistent, 1.83 s at 64 static, 1.49 / 1.85 /
-                // 2.53 s at 32 / 16 / 8).  Waves per block: as many as share one staged copy of the graph, at most 16.
-                uint32_t group = 64;
-                if (const int* gv = T.ptr(POA_TUNE_WS_GROUP)) { const int v = (*gv); if (v == 8 || v == 16 || v == 32 || v == 64) group = (uint32_t)v; }
-                uint32_t wpb = 16;
-                if (const int* wv = T.ptr(POA_TUNE_WS_WAVES)) { const int v = (*wv); if (v >= 1 && v <= 16) wpb = (uint32_t)v; }
-                const uint64_t lds_budget = std::min<uint64_t>((uint64_t)lds_cap, 80u * 1024u);
-                bool ring_lds = false, stage = false;
-                // per-row records of the one-round-trip path (one query per wave: a block of 16 waves has the CU to itself)
-                uint32_t rec_lds = 0;
-                for (;;) {
-                    const uint64_t rb = (uint64_t)wpb * (64 / group) * win * 12;
-                    ring_lds = rb <= lds_budget && !T.ptr(POA_TUNE_WS_RING_GLOBAL);
-                    stage = graph_lds + (ring_lds ? rb : 0) <= lds_budget;
-                    if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) stage = stage && (*gv) != 0;
-                    if (group == 64 || (ring_lds && stage)) break;
-                    // several queries per wave need everything in LDS: fewer waves per block first, then fewer queries per wave
-                    if (wpb > 2 && !T.ptr(POA_TUNE_WS_WAVES)) wpb /= 2; else { group *= 2; if (!T.ptr(POA_TUNE_WS_WAVES)) wpb = 16; }
-                }
-                const uint64_t ring_bytes = ring_lds ? (uint64_t)wpb * (64 / group) * win * 12 : 0;
-                if (group == 64 && stage && ring_lds && !fg.row_rec.empty() && !(T.ptr(POA_TUNE_WS_REC) && *T.ptr(POA_TUNE_WS_REC) == 0)) {
-                    const uint64_t rb = (fg.row_rec.size() * sizeof(FlatGraph::RowRec) + 15) & ~15ull;
-                    if (graph_lds + rb + ring_bytes <= std::min<uint64_t>((uint64_t)lds_cap, 150u * 1024u)) rec_lds = (uint32_t)rb;
-                }
-                wp.rec_lds = rec_lds;
-                wp.graph_lds = stage ? graph_lds : 0;
-                wp.waves_per_block = wpb;
-                wp.group = group;
-                wp.ring_global = nullptr;
-                if (!ring_lds) wp.ring_global = b->d_ex_head.p;  // [slots * 3 * ex_n_prio] holds slots * 3 * win
-                const uint32_t lds_bytes = wp.graph_lds + wp.rec_lds + (uint32_t)ring_bytes;
-                const bool lds_all = wp.graph_lds && !wp.ring_global;   // (else the kernel whose search reads through generic pointers)
-                const void* kfn = group != 64 ? reinterpret_cast<const void*>(poa_wsearch_groups_kernel)
-                                              : (lds_all ? reinterpret_cast<const void*>(poa_wsearch_kernel) : reinterpret_cast<const void*>(poa_wsearch_global_kernel));
-                if (lds_bytes > 48u * 1024u)
-                    HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                const uint32_t per_block = wpb * (64 / group);
-                uint32_t n_blocks = (ch.count + per_block - 1) / per_block;
-                wp.work_counter = nullptr; wp.order = nullptr;
-                if (group == 64 && !T.ptr(POA_TUNE_WS_STATIC)) {
-                    // persistent waves: as many blocks as are resident at once; queries handed out longest-expected-search
-                    // first (by the dense pass's score: more edits, more buckets).  The sort needs the scores on the host:
-                    // one small copy behind the dense pass of this chunk.
-                    int per_cu = 1, cus = 256;
-                    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, (int)(64 * wpb), lds_bytes) != hipSuccess || per_cu < 1) per_cu = 1;
-                    const uint32_t resident = (uint32_t)cus * (uint32_t)per_cu;
-                    if (n_blocks > resident) {
-                        std::vector<uint32_t> sc(ch.count), ord(ch.count);
-                        HIP_TRY(hipMemcpyAsync(sc.data(), b->d_score.p + ch.first, (size_t)ch.count * 4, hipMemcpyDeviceToHost, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));
-                        for (uint32_t i = 0; i < ch.count; ++i) ord[i] = i;
-                        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t c2) { return sc[a] > sc[c2]; });
-                        HIP_TRY(b->d_ex_order.alloc(ch.count + 1));
-                        HIP_TRY(hipMemcpyAsync(b->d_ex_order.p + 1, ord.data(), (size_t)ch.count * 4, hipMemcpyHostToDevice, stream));
-                        HIP_TRY(hipMemsetAsync(b->d_ex_order.p, 0, 4, stream));
-                        HIP_TRY(hipStreamSynchronize(stream));   // `ord` is a host temporary
-                        wp.work_counter = b->d_ex_order.p; wp.order = b->d_ex_order.p + 1;
-                        n_blocks = resident;
-                    }
-                }
-                if (group != 64) hipLaunchKernelGGL(poa_wsearch_groups_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
-                else if (lds_all) hipLaunchKernelGGL(poa_wsearch_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
-                else hipLaunchKernelGGL(poa_wsearch_global_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
-            } else {
-            // active lanes per wave: one sequential search per lane.  Few lanes = little divergence but many
-            // waves; enough waves to fill the chip (~16 per CU) first, then more lanes per wave.
-            uint32_t lanes = (ch.count + 4095) / 4096;
-            if (lanes > 64) lanes = 64;
-            if (const int* lv = T.ptr(POA_TUNE_EXACT_LANES)) { const int v = (*lv); if (v >= 1 && v <= 64) lanes = (uint32_t)v; }
-            ep.lanes_per_wave = lanes;
-            // graph arrays in LDS when they fit beside three other blocks of the same CU (160 KB per CU)
-            uint32_t lds_bytes = exact_lds_bytes(fg.n, ep.n_succ, ep.n_nbm);
-            bool lds_graph = lds_bytes <= 160u * 1024u / 3u;
-            if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) lds_graph = lds_graph && (*gv) != 0;
-            if (lds_graph && lds_bytes > 48u * 1024u)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(poa_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            ep.lds_graph = lds_graph ? 1u : 0u;
-            if (lds_graph && !T.ptr(POA_TUNE_EXACT_LANES)) {
-                // all blocks resident at once (no tail round): LDS bounds the blocks per CU
-                int cus = 256;
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
-                const uint32_t per_cu = std::max(1u, std::min(8u, 160u * 1024u / std::max(lds_bytes, 1u)));
-                const uint32_t cap_waves = (uint32_t)cus * per_cu * (EXACT_BLOCK / 64);
-                lanes = std::min(64u, std::max(lanes, (ch.count + cap_waves - 1) / cap_waves));
-                ep.lanes_per_wave = lanes;
-            }
-            const uint32_t per_block = lanes * (EXACT_BLOCK / 64);
-            hipLaunchKernelGGL(poa_exact_kernel, dim3((ch.count + per_block - 1) / per_block), dim3(EXACT_BLOCK), lds_graph ? lds_bytes : 0, stream, ep);
-            }
-            HIP_TRY(hipGetLastError());
-            tp.exact_pass = 1; tp.ex_status = b->d_ex_status.p; tp.ex_end = b->d_ex_end.p; tp.row_depth = nullptr;
-            hipLaunchKernelGGL((poa_traceback_kernel<uint32_t, false>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, tp);
-            HIP_TRY(hipGetLastError());
-            b->narrow = false; b->compact = false; b->relative = false;  // the planes now hold the replayed u32 table
+            if (const int rc = replay_chunk(b, ch, costs, cfg, T, mode == POA_MODE_HYBRID ? 1u : 0u, ends_free, tp, stream)) return rc;
         }
         if (const int rc = run.mark()) return rc;
     }

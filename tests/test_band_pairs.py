@@ -25,7 +25,7 @@ PAIR = {"POA_BAND_PAIR": "1"}
 
 
 def _pairing(lengths, d_of):
-    """-> (pairs [(a, b)], singles [i]) of one chunk, as prepare_band_pairs of poa_engine.hip forms them"""
+    """-> (pairs [(a, b)], singles [i]) of one chunk, as prepare_band_pairs of poa_engine.hip forms them (launch_band launches them)"""
     waiting, pairs, singles = {}, [], []
     for i, L in enumerate(lengths):
         if d_of[L] < 4:

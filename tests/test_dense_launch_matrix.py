@@ -1,12 +1,15 @@
-"""The dense one-piece pass (poa_batch_run_ex in poasta_amd/csrc/poa_engine.hip) at every kernel its launcher can pick: the
-forward instantiations (poa_forward_kernel, poa_forward_packed_kernel, poa_forward_px_kernel, poa_forward_pxmw_kernel, the banded
-pair) and the traceback instantiations (u32 / u16 full planes, the compact one at 64 / 32 / 16 / 8 lanes per walk over every
-cell encoding).
+"""The dense one-piece pass (poa_batch_run_ex in poasta_amd/csrc/poa_engine.hip, which launches what plan_dense_run and
+plan_dense_chunk of poasta_amd/csrc/poa_dense_plan.cpp decide) at every kernel the rule can pick: the forward instantiations
+(poa_forward_kernel, poa_forward_packed_kernel, poa_forward_px_kernel, poa_forward_pxmw_kernel, the banded pair) and the
+traceback instantiations (u32 / u16 full planes, the compact one at 64 / 32 / 16 / 8 lanes per walk over every cell encoding).
 
-CPU: the launcher's rule restated in plain Python (`predict`), held against hand-computed shapes; a case table (`CASES`) and a
+CPU: the rule restated in plain Python (`predict`), held against hand-computed shapes; a case table (`CASES`) and a
 test that the table reaches every launch site of REQUIRED_SITES, every (cell encoding, lanes per walk) pair of REQUIRED_TB and
 the column edges of every kernel, so a trimmed table fails here rather than passing silently; the multi-wave hand-over graph
 is checked for the edges it exists for (32 and 33 rows back, hundreds of rows back, more rows than the LDS ring holds).
+The C++ rule itself, compiled for the host (tests/dense_plan_host), gives `predict`'s record, layout and band on the case
+table, on the hand-computed shapes and on a grid over costs, path lengths, pitches, counts and overrides; the same harness
+runs as a program of its own under the address and undefined-behaviour sanitizers.
 
 GPU: one test per case.  Overrides travel as keyword arguments of make_config (poa_config_t.tune), never through os.environ.
 What ran is read back with ResidentBatch.launches() (poa_batch_last_launch) and must equal `predict`; layout() and band_info()
@@ -22,14 +25,18 @@ column-group and strip width, so short rows run under the long kernel the chunk'
 The two `count * strips >= 8192` rules (packed multi-wave quads with pxmw refused; u32 `wide`) are checked by count from both
 sides, 4 095 and 4 096 two-strip queries, on a 7-row graph (30 M cells); the kernels they select are also reached by override
 (fwd_quads) on the larger graphs."""
+import ctypes as C
 import functools
 import os
+import subprocess
 from collections import namedtuple
 
 import numpy as np
 import pytest
 
 from poasta_amd import workloads as W
+from poasta_amd._lib import TUNE_KEYS
+from poasta_amd.aligner import LAUNCH_KERNELS
 from poasta_amd.graph import GraphBuilder, pack_queries
 
 from test_two_piece_shapes import min_path_nodes
@@ -46,7 +53,7 @@ def _ambient():
     return any("POA_" + k in os.environ for k in SELECTION_KEYS)
 
 
-# ---- the launcher's rule (poa_batch_run_ex), in plain Python ----------------------------------------------------------------
+# ---- the selection rule (plan_dense_run / plan_dense_chunk, poa_dense_plan.cpp), in plain Python ------------------------------
 def pitch_of(L):
     return (L + 1 + 63) // 64 * 64
 
@@ -56,17 +63,18 @@ def mw_waves(strips):
     return (strips + groups - 1) // groups
 
 
-def predict(g, lengths, costs, n_chunk_queries=None, tune=None, max_len=None, full_planes=False):
+def predict(g, lengths, costs, n_chunk_queries=None, tune=None, max_len=None, full_planes=False, mpn=None):
     """What poa_batch_run_ex launches for one chunk: `lengths` are the chunk's query lengths (their widest pitch decides),
     n_chunk_queries its query count (default len(lengths)), max_len the longest query of the whole BATCH (default
     max(lengths)): the score bound is the batch's.  costs = (mismatch, open, extend); tune = make_config's keyword overrides.
+    mpn: the nodes on the graph's shortest start -> end path, where there is no graph object (g is None).
     Returns the dict ResidentBatch.launches() gives for the chunk plus "layout" (ResidentBatch.layout()), "band" (the banded
     pair ran), "cells" ("u16" / "u32"), "strip" (columns per strip) and "strips" (of the widest query)."""
     _, o, e = costs
     T = dict(tune or {})
     count = len(lengths) if n_chunk_queries is None else n_chunk_queries
     max_len = max(lengths) if max_len is None else max_len
-    mpn = min_path_nodes(g)
+    mpn = min_path_nodes(g) if mpn is None else mpn
     ub = (o + e * max_len if max_len else 0) + (o + e * mpn if mpn else 0)
     narrow = ub <= 65534 and T.get("planes") != 32
     compact = narrow and not full_planes
@@ -169,6 +177,7 @@ def predict(g, lengths, costs, n_chunk_queries=None, tune=None, max_len=None, fu
     return out
 
 
+_predict_itself = predict       # (a test below runs test_selection_rule_restated with `predict` wrapped)
 LAUNCH_KEYS = ("kernel", "quads", "fuse", "mw", "waves", "code_fmt", "tb_lanes", "tb_depth", "queries")
 
 
@@ -177,7 +186,7 @@ def launch_of(pred):
 
 
 def site_of(p):
-    """the launch site of poa_batch_run_ex a prediction stands for, as the issue's list names them"""
+    """the launch of launch_forward / launch_band (poa_engine.hip) a prediction stands for, under the name it had as a site of poa_batch_run_ex"""
     if p["kernel"] == "forward":
         if p["mw"]:
             return "forward<%d,u32,MW>" % p["quads"]
@@ -459,7 +468,7 @@ def _predict(case):
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------
 def test_selection_rule_restated():
-    """`predict` on shapes worked out by hand from poa_batch_run_ex."""
+    """`predict` on shapes worked out by hand from plan_dense_run / plan_dense_chunk (poasta_amd/csrc/poa_dense_plan.cpp)."""
     g = _graph("lin")
     assert min_path_nodes(g) == 180
     assert [pitch_of(L) for L in (0, 62, 63, 64, 511, 512, 1023, 1024)] == [64, 64, 64, 128, 512, 576, 1024, 1088]
@@ -580,6 +589,140 @@ def test_case_table_reaches_every_launch_site():
     for name in ("fwd2-u16-fuse-strips", "fwd4-u32-fuse-strips", "packed2-fuse-strips"):
         p = _predict(BY_NAME[name])
         assert p["fuse"] and p["tb_lanes"] == 64, name
+
+
+# ---- CPU: the C++ rule (poasta_amd/csrc/poa_dense_plan.cpp) against `predict` ------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "poasta_amd", "csrc")
+HOST_SRC = os.path.join(ROOT, "tests", "dense_plan_host", "dense_plan_host.cpp")
+KERNEL_ID = {"forward": 1, "packed": 2, "px": 3, "pxmw": 4, "band": 5}                # POA_KERNEL_*
+LAYOUT_BIT = {"u16": 1, "compact": 2, "relative": 4, "derived_gaps": 8}               # POA_LAYOUT_*
+
+
+@pytest.fixture(scope="module")
+def plan_host():
+    """tests/dense_plan_host and the product's poa_dense_plan.cpp as a shared library, built with g++"""
+    out = os.path.join(ROOT, "tests", "dense_plan_host", "libdense_plan_host.so")
+    deps = [HOST_SRC, os.path.join(CSRC, "poa_dense_plan.cpp"), os.path.join(CSRC, "poa_dense_plan.hpp"), os.path.join(ROOT, "include", "poasta_amd.h")]
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, HOST_SRC, os.path.join(CSRC, "poa_dense_plan.cpp")])
+    X = C.CDLL(out)
+    X.dense_plan_host.argtypes = [C.c_uint32] * 3 + [C.c_uint64] * 2 + [C.c_uint32] * 3 + [C.c_void_p] + [C.c_uint32] * 2 + [C.c_void_p]
+    X.dense_plan_host.restype = None
+    return X
+
+
+def _tune_words(tune):
+    """poa_config_t.tune of make_config's keyword overrides: 0 not set, else value + 1"""
+    t = (C.c_uint32 * 32)()
+    for k, v in dict(tune).items():
+        t[TUNE_KEYS.index(k.upper())] = v + 1
+    return t
+
+
+def _words_of(pred):
+    """a prediction as dense_plan_host writes it: the eight launch words, the layout bits, the banded pair"""
+    return (KERNEL_ID[pred["kernel"]], pred["quads"], int(pred["fuse"]) | int(pred["mw"]) << 1, pred["waves"], pred["code_fmt"], pred["tb_lanes"],
+            pred["tb_depth"], pred["queries"], sum(LAYOUT_BIT[k] for k in pred["layout"]), int(pred["band"]))
+
+
+def _cxx_words(X, costs, max_len, mpn, count, max_pitch, tune_words, full_planes, plan16_same=False):
+    out = (C.c_uint32 * 11)()
+    X.dense_plan_host(costs[0], costs[1], costs[2], max_len, mpn, 0, int(full_planes), int(plan16_same), tune_words, count, max_pitch, out)
+    return tuple(out)
+
+
+def _assert_cxx_equals_predict(X, g, lengths, costs, n_chunk_queries=None, tune=None, max_len=None, full_planes=False, mpn=None):
+    """-> the prediction, after the C++ rule gave the same record, layout, band and chunk plan for the same chunk"""
+    pred = _predict_itself(g, lengths, costs, n_chunk_queries, tune, max_len, full_planes, mpn)
+    mpn = min_path_nodes(g) if mpn is None else mpn
+    args = (costs, max(lengths) if max_len is None else max_len, mpn, pred["queries"], max(pitch_of(L) for L in lengths), _tune_words(tune or {}), full_planes)
+    got = _cxx_words(X, *args)
+    assert got[:10] == _words_of(pred), (lengths, costs, n_chunk_queries, tune, max_len, full_planes, got, _words_of(pred))
+    assert launch_of(pred) == dict(zip(LAUNCH_KEYS, (LAUNCH_KERNELS[got[0]], got[1], bool(got[2] & 1), bool(got[2] & 2)) + got[3:8]))
+    # the chunk plan of the run: 2-byte elements (compact: 2, full planes: 1) unless the batch fits one chunk anyway
+    assert got[10] == ((2 if "compact" in pred["layout"] else 1) if pred["cells"] == "u16" else 0)
+    assert _cxx_words(X, *args, plan16_same=True)[:10] == got[:10] and _cxx_words(X, *args, plan16_same=True)[10] == 0
+    return pred
+
+
+def test_cxx_rule_equals_predict_on_cases_and_restated_shapes(plan_host, monkeypatch):
+    """plan_dense_run / plan_dense_chunk give launch_of(predict), predict's layout and band for every entry of CASES, and for
+    every shape of test_selection_rule_restated: that test runs once more with each predict() it makes held against the C++ rule"""
+    for c in CASES:
+        _assert_cxx_equals_predict(plan_host, _graph(c.kind), _lengths(c), c.costs, tune=dict(c.tune), full_planes=c.full)
+    seen = []
+
+    def both(*args, **kwargs):
+        seen.append(_assert_cxx_equals_predict(plan_host, *args, **kwargs))
+        return seen[-1]
+
+    monkeypatch.setitem(globals(), "predict", both)
+    try:
+        test_selection_rule_restated()
+    finally:
+        monkeypatch.undo()
+    assert len(seen) >= 47 and predict is _predict_itself       # (the 47 predictions that test made when this one was written)
+
+
+GRID_COSTS = ((6, 2), (6, 0), (0, 1), (6, 8), (6, 30), (6, 255))                     # (open, extend)
+GRID_MPN = (0, 1, 180, 5000)
+GRID_MAX_LEN = (None, 3000, 33000)                                                  # None: the chunk's own
+GRID_COLS = (1, 64, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2048, 2049, 8192, 8193, 10241)      # L + 1
+# The count axis of (1, 511, 512, 1023, 1024, 4095, 4096, 6144, 6145, 12288, 12289) took 40 s here, so it is halved: the last count
+# below each threshold (count * strips >= 1024 and >= 8192 at one and two strips, 6 144 and 12 288 walks) and, with the next
+# value, one above it; the counts right at the thresholds are among the shapes of test_selection_rule_restated.
+GRID_COUNT = (511, 1023, 4095, 6144, 12288, 12289)
+GRID_VALUES = dict(planes=(32,), compact=(0, 1), packed=(0, 1), px=(0, 1), mw=(0, 1), pxmw=(0, 1), band=(0, 1), relative=(0, 1), mf=(0, 1, 2, 3),
+                   fwd_quads=(1, 2, 4), fuse_tb=(1,), tb_group=(8, 16, 32, 64, 7), tb_depth=(1, 64, 65), band_delta=(0, 5))
+
+
+def _grid_tunes():
+    """no override, every key of SELECTION_KEYS alone at each value the rule distinguishes, every distinct tune of CASES"""
+    assert set(GRID_VALUES) == {k.lower() for k in SELECTION_KEYS}
+    tunes = [()] + [((k.lower(), v),) for k in SELECTION_KEYS for v in GRID_VALUES[k.lower()]]
+    for c in CASES:
+        if c.tune not in tunes:
+            tunes.append(c.tune)
+    return tunes
+
+
+def test_cxx_rule_equals_predict_on_the_grid(plan_host):
+    """The full product of GRID_* x full planes off / on x _grid_tunes(): the C++ record, layout and band equal predict's.  Only
+    the combinations whose batch max_len is below the chunk's own query are left out, and at least 90 % are compared."""
+    tunes = [(dict(t), _tune_words(t)) for t in _grid_tunes()]
+    total = compared = 0
+    for L1 in GRID_COLS:
+        L, pitch = L1 - 1, pitch_of(L1 - 1)
+        for costs in GRID_COSTS:
+            x_costs = (4,) + costs
+            for mpn in GRID_MPN:
+                for ml in GRID_MAX_LEN:
+                    n = len(GRID_COUNT) * 2 * len(tunes)
+                    total += n
+                    max_len = L if ml is None else ml
+                    if max_len < L:
+                        continue
+                    compared += n
+                    for count in GRID_COUNT:
+                        for full in (False, True):
+                            for tune, words in tunes:
+                                want = _words_of(predict(None, (L,), x_costs, count, tune, max_len, full, mpn))
+                                got = _cxx_words(plan_host, x_costs, max_len, mpn, count, pitch, words, full)
+                                assert got[:10] == want, (L, costs, mpn, max_len, count, full, tune, got, want)
+    assert total == len(GRID_COLS) * len(GRID_COSTS) * len(GRID_MPN) * len(GRID_MAX_LEN) * len(GRID_COUNT) * 2 * len(tunes)
+    assert compared >= 0.9 * total, (compared, total)
+
+
+def test_dense_plan_host_under_sanitizers(tmp_path):
+    """tests/dense_plan_host as a program of its own, address and undefined-behaviour sanitizers on, on the CPU: every record of
+    its grid names a kernel, column groups the cell type has, 1 to 16 waves that cover the widest row, and lanes the traceback has."""
+    exe = os.path.join(str(tmp_path), "dense_plan_host")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe,
+                           HOST_SRC, os.path.join(CSRC, "poa_dense_plan.cpp")])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr.decode()
+    assert b"dense_plan_host ok" in r.stdout
 
 
 def test_handover_graph_has_the_edges_it_exists_for(oracle):
