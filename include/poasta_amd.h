@@ -573,7 +573,9 @@ int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int
 int poa_scoreset_run(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, void* stream);
 int poa_scoreset_run_2piece(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream);
 /* Capped runs — a score cap per pair and an exact early exit in the sweep (poa_scoreset_run_capped, poa_scoreset_run_2piece_capped,
- * poa_scoreset_fetch_swept) — are declared in poasta_amd_scoreset_cap.h, which this header includes at its end. */
+ * poa_scoreset_fetch_swept) — are declared in poasta_amd_scoreset_cap.h, which this header includes at its end; best-of runs
+ * — the cap is the query's best score so far, the run returns the winning pair per query (poa_scoreset_run_best,
+ * poa_scoreset_fetch_best, poa_score_best) — in poasta_amd_scoreset_best.h, included after it. */
 /* synchronises; score[n_pairs], flags[n_pairs] (may be NULL) in pair order */
 int poa_scoreset_fetch(poa_scoreset_t* s, uint32_t* score, uint32_t* flags, poa_stats_t* stats);
 int poa_scoreset_stats(poa_scoreset_t* s, poa_stats_t* stats);
@@ -594,4 +596,5 @@ int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 }
 #endif
 #include "poasta_amd_scoreset_cap.h"
+#include "poasta_amd_scoreset_best.h"
 #endif /* POASTA_AMD_H */

@@ -34,6 +34,16 @@ EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_creat
            "poa_graph_sweep_checks"]
 # every symbol include/poasta_amd_scoreset_cap.h declares (checked by tests/test_sweep_checks.py)
 EXPORTS_SCORESET_CAP = ["poa_scoreset_run_capped", "poa_scoreset_run_2piece_capped", "poa_scoreset_fetch_swept"]
+# every symbol include/poasta_amd_scoreset_best.h declares (checked by tests/test_scoreset_best_plan.py)
+EXPORTS_SCORESET_BEST = ["poa_scoreset_run_best", "poa_scoreset_run_2piece_best", "poa_scoreset_fetch_best", "poa_scoreset_device_best",
+                         "poa_score_best", "poa_score_best_2piece"]
+CFG_BEST_PAIR_ORDER = 2
+
+
+class PoaBest(C.Structure):
+    """poa_best_t: one record per query of a best-of score-set run."""
+    _fields_ = [("pair", C.c_uint32), ("score", C.c_uint32), ("flags", C.c_uint32), ("second_score", C.c_uint32),
+                ("n_within", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class PoaCosts2(C.Structure):
@@ -109,7 +119,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -168,6 +178,21 @@ def lib():
         L.poa_scoreset_run_2piece_capped.argtypes = [vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp, vp]
         L.poa_scoreset_fetch_swept.restype = C.c_int
         L.poa_scoreset_fetch_swept.argtypes = [vp, vp]
+    if hasattr(L, "poa_scoreset_run_best"):   # (as above)
+        L.poa_scoreset_run_best.restype = C.c_int
+        L.poa_scoreset_run_best.argtypes = [vp, C.POINTER(PoaCosts), C.POINTER(PoaConfig), C.c_uint32, vp, vp]
+        L.poa_scoreset_run_2piece_best.restype = C.c_int
+        L.poa_scoreset_run_2piece_best.argtypes = [vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), C.c_uint32, vp, vp]
+        L.poa_scoreset_fetch_best.restype = C.c_int
+        L.poa_scoreset_fetch_best.argtypes = [vp, vp]
+        L.poa_scoreset_device_best.restype = C.c_int
+        L.poa_scoreset_device_best.argtypes = [vp, C.POINTER(vp)]
+        L.poa_score_best.restype = C.c_int
+        L.poa_score_best.argtypes = [vp, C.c_uint32, C.POINTER(PoaCosts), C.POINTER(PoaConfig), C.c_uint32, vp, vp, C.c_uint64, vp, vp,
+                                     C.c_uint32, vp, vp, vp, vp, C.POINTER(PoaStats), C.c_int]
+        L.poa_score_best_2piece.restype = C.c_int
+        L.poa_score_best_2piece.argtypes = [vp, C.c_uint32, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), C.c_uint32, vp, vp, C.c_uint64, vp, vp,
+                                            C.c_uint32, vp, vp, vp, vp, C.POINTER(PoaStats), C.c_int]
     L.poa_graph_checkpoint_plan.restype = C.c_int
     L.poa_graph_checkpoint_plan.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.poa_graph_checkpoint_plan2.restype = C.c_int

@@ -628,16 +628,34 @@ class ScoreSet:
                                                   C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
 
-    def run(self, costs, stream=None, config=None, cap=None):
+    def run(self, costs, stream=None, config=None, cap=None, best=False, slack=0, limit=None):
         """Launch on `stream` without synchronising.  costs: GapAffine (poa_scoreset_run) or GapAffine2Piece
         (poa_scoreset_run_2piece); config: None or make_config("score", ...).
         cap: None, or a score cap — a scalar, or one value per pair in pair order; POA_NONE: no cap for that pair — for
         poa_scoreset_run_capped / _run_2piece_capped: a pair whose score is above its cap comes back as POA_NONE with
-        FLAG_CAPPED set, and its wave stops as soon as a row proves it."""
+        FLAG_CAPPED set, and its wave stops as soon as a row proves it.
+        best=True: a best-of run (poa_scoreset_run_best / _run_2piece_best) — every pair is capped by the best score its query
+        has reached so far plus `slack`, under `limit` (None, a scalar or one ceiling per query; POA_NONE: none); fetch_best
+        returns the winning pair of every query.  cap and best exclude each other."""
         c = costs._c()
         if config is None:
             config = make_config("score")   # (carries the POA_<NAME> overrides, if any are set)
         two_piece = isinstance(costs, GapAffine2Piece)
+        if best:
+            if cap is not None:
+                raise ValueError("run: cap and best=True exclude each other")
+            if not 0 <= int(slack) <= _lib.POA_NONE:
+                raise ValueError("slack: a u32")
+            lim = None
+            if limit is not None:
+                lim = np.full(self.n_queries, limit, np.uint32) if np.ndim(limit) == 0 else np.ascontiguousarray(limit, np.uint32)
+                if lim.shape != (self.n_queries,):
+                    raise ValueError("limit: a scalar or one value per query (%d), got shape %s" % (self.n_queries, lim.shape))
+                if self.n_queries == 0:
+                    lim = None
+            fn = _lib.lib().poa_scoreset_run_2piece_best if two_piece else _lib.lib().poa_scoreset_run_best
+            _lib.check(fn(self.handle, C.byref(c), C.byref(config), int(slack), _p(lim), C.c_void_p(stream or 0)))
+            return
         if cap is None:
             fn = _lib.lib().poa_scoreset_run_2piece if two_piece else _lib.lib().poa_scoreset_run
             _lib.check(fn(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
@@ -655,6 +673,14 @@ class ScoreSet:
         swept = np.zeros(max(self.n, 1), np.uint32)
         _lib.check(_lib.lib().poa_scoreset_fetch_swept(self.handle, _p(swept)))
         return swept[:self.n]
+
+    def fetch_best(self):
+        """Synchronise; the result of the last run, a best-of run (poa_scoreset_fetch_best): a dict of u32 arrays per query —
+        pair (POA_NONE: no pair qualifies), score, flags, second_score, n_within."""
+        rec = np.zeros((max(self.n_queries, 1), C.sizeof(_lib.PoaBest) // 4), np.uint32)
+        _lib.check(_lib.lib().poa_scoreset_fetch_best(self.handle, _p(rec)))
+        rec = rec[:self.n_queries]
+        return {k: np.ascontiguousarray(rec[:, i]) for i, k in enumerate(("pair", "score", "flags", "second_score", "n_within"))}
 
     def fetch(self):
         """Synchronise; (score, flags, stats): u32 arrays in pair order and the poa_stats_t of the runs since the last call."""
@@ -835,6 +861,52 @@ class PoastaAligner:
                       _p(score), _p(flags), C.byref(st), self.device))
         self.last_stats = st.as_dict()
         return score, flags
+
+    def assign(self, graphs, seqs, pairs=None, slack=0, max_score=None):
+        """Which graph does each query belong to: one best-of score-set run (ScoreSet.run(best=True)) over `pairs` ([n, 2]
+        (query, graph) indices; None: every query against every graph).  A query's candidates are tried in the order they are
+        listed, and the best score so far caps the rest: list the likeliest graph first.  max_score: None, a scalar or one
+        ceiling per query.  Returns a dict of arrays per query: graph (int64, -1: no candidate within max_score), pair, score,
+        flags, second_score (the runner-up if within `slack` of the winner, else POA_NONE), n_within."""
+        if self.aln_type != AlignmentType.Global:
+            raise ValueError("assign: AlignmentType.Global only")
+        ss = ScoreSet(graphs, seqs, pairs=pairs, device=self.device)
+        try:
+            ss.run(self.config.costs, config=make_config("score", self.config.heuristic), best=True, slack=slack, limit=max_score)
+            out = ss.fetch_best()
+            self.last_stats = ss.stats()
+        finally:
+            ss.close()
+        si = ss.input
+        won = out["pair"] != _lib.POA_NONE
+        pair = np.where(won, out["pair"], 0).astype(np.int64)
+        if si.pair_graph is None:
+            graph_of = pair % max(si.n_graphs, 1)
+        else:
+            graph_of = si.pair_graph[pair].astype(np.int64) if si.n else pair   # (no pairs: nobody won)
+        out["graph"] = np.where(won, graph_of, -1).astype(np.int64)
+        return out
+
+    def assign_and_align(self, graphs, seqs, pairs=None, max_score=None, want_pairs=True):
+        """assign, then the alignments of the assigned queries against their winning graphs in one align_multi run (the
+        two-piece form for a two-piece config).  Returns (assignment, BatchResult), the BatchResult in the order of seqs; a
+        query without a graph has no pairs, score POA_NONE and flags 0."""
+        a = self.assign(graphs, seqs, pairs=pairs, max_score=max_score)
+        n = len(seqs)
+        order = [np.flatnonzero(a["graph"] == g) for g in range(len(graphs))]
+        res = self.align_multi(graphs, [[seqs[int(i)] for i in idx] for idx in order], want_pairs=want_pairs)
+        score, flags = np.full(n, _lib.POA_NONE, np.uint32), np.zeros(n, np.uint32)
+        counts = np.zeros(n, np.uint64)
+        where = np.concatenate(order).astype(np.int64) if order else np.zeros(0, np.int64)   # where[k]: the query of res' k-th
+        score[where], flags[where] = res.score, res.flags
+        counts[where] = np.diff(res.pair_off.astype(np.int64)).astype(np.uint64)
+        pair_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+        out_pairs = None
+        if want_pairs:
+            out_pairs = np.zeros((int(pair_off[n]), 2), np.uint32)
+            for k, qi in enumerate(where):
+                out_pairs[int(pair_off[qi]):int(pair_off[qi + 1])] = res.pairs[int(res.pair_off[k]):int(res.pair_off[k + 1])]
+        return a, BatchResult(score, out_pairs, pair_off, flags, res.stats)
 
     def score_matrix(self, graphs, seqs, max_score=None):
         """The full queries x graphs matrix of scores, a [n_queries, n_graphs] u32 array (score_pairs with pairs=None).

@@ -2736,11 +2736,16 @@ struct poa_scoreset {
     // capped runs (poa_scoreset_run_capped): the device buffers and the pinned staging area are made by the set's first one
     std::vector<uint8_t> cut;          // [n_rows_total] SweepRows::cut of every graph, concatenated like the row tables
     DevBuf<uint32_t> d_cap, d_swept, d_check_rows;
-    uint32_t* h_stage = nullptr;       // pinned: [n_pairs] caps, then [n_rows_total] check rows
+    uint32_t* h_stage = nullptr;       // pinned: [max(n_pairs, n_queries)] caps or limits, then [n_rows_total] check rows
     hipEvent_t stage_done = nullptr;   // the copies out of h_stage of the last capped run
     bool stage_busy = false;
     uint32_t check_stride = 0;         // the stride d_check_rows was built for (0: not built)
     bool last_capped = false;          // the last run wrote d_swept
+    // best-of runs (poa_scoreset_run_best): made by the set's first one, with the capped runs' buffers if they are not there yet
+    DevBuf<unsigned long long> d_best_word;
+    DevBuf<uint32_t> d_limit, d_query_off, d_query_pairs, d_best_list[SS_N_VARIANTS];
+    DevBuf<ScoreSetBest> d_best;
+    bool last_best = false;            // the last run was a best-of run: d_best holds its result
     ~poa_scoreset() {
         if (h_stage) (void)hipHostFree(h_stage);
         if (stage_done) (void)hipEventDestroy(stage_done);
@@ -2770,26 +2775,31 @@ int scoreset_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32
     return POA_OK;
 }
 
+// words at the front of the staging area: the caps of a capped run or the limits of a best-of run
+size_t scoreset_stage_front(const poa_scoreset* s) { return std::max<size_t>(s->core.n_queries, s->plan.n_queries); }
+
 // what a capped run needs beyond the set's own buffers; made once
 int scoreset_cap_buffers(poa_scoreset* s) {
     const size_t n = s->core.n_queries, n_rows = s->plan.n_rows_total;
     if (!s->d_cap.p) HIP_TRY(s->d_cap.alloc(std::max<size_t>(n, 1)));
     if (!s->d_swept.p) HIP_TRY(s->d_swept.alloc(std::max<size_t>(n, 1)));
     if (!s->d_check_rows.p) HIP_TRY(s->d_check_rows.alloc(std::max<size_t>(n_rows, 1)));
-    if (!s->h_stage) HIP_TRY(hipHostMalloc((void**)&s->h_stage, (n + n_rows + 1) * sizeof(uint32_t), hipHostMallocDefault));
+    if (!s->h_stage) HIP_TRY(hipHostMalloc((void**)&s->h_stage, (scoreset_stage_front(s) + n_rows + 1) * sizeof(uint32_t), hipHostMallocDefault));
     if (!s->stage_done) HIP_TRY(hipEventCreateWithFlags(&s->stage_done, hipEventDisableTiming));
     return POA_OK;
 }
 
-// the caps of this run and, if the stride changed, the check rows: through the pinned staging area, on the run's stream
-int scoreset_cap_upload(poa_scoreset* s, const uint32_t* cap, uint32_t stride, hipStream_t stream) {
-    const size_t n = s->core.n_queries;
+// the caps of this run (dst = d_cap, n = n_pairs) or the limits of a best-of run (dst = d_limit, n = n_queries; cap null:
+// nothing to copy) and, if the stride changed, the check rows: through the pinned staging area, on the run's stream
+int scoreset_cap_upload(poa_scoreset* s, const uint32_t* cap, uint32_t* dst, size_t n, uint32_t stride, hipStream_t stream) {
     if (s->stage_busy) HIP_TRY(hipEventSynchronize(s->stage_done));   // the previous capped run's copies, not its kernels
     s->stage_busy = false;
-    std::memcpy(s->h_stage, cap, n * sizeof(uint32_t));
-    HIP_TRY(hipMemcpyAsync(s->d_cap.p, s->h_stage, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (cap && n) {
+        std::memcpy(s->h_stage, cap, n * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(dst, s->h_stage, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
     if (s->check_stride != stride && s->plan.n_rows_total) {
-        uint32_t* h_check = s->h_stage + n;
+        uint32_t* h_check = s->h_stage + scoreset_stage_front(s);
         std::fill(h_check, h_check + s->plan.n_rows_total, 0xFFFFFFFFu);
         std::vector<uint32_t> rows;
         for (uint32_t g = 0; g < s->plan.graphs.size(); ++g) {
@@ -2806,19 +2816,52 @@ int scoreset_cap_upload(poa_scoreset* s, const uint32_t* cap, uint32_t stride, h
     return POA_OK;
 }
 
+// what a best-of run needs beyond the capped runs' buffers; made once: the best words, limits and records per query, the
+// query-to-pairs lists and the best-of launch orders (host plan: build_scoreset_best_order), uploaded here
+int scoreset_best_buffers(poa_scoreset* s) {
+    if (s->d_best.p) return POA_OK;
+    ScoreSetPlan& pl = s->plan;
+    const size_t n = pl.n_pairs, nq = pl.n_queries;
+    build_scoreset_best_order(pl);
+    HIP_TRY(s->d_best_word.alloc(std::max<size_t>(nq, 1)));
+    HIP_TRY(s->d_limit.alloc(std::max<size_t>(nq, 1)));
+    HIP_TRY(s->d_query_off.alloc(nq + 1));
+    HIP_TRY(s->d_query_pairs.alloc(std::max<size_t>(n, 1)));
+    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(s->d_best_list[v].alloc(std::max<size_t>(n, 1)));
+    HIP_TRY(hipMemcpy(s->d_query_off.p, pl.query_off.data(), (nq + 1) * 4, hipMemcpyHostToDevice));
+    if (n) {
+        HIP_TRY(hipMemcpy(s->d_query_pairs.p, pl.query_pairs.data(), n * 4, hipMemcpyHostToDevice));
+        for (uint32_t v = 0; v < SS_N_VARIANTS; ++v)
+            HIP_TRY(hipMemcpy(s->d_best_list[v].p, pl.best_list[v].data(), n * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(s->d_best.alloc(std::max<size_t>(nq, 1)));   // last: its presence says the rest is there
+    return POA_OK;
+}
+
+struct ScoreSetBestArgs {
+    uint32_t slack;
+    const uint32_t* limit;   // [n_queries] or null
+};
+
 // one sweep launch per chunk and non-empty kernel class, nothing else.  Costs are 32-bit, as in run_sweep.
 // cap: nullptr, or the caps of a capped run in pair order (the capped kernels, which also write the swept-row counts).
+// best: nullptr, or the slack and limits of a best-of run (kernels of their own again, between an init and a finalize launch).
 int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cost_e, const poa_config_t* cfg, hipStream_t stream, const char* who,
-                 const uint32_t* cap = nullptr) {
+                 const uint32_t* cap = nullptr, const ScoreSetBestArgs* best = nullptr) {
     const TuneView T(cfg);
     poa_batch* b = &s->core;
     HIP_TRY(hipSetDevice(b->device));
     RunFrame run;
     if (const int rc = run.open(b, std::string(who) + ": call poa_scoreset_stats/fetch at least every 256 runs")) return rc;
     uint32_t cap_stride = SWEEP_CHECK_STRIDE;
-    if (cap) {
+    if (cap || best) {
         if (const int* sv = T.ptr(POA_TUNE_CAP_STRIDE)) { if ((*sv) > 0) cap_stride = (uint32_t)(*sv); }
         if (const int rc = scoreset_cap_buffers(s)) return rc;
+    }
+    if (best) {
+        try {
+            if (const int rc = scoreset_best_buffers(s)) return rc;
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
     }
     // u16 cells only if every graph's own bound (the longest query paired with it and its shortest path) allows them
     bool narrow = !planes32(T);
@@ -2833,13 +2876,38 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
     b->two_piece = false;
     set_layout(b, narrow);
     b->active_plan = 0;
-    s->last_capped = cap != nullptr;
-    if (b->n_queries == 0) return run.end_empty(false);
+    s->last_capped = cap != nullptr || best != nullptr;
+    s->last_best = best != nullptr;
+    const dim3 qgrid((pl.n_queries + 255) / 256), qblock(256);
+    auto finalize = [&]() -> int {   // (best) one record per query from its best word and the per-pair results
+        if (!pl.n_queries) return POA_OK;
+        hipLaunchKernelGGL(poa_scoreset_best_finalize_kernel, qgrid, qblock, 0, stream, s->d_best_word.p, s->d_limit.p, best->slack,
+                           s->d_query_off.p, s->d_query_pairs.p, b->d_score.p, b->d_flags.p, s->d_best.p, pl.n_queries);
+        HIP_TRY(hipGetLastError());
+        return POA_OK;
+    };
+    if (best) {
+        try {
+            if (const int rc = scoreset_cap_upload(s, best->limit, s->d_limit.p, pl.n_queries, cap_stride, stream)) return rc;
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
+        if (pl.n_queries) {
+            hipLaunchKernelGGL(poa_scoreset_best_init_kernel, qgrid, qblock, 0, stream, s->d_best_word.p, s->d_limit.p, pl.n_queries,
+                               best->limit ? 1u : 0u);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (b->n_queries == 0) {
+        if (best) { if (const int rc = finalize()) return rc; }
+        return run.end_empty(false);
+    }
     if (cap) {
         try {
-            if (const int rc = scoreset_cap_upload(s, cap, cap_stride, stream)) return rc;
+            if (const int rc = scoreset_cap_upload(s, cap, s->d_cap.p, b->n_queries, cap_stride, stream)) return rc;
         } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
     }
+    // a best-of run launches from the best-of order of the same (chunk, class) ranges
+    const bool pair_order = cfg && (cfg->flags & POA_CFG_BEST_PAIR_ORDER);
+    const uint32_t* d_list = best && !pair_order ? s->d_best_list[variant].p : s->d_class_list[variant].p;
     // slot bytes stored: kept rows x 2 planes x (1024 two-byte cells in the packed kernel's register layout, else the pitch)
     b->sweep_bytes_written = variant == SS_VAR_U16_PX ? 2ull * (pl.slotted_px * 2048ull + pl.slotted_pitch * 2ull)
                                                       : 2ull * pl.slotted_pitch_all * (narrow ? 2ull : 4ull);
@@ -2852,9 +2920,20 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
         for (uint32_t c = 0; c < SS_N_CLASSES; ++c) {
             const uint32_t begin = ch.class_begin[variant][c], count = ch.class_begin[variant][c + 1] - begin;
             if (!count) continue;
-            sl.list = s->d_class_list[variant].p + begin; sl.n = count;
+            sl.list = d_list + begin; sl.n = count;
             const dim3 grid((count + 3) / 4), block(256);
-            if (cap) {
+            if (best) {
+                const ScoreSetBestLaunch bl{sl, s->d_best_word.p, s->d_limit.p, best->slack, s->d_swept.p, s->d_check_rows.p, b->d_rows.p};
+                if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_best_kernel, grid, block, 0, stream, bl);
+                else if (narrow) {
+                    if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_best_kernel<1, uint16_t>), grid, block, 0, stream, bl);
+                    else hipLaunchKernelGGL((poa_scoreset_sweep_best_kernel<2, uint16_t>), grid, block, 0, stream, bl);
+                } else {
+                    if (c == SS_CLASS_Q1) hipLaunchKernelGGL((poa_scoreset_sweep_best_kernel<1, uint32_t>), grid, block, 0, stream, bl);
+                    else if (c == SS_CLASS_Q2) hipLaunchKernelGGL((poa_scoreset_sweep_best_kernel<2, uint32_t>), grid, block, 0, stream, bl);
+                    else hipLaunchKernelGGL((poa_scoreset_sweep_best_kernel<4, uint32_t>), grid, block, 0, stream, bl);
+                }
+            } else if (cap) {
                 const ScoreSetCapLaunch cl{sl, s->d_cap.p, s->d_swept.p, s->d_check_rows.p, b->d_rows.p};
                 if (c == SS_CLASS_PX) hipLaunchKernelGGL(poa_scoreset_sweep_px_capped_kernel, grid, block, 0, stream, cl);
                 else if (narrow) {
@@ -2876,6 +2955,8 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
             }
             HIP_TRY(hipGetLastError());
         }
+        // (the finalize launch in front of the last chunk's marks: poa_stats_t counts it with the sweep)
+        if (best && &ch == &pl.chunks.back()) { if (const int rc = finalize()) return rc; }
         if (const int rc = run.mark(3)) return rc;
     }
     return run.end();
@@ -3081,6 +3162,46 @@ int poa_scoreset_run_2piece_capped(poa_scoreset_t* s, const poa_costs2_t* costs,
                         (hipStream_t)stream, "poa_scoreset_run_2piece_capped", cap);
 }
 
+int poa_scoreset_run_best(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, uint32_t slack, const uint32_t* limit,
+                          void* stream) {
+    if (!s || !costs) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run_best: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run_best");
+    if (rc != POA_OK) return rc;
+    const ScoreSetBestArgs best{slack, limit};
+    return scoreset_run(s, costs->mismatch, costs->gap_open, costs->gap_extend, cfg, (hipStream_t)stream, "poa_scoreset_run_best", nullptr, &best);
+}
+
+int poa_scoreset_run_2piece_best(poa_scoreset_t* s, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t slack, const uint32_t* limit,
+                                 void* stream) {
+    if (!s || !costs) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_run_2piece_best: null argument");
+    const int rc = scoreset_mode_check(cfg, "poa_scoreset_run_2piece_best");
+    if (rc != POA_OK) return rc;
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    // bests, slack and limits are compared with the score under the reduced costs, which is the two-piece score
+    const ScoreSetBestArgs best{slack, limit};
+    return scoreset_run(s, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
+                        (hipStream_t)stream, "poa_scoreset_run_2piece_best", nullptr, &best);
+}
+
+int poa_scoreset_fetch_best(poa_scoreset_t* s, poa_best_t* best) {
+    if (!s || !best) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch_best: null argument");
+    poa_batch* b = &s->core;
+    if (!b->ran || !s->last_best) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch_best: the last run was not a best-of run (poa_scoreset_run_best)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    static_assert(sizeof(poa_best_t) == sizeof(ScoreSetBest), "poa_best_t is the device record");
+    if (s->plan.n_queries) HIP_TRY(hipMemcpy(best, s->d_best.p, (size_t)s->plan.n_queries * sizeof(poa_best_t), hipMemcpyDeviceToHost));
+    return POA_OK;
+}
+
+int poa_scoreset_device_best(poa_scoreset_t* s, void** best) {
+    if (!s || !best) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_device_best: null argument");
+    if (!s->d_best.p) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_device_best: poa_scoreset_run_best has not been called");
+    *best = s->d_best.p;
+    return POA_OK;
+}
+
 int poa_scoreset_fetch_swept(poa_scoreset_t* s, uint32_t* swept) {
     if (!s || !swept) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_fetch_swept: null argument");
     poa_batch* b = &s->core;
@@ -3165,6 +3286,42 @@ static int score_pairs_impl(const poa_graph_t* const* graphs, uint32_t n_graphs,
     if (rc == POA_OK) rc = poa_scoreset_fetch(s, score, flags, stats);
     poa_scoreset_destroy(s);
     return rc;
+}
+
+// one-shot best-of: exactly one of costs / costs2 is set
+static int score_best_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_costs2_t* costs2,
+                           const poa_config_t* cfg, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs,
+                           const uint32_t* pair_query, const uint32_t* pair_graph, uint32_t slack, const uint32_t* limit, poa_best_t* best,
+                           uint32_t* score, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    poa_scoreset_t* s = nullptr;
+    int rc = poa_scoreset_create(graphs, n_graphs, device, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, cfg, 0, &s);
+    if (rc != POA_OK) return rc;
+    rc = costs ? poa_scoreset_run_best(s, costs, cfg, slack, limit, nullptr) : poa_scoreset_run_2piece_best(s, costs2, cfg, slack, limit, nullptr);
+    if (rc == POA_OK) rc = poa_scoreset_fetch_best(s, best);
+    if (rc == POA_OK && (score || flags || stats)) rc = poa_scoreset_fetch(s, score, flags, stats);
+    poa_scoreset_destroy(s);
+    return rc;
+}
+
+int poa_score_best(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_config_t* cfg,
+                   uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query,
+                   const uint32_t* pair_graph, uint32_t slack, const uint32_t* limit, poa_best_t* best, uint32_t* score,
+                   uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs || !best) return fail(POA_ERR_INVALID_ARG, "poa_score_best: null argument");
+    return score_best_impl(graphs, n_graphs, costs, nullptr, cfg, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, slack, limit, best,
+                           score, flags, stats, device);
+}
+
+int poa_score_best_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs2_t* costs, const poa_config_t* cfg,
+                          uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query,
+                          const uint32_t* pair_graph, uint32_t slack, const uint32_t* limit, poa_best_t* best, uint32_t* score,
+                          uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs || !best) return fail(POA_ERR_INVALID_ARG, "poa_score_best_2piece: null argument");
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    return score_best_impl(graphs, n_graphs, nullptr, costs, cfg, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, slack, limit, best,
+                           score, flags, stats, device);
 }
 
 int poa_score_pairs(const poa_graph_t* const* graphs, uint32_t n_graphs, const poa_costs_t* costs, const poa_config_t* cfg,

@@ -56,12 +56,44 @@ struct SweepParams {
 // returns.  The result does not depend on where a wave stops: the final write applies the same rule to the score itself.
 // Everything in here is wave-uniform (the callers pass it through readfirstlane): the test is a scalar compare and branch.
 struct SweepCap {
-    static constexpr bool on = true;
+    static constexpr bool on = true, best = false;
     uint32_t cap;            // POA_SCORE_UNVISITED: no cap (no check can fire, the final write changes nothing)
     const uint32_t* check;   // the graph's check rows, ascending, 0xFFFFFFFF behind the last one
     uint32_t* swept;         // [n_pairs] row bodies the pair's wave executed
+    // the cap as the row bodies ask for it: by the whole wave at a check row or a strip end, by the one lane of the final write
+    __device__ __forceinline__ uint32_t now_wave(uint32_t) const { return cap; }
+    __device__ __forceinline__ uint32_t now_lane() const { return cap; }
+    __device__ __forceinline__ void publish(uint32_t, uint32_t) const {}
 };
 struct SweepNoCap { static constexpr bool on = false; };   // the uncapped form: nothing is passed, nothing is compiled in
+
+// Best-of form (score sets: poa_scoreset_run_best): the cap is not a number the caller gave but the best score any pair of the
+// SAME QUERY has finished with so far, plus a slack, under an optional ceiling of the query.  The query's best lives in one
+// 64-bit word, score << 32 | pair index, all ones before the first result; it only ever decreases (atomic min), so a cap read
+// from it is never below the final one: a stale value prunes less, never wrongly, and no wave waits for another.  The word is
+// read where SweepCap's number is used — at every check row, strip end and final write — with a relaxed agent-scope atomic
+// VECTOR load (one lane, then readfirstlane): the scalar cache is not coherent with the atomics of other waves.  The final
+// write publishes a finite score that is within the cap it has just read; ties go to the lowest pair index by the key's low half.
+struct SweepBest {
+    static constexpr bool on = true, best = true;
+    unsigned long long* word;   // the query's best word
+    uint32_t slack, limit;      // cap = min(best score + slack (saturating), limit); limit POA_SCORE_UNVISITED: none
+    const uint32_t* check;      // as SweepCap
+    uint32_t* swept;
+    __device__ __forceinline__ uint32_t now_lane() const {
+        const uint32_t s = (uint32_t)(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32);
+        const uint32_t t = s + slack;
+        return umin(t < s ? 0xFFFFFFFFu : t, limit);
+    }
+    __device__ __forceinline__ uint32_t now_wave(uint32_t lane) const {
+        uint32_t c = 0;
+        if (lane == 0) c = now_lane();
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+    }
+    __device__ __forceinline__ void publish(uint32_t score, uint32_t pair) const {
+        (void)__hip_atomic_fetch_min(word, ((unsigned long long)score << 32) | pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 
 // minimum over the 64 lanes, uniform: the DPP steps of wave_scan_min_plus without the weights, lane 63 ends with the total
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
@@ -94,7 +126,7 @@ __device__ __forceinline__ uint32_t wave_min_pk(uint32_t v) {
 // flags; the query (L symbols at q, `pitch` columns), its slot region (M at Mp, D behind it), its carries (4 x n_rows words,
 // touched only by a query wider than one strip) and the index `out` of its result come from the caller.
 //
-// CapT = SweepCap: the capped form (CAP).  A query of one strip tests at its graph's check rows.  A row of one strip of a wider query
+// CapT = SweepCap or SweepBest: the capped form (CAP).  A query of one strip tests at its graph's check rows.  A row of one strip of a wider query
 // is not a cut of the cell grid, so such a query tests at the end of every strip but the last instead: the query extends
 // beyond the strip, every path to column L crosses from the strip's last column to the next one, and the minimum over all
 // rows of M in that column — the carry word, which also bounds the insertion carry from below — is a lower bound again.
@@ -268,7 +300,7 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
 #pragma unroll
                         for (int k = 0; k < K; ++k) mn = umin(mn, k <= last ? Mc[K * m + k] : INF);
                     }
-                    if (wave_min(mn) > cap.cap) {
+                    if (wave_min(mn) > cap.now_wave(lane)) {
                         if (lane == 0) {
                             P.score[out] = INF;
                             P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
@@ -301,10 +333,11 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
                 if (lane == owner) {
                     if constexpr (CAP) {
                         const uint32_t sc = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
-                        const bool over = sc > cap.cap;
+                        const bool over = sc > cap.now_lane();
                         P.score[out] = over ? INF : sc;
                         P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | (over ? POA_FLAG_CAPPED : 0u);
                         cap.swept[out] = n_strips * P.n_rows;
+                        if constexpr (CapT::best) { if (!over && sc != INF) cap.publish(sc, out); }
                     } else {
                         P.score[out] = (sizeof(T) == 2 && v >= 0xFFFFu) ? INF : v;
                         P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;
@@ -315,7 +348,7 @@ __device__ __forceinline__ void sweep_rows(const SweepParams& P, const uint32_t 
             for (int k = 0; k < C; ++k) { Mprev[k] = Mc[k]; Dprev[k] = Dc[k]; }
         }
         if constexpr (CAP) {
-            if (to_next && (uint32_t)__builtin_amdgcn_readlane((int)last_col_min, 63) > cap.cap) {
+            if (to_next && (uint32_t)__builtin_amdgcn_readlane((int)last_col_min, 63) > cap.now_wave(lane)) {
                 if (lane == 0) {
                     P.score[out] = INF;
                     P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
@@ -350,7 +383,8 @@ __global__ __launch_bounds__(256) void poa_sweep_kernel(SweepParams P) {
 //
 // The rows of one query: the body of poa_sweep_px_kernel, shared with the score-set kernels (poa_scoreset.hpp) as sweep_rows
 // is.  L <= 1023 symbols at q; Mp is the calling lane's place in the query's region, [M: n_slots x 128 uint4 | D: n_slots x
-// 128 uint4] + lane; the result goes to index `out`.  CapT = SweepCap: the capped form (CAP), tested at the graph's check rows.
+// 128 uint4] + lane; the result goes to index `out`.  CapT = SweepCap or SweepBest: the capped form (CAP), tested at the graph's
+// check rows.
 template <typename CapT = SweepNoCap>
 __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32_t out, const uint32_t lane, const uint32_t L,
                                               const uint8_t* __restrict__ q, uint4* __restrict__ Mp, const CapT cap = CapT{}) {
@@ -567,7 +601,7 @@ __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32
                 // register min tree over the lane's eight packed cells, both halves being columns, then across the lanes
                 const uint32_t a = pk_min(pk_min(Mc[0] | pad[0], Mc[1] | pad[1]), pk_min(Mc[2] | pad[2], Mc[3] | pad[3]));
                 const uint32_t b = pk_min(pk_min(Mc[4] | pad[4], Mc[5] | pad[5]), pk_min(Mc[6] | pad[6], Mc[7] | pad[7]));
-                if (wave_min_pk(pk_min(a, b)) > cap.cap) {   // (0xFFFF is INF: a cap of 0xFFFF or more never fires)
+                if (wave_min_pk(pk_min(a, b)) > cap.now_wave(lane)) {   // (0xFFFF is INF: a cap of 0xFFFF or more never fires)
                     if (lane == 0) {
                         P.score[out] = INF;
                         P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | POA_FLAG_CAPPED;
@@ -594,10 +628,11 @@ __device__ __forceinline__ void sweep_px_rows(const SweepParams& P, const uint32
         v = L >= QW ? v >> 16 : v & 0xFFFFu;
         if constexpr (CAP) {
             const uint32_t sc = v == I16 ? INF : v;
-            const bool over = sc > cap.cap;
+            const bool over = sc > cap.now_lane();
             P.score[out] = over ? INF : sc;
             P.flags[out] = (L == 1 ? POA_FLAG_SHORT_QUERY : 0u) | (over ? POA_FLAG_CAPPED : 0u);
             cap.swept[out] = P.n_rows;
+            if constexpr (CapT::best) { if (!over && sc != INF) cap.publish(sc, out); }
         } else {
             P.score[out] = v == I16 ? INF : v;
             P.flags[out] = L == 1 ? POA_FLAG_SHORT_QUERY : 0u;

@@ -157,4 +157,118 @@ __global__ __launch_bounds__(256) void poa_scoreset_sweep_px_capped_kernel(Score
     sweep_px_rows<SweepCap>(P, p, lane, L, q, reinterpret_cast<uint4*>(A.planes + A.region_off[p]) + lane, scoreset_cap(C, P, p));
 }
 
+// ---- best-of runs (poa_scoreset_run_best) --------------------------------------------------------------------------------------
+// Kernels and an argument block of their own again: the row bodies in their SweepBest form, whose cap is the running best of the
+// pair's QUERY (best[pair_query[p]]) plus the run's slack, under the query's limit.  An init kernel resets the best words at
+// the start of every run, a finalize kernel turns them and the per-pair results into one poa_best_t per query.
+struct ScoreSetBestLaunch {
+    ScoreSetLaunch A;
+    unsigned long long* best;         // [n_queries] score << 32 | pair index of the best finished pair; all ones: none yet
+    const uint32_t* limit;            // [n_queries] POA_SCORE_UNVISITED: no ceiling
+    uint32_t slack;
+    uint32_t* swept;                  // [n_pairs]
+    const uint32_t* check_rows;       // as ScoreSetCapLaunch
+    const RowMeta* rows_base;
+};
+
+// the device's image of poa_best_t (include/poasta_amd_scoreset_best.h)
+struct ScoreSetBest {
+    uint32_t pair, score, flags, second_score, n_within, reserved[3];
+};
+static_assert(sizeof(ScoreSetBest) == 32, "poa_best_t is 32 bytes");
+
+// scoreset_load for a best-of run; `cap` is the wave's policy, ready for the row bodies.  A pair against a graph without real
+// nodes takes part with its shortcut score like any other pair: tested against the cap of the moment, published if within it.
+__device__ __forceinline__ bool scoreset_load_best(const ScoreSetBestLaunch& B, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
+                                                   const uint8_t*& q, SweepBest& cap) {
+    const ScoreSetLaunch& A = B.A;
+    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (w >= A.n) return false;
+    p = scoreset_uni(A.list[w]);
+    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
+    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
+    P = gp->P;
+    const uint32_t empty = gp->empty;
+    P.cost_x = A.cost_x; P.cost_oe = A.cost_oe; P.cost_e = A.cost_e;
+    const uint64_t qbeg = A.qoff[qid];
+    L = (uint32_t)(A.qoff[qid + 1] - qbeg);
+    q = A.qseq + qbeg;
+    cap = SweepBest{B.best + qid, B.slack, scoreset_uni(B.limit[qid]), B.check_rows + (P.rows - B.rows_base), B.swept};
+    if (empty) {
+        if (lane == 0) {
+            const bool over = L * 4u > cap.now_lane();
+            P.score[p] = over ? 0xFFFFFFFFu : L * 4u;
+            P.flags[p] = POA_FLAG_EMPTY_GRAPH | (over ? POA_FLAG_CAPPED : 0u);
+            B.swept[p] = 0;
+            if (!over) cap.publish(L * 4u, p);
+        }
+        return false;
+    }
+    return true;
+}
+
+template <int Q, typename T>
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_best_kernel(ScoreSetBestLaunch B) {
+    const ScoreSetLaunch& A = B.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    SweepBest cap;
+    if (!scoreset_load_best(B, lane, p, P, L, q, cap)) return;
+    sweep_rows<Q, T, SweepBest>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                                A.carry + scoreset_uni(A.carry_off[p]), cap);
+}
+
+__global__ __launch_bounds__(256) void poa_scoreset_sweep_px_best_kernel(ScoreSetBestLaunch B) {
+    const ScoreSetLaunch& A = B.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t p, L;
+    const uint8_t* q;
+    SweepParams P;
+    SweepBest cap;
+    if (!scoreset_load_best(B, lane, p, P, L, q, cap)) return;
+    sweep_px_rows<SweepBest>(P, p, lane, L, q, reinterpret_cast<uint4*>(A.planes + A.region_off[p]) + lane, cap);
+}
+
+// start of every best-of run: no query has a result yet; a run without limits gets "none" for every query
+__global__ __launch_bounds__(256) void poa_scoreset_best_init_kernel(unsigned long long* best, uint32_t* limit, uint32_t n_queries,
+                                                                     uint32_t has_limit) {
+    const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= n_queries) return;
+    best[qi] = ~0ull;
+    if (!has_limit) limit[qi] = 0xFFFFFFFFu;
+}
+
+// end of the run, one query per thread: its pairs (q_off / q_pairs, ascending pair index) against T = min(best score + slack,
+// limit).  The rule s <= T is applied here to the scores as written: a pair that happened to finish above T does not count, a
+// stopped pair (POA_SCORE_UNVISITED with POA_FLAG_CAPPED) lies above T by the contract.
+__global__ __launch_bounds__(256) void poa_scoreset_best_finalize_kernel(const unsigned long long* best, const uint32_t* limit, uint32_t slack,
+                                                                         const uint32_t* q_off, const uint32_t* q_pairs,
+                                                                         const uint32_t* score, const uint32_t* flags, ScoreSetBest* out,
+                                                                         uint32_t n_queries) {
+    const uint32_t qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= n_queries) return;
+    const unsigned long long w = best[qi];
+    const uint32_t lim = limit[qi];
+    ScoreSetBest r;
+    r.pair = 0xFFFFFFFFu; r.score = 0xFFFFFFFFu; r.flags = 0; r.second_score = 0xFFFFFFFFu; r.n_within = 0;
+    r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+    uint32_t T = lim;
+    if (w != ~0ull) {
+        r.pair = (uint32_t)w; r.score = (uint32_t)(w >> 32); r.flags = flags[r.pair];
+        const uint32_t t = r.score + slack;
+        T = umin(t < r.score ? 0xFFFFFFFFu : t, lim);
+    }
+    for (uint32_t k = q_off[qi]; k < q_off[qi + 1]; ++k) {
+        const uint32_t p = q_pairs[k];
+        const uint32_t s = score[p];
+        if (s > T) continue;
+        r.n_within++;
+        if (p != r.pair) r.second_score = umin(r.second_score, s);
+    }
+    out[qi] = r;
+}
+
 }  // namespace poa_amd

@@ -125,4 +125,26 @@ int build_scoreset_plan(const ScoreSetGraphIn* graphs, uint32_t n_graphs, uint32
     return 0;
 }
 
+void build_scoreset_best_order(ScoreSetPlan& plan) {
+    const uint32_t n = plan.n_pairs, nq = plan.n_queries;
+    plan.query_off.assign((size_t)nq + 1, 0);
+    plan.query_pairs.resize(n);
+    for (uint32_t p = 0; p < n; ++p) plan.query_off[plan.pair_query[p] + 1]++;
+    for (uint32_t q = 0; q < nq; ++q) plan.query_off[q + 1] += plan.query_off[q];
+    std::vector<uint32_t> rank(n), seen(nq, 0);
+    for (uint32_t p = 0; p < n; ++p) {
+        const uint32_t q = plan.pair_query[p];
+        rank[p] = seen[q]++;
+        plan.query_pairs[plan.query_off[q] + rank[p]] = p;
+    }
+    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) {
+        std::vector<uint32_t>& list = plan.best_list[v];
+        list = plan.class_list[v];
+        for (const ScoreSetPlan::Chunk& ch : plan.chunks)
+            for (uint32_t c = 0; c < SS_N_CLASSES; ++c)
+                std::sort(list.begin() + ch.class_begin[v][c], list.begin() + ch.class_begin[v][c + 1],
+                          [&](uint32_t a, uint32_t b) { return rank[a] != rank[b] ? rank[a] < rank[b] : a < b; });
+    }
+}
+
 }  // namespace poa_amd

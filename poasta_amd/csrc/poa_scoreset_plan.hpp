@@ -23,6 +23,8 @@
 //                class depends on the cell width of the run and on whether the packed path is on, so the plan holds three
 //                VARIANTS (u16 with the packed path, u16 without, u32): per variant the pairs of every chunk sorted by class
 //                (stable: pair order inside a class) and, per chunk and class, the range of that list.
+//   best-of runs   (build_scoreset_best_order, made at the set's first best-of run) the pairs of every query as a CSR, and per
+//                variant a second list over the same ranges, ordered by (rank, pair index) inside a range.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -72,6 +74,11 @@ struct ScoreSetPlan {
     std::vector<uint32_t> pair_graph, pair_query, pitch, carry_off;   // [n_pairs]
     std::vector<uint64_t> region_off;                                 // [n_pairs] 4-byte cells from the start of the pair's chunk
     std::vector<uint32_t> class_list[SS_N_VARIANTS];                  // [n_pairs] pair indices, chunk by chunk, class by class
+    // best-of runs (poa_scoreset_run_best): the pairs of every query, and a second launch order
+    std::vector<uint32_t> query_off;                                  // [n_queries + 1] CSR over query_pairs
+    std::vector<uint32_t> query_pairs;                                // [n_pairs] a query's pairs, ascending pair index
+    std::vector<uint32_t> best_list[SS_N_VARIANTS];                   // [n_pairs] the (chunk, class) ranges of class_list, each
+                                                                      // ordered by (rank, pair index); see build_scoreset_best_order
     std::vector<Chunk> chunks;
     uint64_t bytes_total = 0;           // the whole set as one chunk
     uint64_t largest_pair_bytes = 0;
@@ -95,5 +102,12 @@ inline uint64_t scoreset_pair_cells(uint32_t n_slots, uint64_t len) {
 int build_scoreset_plan(const ScoreSetGraphIn* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff, uint64_t n_pairs,
                         const uint32_t* pair_query, const uint32_t* pair_graph, uint64_t workspace_bytes, ScoreSetPlan& out,
                         std::string& err);
+
+// What a best-of run adds to a built plan: the query-to-pairs CSR and, per variant, the best-of launch order.  A pair's RANK is
+// its position among its query's pairs in pair order.  Every (chunk, class) range of class_list is reordered by (rank, pair
+// index), so the k-th candidate of every query is dispatched before any (k + 1)-th: in pair order a query's candidates are
+// neighbours and run side by side, none of them seeing a result of another; in rank order the caller's most likely graph,
+// listed first, has set the query's cap by the time its later candidates start.  Idempotent.
+void build_scoreset_best_order(ScoreSetPlan& plan);
 
 }  // namespace poa_amd
