@@ -155,7 +155,8 @@ enum {
     POA_TUNE_CKPT_ROWS,       /* checkpointed mode: rows per segment (read when the batch is created; 0 / unset: the engine's choice) */
     POA_TUNE_BAND,            /* 0: the one-strip dense kernel computes every cell instead of an exact band (poa_batch_band_info) */
     POA_TUNE_BAND_DELTA,      /* banded kernel: cap of the band distance D (tests: a small cap sends every query to the full kernel) */
-    POA_TUNE_BAND_PAIR,       /* banded kernel, two queries of one length per wave: 0 never, 1 whatever the chunk's count (default: from a count on, poa_batch_band_pair_info) */
+    POA_TUNE_BAND_PAIR,       /* banded kernel, two queries of one length per wave: 0 never, 1 whatever the chunk's count (default: from a count on, poa_batch_band_pair_info);
+                               * the table is full, so the value also carries the override of the narrow tier: see POA_BAND_NARROW_SHIFT */
     POA_TUNE_CAP_STRIDE,      /* capped score-set run: least distance in rows between two check rows (default: poa_graph_sweep_checks) */
     POA_TUNE_COUNT = 32
 };
@@ -425,6 +426,17 @@ int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
  * count (a chunk pairs from that many queries in pairs on; POA_TUNE_BAND_PAIR overrides), out[3] = 1 if the run paired.
  * poa_batch_band_info and poa_batch_last_launch say the same for both ways.  Host side only. */
 int poa_batch_band_pair_info(poa_batch_t* b, uint32_t out[4]);
+/* POA_TUNE_BAND_PAIR, in full: value & POA_BAND_PAIR_MASK is the pairing (0 never, 1 always, POA_BAND_PAIR_RULE: the default
+ * rule, as if unset), (value >> POA_BAND_NARROW_SHIFT) & 3 the narrow tier of the paired pass (0: the default rule, 1: never,
+ * 2: for every pair whose class has a narrow band, whatever the rule says). */
+#define POA_BAND_PAIR_MASK 3
+#define POA_BAND_PAIR_RULE 2
+#define POA_BAND_NARROW_SHIFT 2
+/* the narrow tier of the last dense run (paired banded pass over a window of 384 columns; a query it cannot certify runs the
+ * 512-column pass, and the full pass after that): out[0] = queries that ran the narrow tier, out[1] = those it certified,
+ * out[2] = those the 512 pass then certified (the rest were recomputed by the full pass), out[3] = 0 the tier did not run,
+ * 1 the default rule chose it, 2 an override did.  poa_batch_band_info counts a query certified by either tier as banded. */
+int poa_batch_band_narrow_info(poa_batch_t* b, uint32_t out[4]);
 /* debugging / parity: copy the M, I, D score planes of query i (rows x (len+1), row = topological
  * rank, see poa_graph_node_rows) — only valid if the query's chunk was the last one run */
 int poa_batch_fetch_planes(poa_batch_t* b, uint32_t query, uint32_t* m, uint32_t* i, uint32_t* d);

@@ -22,7 +22,7 @@ FLAG_CAPPED = 0x80
 EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_create", "poa_graph_destroy",
            "poa_graph_rows", "poa_graph_node_rows", "poa_graph_update", "poa_align_batch", "poa_align_batch_ex", "poa_align_batch_2piece", "poa_align_batch_2piece_ex", "poa_planes_2piece", "poa_release_cache", "poa_batch_create", "poa_batch_run",
            "poa_batch_run_ex",
-           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_band_pair_info", "poa_batch_last_launch", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
+           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_band_pair_info", "poa_batch_band_narrow_info", "poa_batch_last_launch", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
            "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
            "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
@@ -82,6 +82,12 @@ def tune_from_env(cfg=None, **overrides):
         if v is None or v == "":
             continue
         vals[i] = EXACT_IMPLS[v] if (k == "EXACT_IMPL" and v in EXACT_IMPLS) else int(v)
+    # POA_BAND_NARROW (0: never the narrow tier of the paired banded pass, 1: for every pair whose class has a narrow band): the
+    # table is full, so it rides in BAND_PAIR's entry (poasta_amd.h: POA_BAND_NARROW_SHIFT; pairing 2 = by the rule, as if unset)
+    nv = overrides.get("band_narrow", os.environ.get("POA_BAND_NARROW"))
+    if nv is not None and nv != "":
+        i = TUNE_KEYS.index("BAND_PAIR")
+        vals[i] = (min(vals[i], 1) if i in vals else 2) | ((2 if int(nv) else 1) << 2)
     if cfg is None:
         if not vals:
             return None
@@ -217,6 +223,9 @@ def lib():
     if hasattr(L, "poa_batch_band_pair_info"):
         L.poa_batch_band_pair_info.restype = C.c_int
         L.poa_batch_band_pair_info.argtypes = [vp, vp]
+    if hasattr(L, "poa_batch_band_narrow_info"):
+        L.poa_batch_band_narrow_info.restype = C.c_int
+        L.poa_batch_band_narrow_info.argtypes = [vp, vp]
     if hasattr(L, "poa_batch_last_launch"):
         L.poa_batch_last_launch.restype = C.c_int
         L.poa_batch_last_launch.argtypes = [vp, C.c_uint32, vp]

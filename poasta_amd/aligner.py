@@ -414,6 +414,14 @@ class ResidentBatch:
         _lib.check(_lib.lib().poa_batch_band_pair_info(self.handle, out))
         return {"paired": int(out[0]), "single": int(out[1]), "rule_count": int(out[2]), "ran_paired": bool(out[3])}
 
+    def band_narrow_info(self):
+        """The narrow tier of the paired banded pass in the last dense run: {"ran", "certified", "certified_512", "chosen_by"}
+        (poa_batch_band_narrow_info): queries that ran the 384-column tier, those it certified, those the 512-column pass then
+        certified (the rest went to the full pass), and None / "rule" / "override"."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.lib().poa_batch_band_narrow_info(self.handle, out))
+        return {"ran": int(out[0]), "certified": int(out[1]), "certified_512": int(out[2]), "chosen_by": (None, "rule", "override")[int(out[3])]}
+
     def launches(self):
         """What the dense one-piece pass of the last run launched, one dict per chunk (poa_batch_last_launch): "kernel" in
         {"forward", "packed", "px", "pxmw", "band"}, "quads", "fuse", "mw", "waves", "code_fmt", "tb_lanes" (0: no separate

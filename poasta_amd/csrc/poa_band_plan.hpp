@@ -20,6 +20,7 @@ namespace poa_amd {
 
 constexpr uint32_t BAND_SEG_ROWS = 64;     // rows per segment: the window moves only at multiples of it
 constexpr uint32_t BAND_WINDOW = 512;      // columns per window
+constexpr uint32_t BAND_WINDOW_NARROW = 384;   // columns per window of the narrow tier: a second plan per class, same segments and alignment
 constexpr uint32_t BAND_BASE_ALIGN = 8;    // a window starts at a multiple of it
 constexpr uint32_t BAND_NONE = 0xFFFFFFFFu;
 constexpr uint32_t BAND_D_MAX = 65535;     // no score of a 14-bit plane needs a wider band

@@ -76,9 +76,35 @@ DenseRunPlan plan_dense_run(uint32_t gap_open, uint32_t gap_extend, uint64_t max
     R.band_cap = 0xFFFFFFFFu;
     if (const int* dv = T.ptr(POA_TUNE_BAND_DELTA)) R.band_cap = (*dv) > 0 ? (uint32_t)(*dv) : 0u;
     // two queries of one length per wave (poa_forward_band2_kernel): POA_BAND_PAIR=0 never, 1 whatever the count, else the rule
+    // The tune table is full, so the same entry carries the override of the narrow tier (poasta_amd.h: POA_TUNE_BAND_PAIR):
+    // bits 0..1 the pairing (0 never, 1 always, 2 by the rule), bits 2..3 the narrow tier (0 by the rule, 1 never, 2 whenever paired)
     R.band_pair = -1;
-    if (const int* pv = T.ptr(POA_TUNE_BAND_PAIR)) R.band_pair = (*pv) != 0 ? 1 : 0;
+    R.band_narrow = -1;
+    if (const int* pv = T.ptr(POA_TUNE_BAND_PAIR)) {
+        const int p = (*pv) & POA_BAND_PAIR_MASK, n = ((*pv) >> POA_BAND_NARROW_SHIFT) & 3;
+        if (p != POA_BAND_PAIR_RULE) R.band_pair = p != 0 ? 1 : 0;
+        if (n) R.band_narrow = n - 1;
+    }
     return R;
+}
+
+// The narrow tier (poa_forward_band2_kernel<6>, a window of 384 columns) for a band class of query length L whose narrow plan has
+// band distance d_n: 0 the rule takes it, 1 only the override does (the plan has a band), 2 never (no band: D_n < 4).
+// BAND_NARROW_MIN_SHARE is a policy, not a measurement: a query the tier cannot certify costs a second banded pass, so the rule
+// keeps the tier to classes where it certifies every score up to e * L / 4 - half a unit of gap extension per base under the
+// default costs, far above what reads that align at all score (profiles/pr_band_narrow/README.md has the price of a miss).
+constexpr uint32_t BAND_NARROW_MIN_SHARE = 4;   // D_n - 4 >= L / 4
+uint32_t band_narrow_class(uint32_t d_n, uint32_t L) {
+    if (d_n < 4) return 2;
+    return (uint64_t)BAND_NARROW_MIN_SHARE * (d_n - 4) >= L ? 0 : 1;
+}
+// how many of a paired chunk's leading pairs run the narrow tier: n_rule of them belong to classes the rule takes, n_any to
+// classes with a narrow band at all.  The rule asks that the chunk pairs by band_pair_rule itself (pair_by_rule), not only
+// under a forced POA_BAND_PAIR=1: the tier exists in the paired form alone and pays where pairing does.
+uint32_t band_narrow_pairs(const DenseRunPlan& R, bool pair_by_rule, uint32_t n_rule, uint32_t n_any) {
+    if (R.band_narrow == 0) return 0;
+    if (R.band_narrow > 0) return n_any;
+    return pair_by_rule ? n_rule : 0;
 }
 
 DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T) {

@@ -27,6 +27,7 @@ struct DenseRunPlan {
     int plan;                                // chunk plan of the batch: 0 (4-byte elements), 1 (u16 full planes), 2 (compact)
     bool fuse_tb, want_band;
     int quads_override, band_pair, tb_group; // 0: no override; -1: by the rule; 0: by the chunk's count
+    int band_narrow;                         // the narrow tier of the paired banded pass: -1 by the rule, 0 never, 1 whenever paired
     uint32_t band_cap, spec_depth;
 };
 DenseRunPlan plan_dense_run(uint32_t gap_open, uint32_t gap_extend, uint64_t max_len, uint64_t min_path_nodes, uint32_t mode, bool full_planes,
@@ -39,4 +40,6 @@ struct DenseChunkPlan {
     bool separate_tb;  // the traceback is a launch of its own (v[5] != 0)
 };
 DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T);
+uint32_t band_narrow_class(uint32_t d_n, uint32_t L);
+uint32_t band_narrow_pairs(const DenseRunPlan& R, bool pair_by_rule, uint32_t n_rule, uint32_t n_any);
 }  // namespace poa_amd

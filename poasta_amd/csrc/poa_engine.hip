@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -264,6 +265,14 @@ struct poa_batch {
     std::vector<uint32_t> h_band_cls, h_band_d;          // per query: class; per class: band distance D
     DevBuf<uint32_t> d_band_cls, d_band_d, d_band_base;  // the same on the device, and the window bases [class][segment]
     DevBuf<uint32_t> d_band_list, d_band_count;          // queries the full kernel redoes: [n_queries], and their number per chunk
+    // narrow tier (poa_forward_band2_kernel<6>): the classes' second plan for a window of BAND_WINDOW_NARROW columns, and the list
+    // of the queries it could not certify, which the 512 pass then takes.  d_band_count holds three counters per chunk:
+    // [chunk] the full pass's list, [n_chunks + chunk] the narrow tier's list, [2 * n_chunks + chunk] those of it the 512 pass missed too
+    std::vector<uint32_t> h_band_dn;
+    DevBuf<uint32_t> d_band_dn, d_band_base_n, d_band_list_n;
+    std::vector<uint32_t> h_band_order;                              // the host's copy of d_band_order
+    std::vector<uint32_t> h_band_nnarrow_rule, h_band_nnarrow_any;   // per chunk: its leading pairs whose class takes the tier by the rule / has D_n >= 4
+    uint32_t narrow_ran = 0, narrow_how = 0, narrow_chunks = 0;      // the last run (poa_batch_band_narrow_info)
     // paired banded pass (poa_forward_band2_kernel): per chunk of plan[band_pair_plan] the queries in launch order - the pairs
     // (A, B, A, B, ...), then the singles - built from the lengths alone at the first run that may pair and kept
     int band_pair_plan = -1;
@@ -449,6 +458,8 @@ static int prepare_band(poa_batch* b) {
     std::vector<uint32_t> bases;
     b->h_band_cls.resize(b->n_queries);
     b->h_band_d.clear();
+    b->h_band_dn.clear();
+    std::vector<uint32_t> bases_n;
     for (uint32_t i = 0; i < b->n_queries; ++i) {
         const uint64_t len = b->h_qoff[i + 1] - b->h_qoff[i];
         auto it = cls_of_len.find(len);
@@ -456,6 +467,8 @@ static int prepare_band(poa_batch* b) {
             it = cls_of_len.emplace(len, (uint32_t)b->h_band_d.size()).first;
             bases.resize(bases.size() + b->band_n_seg);
             b->h_band_d.push_back(plan_band(fg, bt, (uint32_t)len, BAND_SEG_ROWS, BAND_WINDOW, bases.data() + bases.size() - b->band_n_seg));
+            bases_n.resize(bases.size());
+            b->h_band_dn.push_back(plan_band(fg, bt, (uint32_t)len, BAND_SEG_ROWS, BAND_WINDOW_NARROW, bases_n.data() + bases_n.size() - b->band_n_seg));
         }
         b->h_band_cls[i] = it->second;
     }
@@ -466,6 +479,11 @@ static int prepare_band(poa_batch* b) {
     HIP_TRY(hipMemcpy(b->d_band_cls.p, b->h_band_cls.data(), b->h_band_cls.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_band_d.p, b->h_band_d.data(), b->h_band_d.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->d_band_base.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(b->d_band_dn.alloc(b->h_band_dn.size()));
+    HIP_TRY(b->d_band_base_n.alloc(bases_n.size()));
+    HIP_TRY(b->d_band_list_n.alloc(b->n_queries));
+    HIP_TRY(hipMemcpy(b->d_band_dn.p, b->h_band_dn.data(), b->h_band_dn.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_band_base_n.p, bases_n.data(), bases_n.size() * 4, hipMemcpyHostToDevice));
     b->band_ready = true;
     return POA_OK;
 }
@@ -479,6 +497,7 @@ static int prepare_band_pairs(poa_batch* b) {
     constexpr uint32_t NONE = 0xFFFFFFFFu;
     std::vector<uint32_t> order(b->n_queries), waiting(b->h_band_d.size(), NONE), singles;
     b->h_band_npair.assign(PL.chunks.size(), 0);
+    b->h_band_nnarrow_rule.assign(PL.chunks.size(), 0); b->h_band_nnarrow_any.assign(PL.chunks.size(), 0);
     for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
         const auto& ch = PL.chunks[ci];
         uint32_t at = ch.first;
@@ -490,6 +509,19 @@ static int prepare_band_pairs(poa_batch* b) {
             else { order[at++] = waiting[cl]; order[at++] = i; waiting[cl] = NONE; }
         }
         b->h_band_npair[ci] = (at - ch.first) / 2;
+        // the pairs the narrow tier can take come first, those it takes by the rule before those only an override sends there
+        // (band_narrow_class, poa_dense_plan.cpp): the tier's launch is then a prefix of the chunk's pairs
+        std::vector<std::array<uint32_t, 3>> pr;   // {class of narrow tier, A, B}
+        uint32_t n_of[3] = {0, 0, 0};
+        for (uint32_t k = ch.first; k < at; k += 2) {
+            const uint32_t cl = b->h_band_cls[order[k]];
+            const uint32_t t = band_narrow_class(b->h_band_dn[cl], (uint32_t)(b->h_qoff[order[k] + 1] - b->h_qoff[order[k]]));
+            pr.push_back({t, order[k], order[k + 1]});
+            ++n_of[t];
+        }
+        std::stable_sort(pr.begin(), pr.end(), [](const auto& x, const auto& y) { return x[0] < y[0]; });
+        for (size_t k = 0; k < pr.size(); ++k) { order[ch.first + 2 * k] = pr[k][1]; order[ch.first + 2 * k + 1] = pr[k][2]; }
+        b->h_band_nnarrow_rule[ci] = n_of[0]; b->h_band_nnarrow_any[ci] = n_of[0] + n_of[1];
         for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) {
             uint32_t& w = waiting[b->h_band_cls[i]];
             if (w == i) { singles.push_back(i); w = NONE; }
@@ -497,6 +529,7 @@ static int prepare_band_pairs(poa_batch* b) {
         std::sort(singles.begin(), singles.end());
         for (uint32_t i : singles) order[at++] = i;
     }
+    b->h_band_order = order;
     if (b->d_band_order.n < b->n_queries) HIP_TRY(b->d_band_order.alloc(b->n_queries));
     HIP_TRY(hipMemcpy(b->d_band_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
     b->band_pair_plan = b->active_plan;
@@ -596,19 +629,43 @@ int launch_band(poa_batch* b, size_t ci, const DenseRunPlan& R, const FwdParams&
     BandParams bp;
     bp.cls = b->d_band_cls.p; bp.cls_d = b->d_band_d.p; bp.cls_base = b->d_band_base.p; bp.n_seg = b->band_n_seg;
     bp.d_cap = R.band_cap; bp.list = b->d_band_list.p; bp.count = b->d_band_count.p + ci; bp.order = nullptr;
-    uint32_t n_pairs = 0;
+    bp.n_order = nullptr; bp.count_nf = nullptr;
+    const size_t n_chunks = b->cur().chunks.size();
+    uint32_t n_pairs = 0, n_narrow = 0;
     if (R.band_pair != 0) {
         if (const int rc = prepare_band_pairs(b)) return rc;
         n_pairs = b->h_band_npair[ci];
-        if (R.band_pair < 0 && !band_pair_rule(2 * n_pairs)) n_pairs = 0;
+        const bool by_rule = band_pair_rule(2 * n_pairs);
+        if (R.band_pair < 0 && !by_rule) n_pairs = 0;
+        if (n_pairs) n_narrow = band_narrow_pairs(R, by_rule, b->h_band_nnarrow_rule[ci], b->h_band_nnarrow_any[ci]);
     }
     if (n_pairs) {
         // the pairs, then the singles one per wave: grids sized on the host, nothing read back
         const uint32_t n_single = ch.count - 2 * n_pairs;
         FwdParams fq = fp;
         BandParams bq = bp;
-        fq.n_queries = n_pairs; bq.order = b->d_band_order.p + ch.first;
-        hipLaunchKernelGGL(poa_forward_band2_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, stream, fq, bq);
+        if (n_narrow) {
+            // the narrow tier over the leading pairs, under the classes' narrow plan; what it cannot certify goes to a list of
+            // its own, which the 512 pass works off one query per wave (its grid sized for all of them: the waves past the
+            // device-side count return at once); what that pass cannot certify joins the full pass's list
+            BandParams bn = bp;
+            bn.cls_d = b->d_band_dn.p; bn.cls_base = b->d_band_base_n.p;
+            bn.list = b->d_band_list_n.p; bn.count = b->d_band_count.p + n_chunks + ci;
+            fq.n_queries = n_narrow; bn.order = b->d_band_order.p + ch.first;
+            hipLaunchKernelGGL(poa_forward_band2_kernel<6>, dim3((n_narrow + 3) / 4), dim3(256), 0, stream, fq, bn);
+            HIP_TRY(hipGetLastError());
+            fq.n_queries = 2 * n_narrow; bq.order = b->d_band_list_n.p + fp.first_query;
+            bq.n_order = bn.count; bq.count_nf = b->d_band_count.p + 2 * n_chunks + ci;
+            hipLaunchKernelGGL((poa_forward_band_kernel<false, true>), dim3((2 * n_narrow + 3) / 4), dim3(256), 0, stream, fq, bq);
+            HIP_TRY(hipGetLastError());
+            bq.n_order = nullptr; bq.count_nf = nullptr;
+            b->narrow_ran += 2 * n_narrow; b->narrow_chunks = (uint32_t)ci + 1;
+            b->narrow_how = R.band_narrow > 0 ? 2u : 1u;
+        }
+        if (n_pairs > n_narrow) {
+            fq.n_queries = n_pairs - n_narrow; bq.order = b->d_band_order.p + ch.first + 2 * n_narrow;
+            hipLaunchKernelGGL(poa_forward_band2_kernel<8>, dim3((n_pairs - n_narrow + 3) / 4), dim3(256), 0, stream, fq, bq);
+        }
         if (n_single) {
             HIP_TRY(hipGetLastError());
             fq.n_queries = n_single; bq.order = b->d_band_order.p + ch.first + 2 * n_pairs;
@@ -623,6 +680,8 @@ int launch_band(poa_batch* b, size_t ci, const DenseRunPlan& R, const FwdParams&
     hipLaunchKernelGGL(poa_forward_band_kernel<true>, dim3(blocks), dim3(256), 0, stream, fp, bp);
     uint32_t min_d = 0xFFFFFFFFu;
     for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) min_d = std::min(min_d, std::min(b->h_band_d[b->h_band_cls[i]], R.band_cap));
+    // (the queries of the narrow tier: the D of the tier that ran first)
+    for (uint32_t k = 0; k < 2 * n_narrow; ++k) min_d = std::min(min_d, std::min(b->h_band_dn[b->h_band_cls[b->h_band_order[ch.first + k]]], R.band_cap));
     b->band_min_d = b->band_used ? std::min(b->band_min_d, min_d) : min_d;
     b->band_used = true; b->band_queries += ch.count; b->band_chunks = (uint32_t)ci + 1;
     return POA_OK;
@@ -1446,12 +1505,13 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     b->launches.clear();
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->pair_paired = 0; b->pair_single = 0;
+    b->narrow_ran = 0; b->narrow_how = 0; b->narrow_chunks = 0;
     b->active_plan = R.plan;
     const poa_batch::Plan& PL = b->cur();
     if (b->n_queries == 0) return run.end_empty(true);
     if (R.want_band && !PL.chunks.empty()) {   // one fallback counter per chunk, cleared per run
-        if (b->d_band_count.n < PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(PL.chunks.size()));
-        HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, PL.chunks.size() * 4, stream));
+        if (b->d_band_count.n < 3 * PL.chunks.size()) HIP_TRY(b->d_band_count.alloc(3 * PL.chunks.size()));
+        HIP_TRY(hipMemsetAsync(b->d_band_count.p, 0, 3 * PL.chunks.size() * 4, stream));
     }
     for (size_t ci = 0; ci < PL.chunks.size(); ++ci) {
         const auto& ch = PL.chunks[ci];
@@ -1641,6 +1701,22 @@ int poa_batch_band_info(poa_batch_t* b, uint32_t out[4]) {
     uint32_t fell = 0;
     for (uint32_t c : counts) fell += c;
     out[2] = fell; out[1] = b->band_queries - std::min(fell, b->band_queries);
+    return POA_OK;
+}
+
+int poa_batch_band_narrow_info(poa_batch_t* b, uint32_t out[4]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_narrow_info: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_band_narrow_info: poa_batch_run has not been called");
+    out[0] = b->narrow_ran; out[1] = 0; out[2] = 0; out[3] = b->narrow_how;
+    if (!b->narrow_ran) return POA_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const size_t n_chunks = b->cur().chunks.size();
+    std::vector<uint32_t> counts(3 * n_chunks);
+    HIP_TRY(hipMemcpy(counts.data(), b->d_band_count.p, counts.size() * 4, hipMemcpyDeviceToHost));
+    uint32_t missed = 0, missed_both = 0;
+    for (size_t c = 0; c < n_chunks; ++c) { missed += counts[n_chunks + c]; missed_both += counts[2 * n_chunks + c]; }
+    out[1] = b->narrow_ran - std::min(missed, b->narrow_ran); out[2] = missed - std::min(missed_both, missed);
     return POA_OK;
 }
 

@@ -30,6 +30,10 @@ struct BandParams {
     uint32_t* list;            // queries the full kernel has to redo, appended at list[first_query + k]
     uint32_t* count;           // their number (cleared per run)
     const uint32_t* order;     // paired runs: the launch's queries - the chunk's pairs (A, B, A, B, ...) or its singles; else unused
+    // the 512 pass over the narrow tier's misses (LIST): order is that tier's list and *n_order its length, known on the device
+    // alone (the grid is sized for every query of the tier); a query this pass cannot certify either is counted in *count_nf
+    const uint32_t* n_order;   // nullptr: order holds P.n_queries entries
+    uint32_t* count_nf;
 };
 
 constexpr uint32_t BAND_ROWS = BAND_SEG_ROWS;
@@ -54,11 +58,15 @@ __global__ __launch_bounds__(256) void poa_forward_band_kernel(FwdParams P, Band
     const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
     if (wq >= P.n_queries) return;
     if (FULL && wq >= *B.count) return;   // the list of the banded pass: usually empty (the grid is sized for the chunk)
+    if (LIST && B.n_order && wq >= *B.n_order) return;   // the list of the narrow tier, likewise
     const uint32_t qi = FULL ? B.list[P.first_query + wq] : (LIST ? B.order[wq] : P.first_query + wq);
     const uint32_t cl = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.cls[qi]);   // uniform: the bases come in over the scalar cache
     const uint32_t band_d = ((const CU32*)B.cls_d)[cl] < B.d_cap ? ((const CU32*)B.cls_d)[cl] : B.d_cap;
     if (!FULL && band_d < 4) {   // no band for this length (T = e * (D - 4) needs D >= 4): the full pass computes the query
-        if (lane == 0) B.list[P.first_query + atomicAdd(B.count, 1u)] = qi;
+        if (lane == 0) {
+            B.list[P.first_query + atomicAdd(B.count, 1u)] = qi;
+            if (LIST && B.n_order) atomicAdd(B.count_nf, 1u);
+        }
         return;
     }
     const uint64_t qbeg = P.qoff[qi];
@@ -379,7 +387,10 @@ __global__ __launch_bounds__(256) void poa_forward_band_kernel(FwdParams P, Band
     // certified: the computed end score is finite and <= T = e * (D - 4)
     const uint32_t T = e * (band_d - 4u) < 0x3FFEu ? e * (band_d - 4u) : 0x3FFEu;
     if (!(end_score <= T)) {
-        if (lane == 0) B.list[P.first_query + atomicAdd(B.count, 1u)] = qi;
+        if (lane == 0) {
+            B.list[P.first_query + atomicAdd(B.count, 1u)] = qi;
+            if (LIST && B.n_order) atomicAdd(B.count_nf, 1u);
+        }
     }
 }
 
@@ -395,10 +406,19 @@ __global__ __launch_bounds__(256) void poa_forward_band_kernel(FwdParams P, Band
 // LDS: the four ACGT mask tables, 8 KB per wave (the table "no child symbol" of the other instantiations is all zeros and is
 // not kept); the hand-over buffer of a window move (2 arrays x 2 queries x 512 u16 = 4 KB) lies over them, since place()
 // rebuilds the tables right after every move.  32 KB per workgroup, and at most 96 VGPRs: five workgroups per CU.
+//
+// K = 6 is the NARROW tier: the same pass over a window of 384 columns (BAND_WINDOW_NARROW), six registers per row array, under
+// the class's narrow plan (its own D and bases; the launcher hands them in as B.cls_d and B.cls_base, and the list of the 512
+// pass as B.list).  A lane's six columns are three dwords of a plane row, and bases stay multiples of 8, so whatever K = 8
+// decides per lane is decided per DWORD here: a lane may straddle the end of the plane row (the pitch is a multiple of 8, 6 *
+// lane is not) or the edge of a predecessor's window, and a window moves by a number of columns that is no multiple of 6.
+// LDS: four tables of six registers (a 16-byte and an 8-byte piece per lane), 6 KB per wave; the hand-over buffer (3 KB) over them.
+template <int K>
 __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, BandParams B) {
-    constexpr int K = 8;
+    static_assert(K == 8 || K == 6, "the 512-column window or the narrow one");
     constexpr uint32_t WIN = 64 * K;
-    static_assert(WIN == BAND_WINDOW && BAND_BASE_ALIGN % K == 0, "a lane's eight columns move together");
+    static_assert(WIN == (K == 8 ? BAND_WINDOW : BAND_WINDOW_NARROW) && BAND_BASE_ALIGN % 8 == 0,
+                  "K = 8: a lane's eight columns move together; K = 6: a lane's dwords do");
     constexpr uint32_t I16 = 0xFFFFu, INF2 = 0xFFFFFFFFu;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wp = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -436,17 +456,24 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
     const CU32* cpslot = (const CU32*)P.pred_dslot;
     const CU32* cbase = (const CU32*)(B.cls_base + (uint64_t)cl * B.n_seg);
 
-    __shared__ uint4 sym_tab[4 * 4 * 2 * 64];
-    uint4* my_tab = sym_tab + (threadIdx.x >> 6) * (4 * 2 * 64) + lane;
-    uint4* my_move = sym_tab + (threadIdx.x >> 6) * (4 * 2 * 64);   // [array][query][lane]
+    constexpr uint32_t TAB_WAVE = K == 8 ? 4 * 2 * 64 : 4 * 64 + 2 * 64;   // uint4 per wave (K = 6: 4 x 64 uint4, then 4 x 64 uint2)
+    __shared__ uint4 sym_tab[4 * TAB_WAVE];
+    uint4* my_tab = sym_tab + (threadIdx.x >> 6) * TAB_WAVE + lane;
+    uint4* my_move = sym_tab + (threadIdx.x >> 6) * TAB_WAVE;   // [array][query][lane] (K = 6: [array][query][dword of the window])
+    uint2* my_tab2 = reinterpret_cast<uint2*>(my_move + 4 * 64) + lane;   // (K = 6) registers 4 and 5 of the tables
 
     uint32_t base = 0, c0 = 0;
     bool act = false;
+    uint32_t nd = 0;   // (K = 6) my dwords inside the plane row: 0..3; act = all three
     uint32_t qP[K], qlE = 0;
     auto place = [&](const uint32_t nb) {
         base = nb;
         c0 = nb + K * lane;
-        act = c0 < pitch;
+        if constexpr (K == 8) act = c0 < pitch;
+        else {
+            nd = c0 < pitch ? ((pitch - c0) >> 1 < 3u ? (pitch - c0) >> 1 : 3u) : 0u;   // (c0 and the pitch are even)
+            act = nd == 3u;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const bool in = c0 + k < L;
@@ -461,8 +488,13 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
             uint32_t m[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) m[k] = pku(pkv(0u) - pkv(pk_is_zero(qP[k] ^ s2)));
-            my_tab[(si * 2) * 64] = make_uint4(m[0], m[1], m[2], m[3]);
-            my_tab[(si * 2 + 1) * 64] = make_uint4(m[4], m[5], m[6], m[7]);
+            if constexpr (K == 8) {
+                my_tab[(si * 2) * 64] = make_uint4(m[0], m[1], m[2], m[3]);
+                my_tab[(si * 2 + 1) * 64] = make_uint4(m[4], m[5], m[6], m[7]);
+            } else {
+                my_tab[si * 64] = make_uint4(m[0], m[1], m[2], m[3]);
+                my_tab2[si * 64] = make_uint2(m[4], m[5]);
+            }
         }
         // each lane reads back only what it wrote itself: no barrier needed
     };
@@ -503,6 +535,7 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
                 uint32_t mD[K], mI[K];
                 const uint32_t si = meta.sym_idx & 15u, ci = meta.sym_idx >> 4;
                 if ((meta.sym_idx & 0x88u) == 0) {   // both symbols among ACGT, or no child symbol (ci == 4: no mask)
+                    if constexpr (K == 8) {
                     const uint4 a0 = my_tab[(si * 2) * 64], a1 = my_tab[(si * 2 + 1) * 64];
                     mD[0] = a0.x; mD[1] = a0.y; mD[2] = a0.z; mD[3] = a0.w; mD[4] = a1.x; mD[5] = a1.y; mD[6] = a1.z; mD[7] = a1.w;
                     if (ci < 4u) {
@@ -511,6 +544,19 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
                     } else {
 #pragma unroll
                         for (int k = 0; k < K; ++k) mI[k] = 0u;
+                    }
+                    } else {
+                        const uint4 a0 = my_tab[si * 64];
+                        const uint2 a1 = my_tab2[si * 64];
+                        mD[0] = a0.x; mD[1] = a0.y; mD[2] = a0.z; mD[3] = a0.w; mD[4] = a1.x; mD[5] = a1.y;
+                        if (ci < 4u) {
+                            const uint4 c0_ = my_tab[ci * 64];
+                            const uint2 c1_ = my_tab2[ci * 64];
+                            mI[0] = c0_.x; mI[1] = c0_.y; mI[2] = c0_.z; mI[3] = c0_.w; mI[4] = c1_.x; mI[5] = c1_.y;
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < K; ++k) mI[k] = 0u;
+                        }
                     }
                 } else {
                     const uint32_t csym2 = cs1 | (cs1 << 16);
@@ -574,6 +620,7 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
             const bool keep_d = (meta.flags & ROW_STORE_D) != 0;
             const uint64_t rbase = (uint64_t)r * pitch;
             const uint64_t dbase = d_off + (keep_d ? (uint64_t)(cslot ? cslot[r] : r) * pitch : 0);
+            if constexpr (K == 8) {
             if (act) {
                 *reinterpret_cast<uint4*>(Mp_a + rbase + c0) = make_uint4(pk_lo_lo(Ms[0], Ms[1]), pk_lo_lo(Ms[2], Ms[3]), pk_lo_lo(Ms[4], Ms[5]), pk_lo_lo(Ms[6], Ms[7]));
                 *reinterpret_cast<uint4*>(Mp_b + rbase + c0) = make_uint4(pk_hi_hi(Ms[0], Ms[1]), pk_hi_hi(Ms[2], Ms[3]), pk_hi_hi(Ms[4], Ms[5]), pk_hi_hi(Ms[6], Ms[7]));
@@ -582,14 +629,41 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
                     *reinterpret_cast<uint4*>(Mp_b + dbase + c0) = make_uint4(pk_hi_hi(Dc[0], Dc[1]), pk_hi_hi(Dc[2], Dc[3]), pk_hi_hi(Dc[4], Dc[5]), pk_hi_hi(Dc[6], Dc[7]));
                 }
             }
+            } else {
+                // twelve bytes per query and array at 4-byte alignment; the lane that straddles the end of the plane row stores
+                // only its dwords inside it (the next one would land in the next row, after the last row outside the plane)
+                if (act) {
+                    *reinterpret_cast<uint3*>(Mp_a + rbase + c0) = make_uint3(pk_lo_lo(Ms[0], Ms[1]), pk_lo_lo(Ms[2], Ms[3]), pk_lo_lo(Ms[4], Ms[5]));
+                    *reinterpret_cast<uint3*>(Mp_b + rbase + c0) = make_uint3(pk_hi_hi(Ms[0], Ms[1]), pk_hi_hi(Ms[2], Ms[3]), pk_hi_hi(Ms[4], Ms[5]));
+                    if (keep_d) {
+                        *reinterpret_cast<uint3*>(Mp_a + dbase + c0) = make_uint3(pk_lo_lo(Dc[0], Dc[1]), pk_lo_lo(Dc[2], Dc[3]), pk_lo_lo(Dc[4], Dc[5]));
+                        *reinterpret_cast<uint3*>(Mp_b + dbase + c0) = make_uint3(pk_hi_hi(Dc[0], Dc[1]), pk_hi_hi(Dc[2], Dc[3]), pk_hi_hi(Dc[4], Dc[5]));
+                    }
+                } else if (nd) {
+                    *reinterpret_cast<uint32_t*>(Mp_a + rbase + c0) = pk_lo_lo(Ms[0], Ms[1]);
+                    *reinterpret_cast<uint32_t*>(Mp_b + rbase + c0) = pk_hi_hi(Ms[0], Ms[1]);
+                    if (nd == 2u) {
+                        *reinterpret_cast<uint32_t*>(Mp_a + rbase + c0 + 2) = pk_lo_lo(Ms[2], Ms[3]);
+                        *reinterpret_cast<uint32_t*>(Mp_b + rbase + c0 + 2) = pk_hi_hi(Ms[2], Ms[3]);
+                    }
+                    if (keep_d) {
+                        *reinterpret_cast<uint32_t*>(Mp_a + dbase + c0) = pk_lo_lo(Dc[0], Dc[1]);
+                        *reinterpret_cast<uint32_t*>(Mp_b + dbase + c0) = pk_hi_hi(Dc[0], Dc[1]);
+                        if (nd == 2u) {
+                            *reinterpret_cast<uint32_t*>(Mp_a + dbase + c0 + 2) = pk_lo_lo(Dc[2], Dc[3]);
+                            *reinterpret_cast<uint32_t*>(Mp_b + dbase + c0 + 2) = pk_hi_hi(Dc[2], Dc[3]);
+                        }
+                    }
+                }
+            }
             if (meta.flags & ROW_END) {
-                // the end cell (end row, L), if the window holds it: window column wc sits in lane wc / 8, register wc & 7
+                // the end cell (end row, L), if the window holds it: window column wc sits in lane wc / K, register wc % K
                 const uint32_t wc = L - base;
                 if (L >= base && wc < WIN) {
-                    const uint32_t kk = wc & 7u;
+                    const uint32_t kk = wc % (uint32_t)K;
                     // (every register is read out and the choice made among scalars: a choice among the registers themselves
                     // becomes an indexed access that puts the row arrays into scratch)
-                    const int src = __builtin_amdgcn_readfirstlane((int)(wc >> 3));
+                    const int src = __builtin_amdgcn_readfirstlane((int)(wc / (uint32_t)K));
                     uint32_t w = 0;
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
@@ -626,6 +700,7 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
                     const uint32_t pb = cbase[pr / BAND_ROWS];
                     const uint64_t pbase = (uint64_t)pr * pitch;
                     const uint64_t pbase_d = d_off + (cpslot ? (uint64_t)cpslot[meta.pred_begin + pe] * pitch : pbase);
+                    if constexpr (K == 8) {
                     const bool in = act && c0 - pb < WIN;   // (unsigned: also false left of that window)
                     uint4 m0 = make_uint4(INF2, INF2, INF2, INF2), d0 = m0, m1 = m0, d1 = m0;
                     if (in) {
@@ -640,6 +715,35 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
                     for (int i = 0; i < 4; ++i) {
                         tm[2 * i] = pk_lo_lo(a0[i], a1[i]); tm[2 * i + 1] = pk_hi_hi(a0[i], a1[i]);
                         td[2 * i] = pk_lo_lo(b0[i], b1[i]); td[2 * i + 1] = pk_hi_hi(b0[i], b1[i]);
+                    }
+                    } else {
+                        // per dword: inside the plane row and inside the predecessor's window (both edges are even columns, so a
+                        // dword's two columns lie on one side; unsigned: also false left of that window)
+                        const uint32_t off = c0 - pb;
+                        const bool in0 = nd > 0u && off < WIN, in1 = nd > 1u && off + 2u < WIN, in2 = nd > 2u && off + 4u < WIN;
+                        uint32_t a0[3] = {INF2, INF2, INF2}, a1[3] = {INF2, INF2, INF2}, b0[3] = {INF2, INF2, INF2}, b1[3] = {INF2, INF2, INF2};
+                        if (in0 && in2) {   // (then in1 as well) the whole lane
+                            const uint3 m0 = *reinterpret_cast<const uint3*>(Mp_a + pbase + c0), d0 = *reinterpret_cast<const uint3*>(Mp_a + pbase_d + c0);
+                            const uint3 m1 = *reinterpret_cast<const uint3*>(Mp_b + pbase + c0), d1 = *reinterpret_cast<const uint3*>(Mp_b + pbase_d + c0);
+                            a0[0] = m0.x; a0[1] = m0.y; a0[2] = m0.z; a1[0] = m1.x; a1[1] = m1.y; a1[2] = m1.z;
+                            b0[0] = d0.x; b0[1] = d0.y; b0[2] = d0.z; b1[0] = d1.x; b1[1] = d1.y; b1[2] = d1.z;
+                        } else {
+                            const bool ins[3] = {in0, in1, in2};
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) {
+                                if (ins[i]) {
+                                    a0[i] = *reinterpret_cast<const uint32_t*>(Mp_a + pbase + c0 + 2 * i);
+                                    b0[i] = *reinterpret_cast<const uint32_t*>(Mp_a + pbase_d + c0 + 2 * i);
+                                    a1[i] = *reinterpret_cast<const uint32_t*>(Mp_b + pbase + c0 + 2 * i);
+                                    b1[i] = *reinterpret_cast<const uint32_t*>(Mp_b + pbase_d + c0 + 2 * i);
+                                }
+                            }
+                        }
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            tm[2 * i] = pk_lo_lo(a0[i], a1[i]); tm[2 * i + 1] = pk_hi_hi(a0[i], a1[i]);
+                            td[2 * i] = pk_lo_lo(b0[i], b1[i]); td[2 * i + 1] = pk_hi_hi(b0[i], b1[i]);
+                        }
                     }
                     // strip the flags; the 14-bit INF becomes the 16-bit one again
                     constexpr uint32_t VM = 0x3FFF3FFFu;
@@ -661,12 +765,24 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
 
     // A window move, as in <false>: a row array of both queries goes through LDS and comes back at the new columns; what the
     // old window did not hold is INF.  Bases are multiples of 8: a lane's eight columns lie inside the old window or outside.
+    // K = 6: the buffer holds the old window dword by dword ([array][query][WIN / 2]); a shift is a multiple of 8 columns, so my
+    // three dwords are three dwords of the old window, each of them inside it or not on its own.
+    uint32_t* my_move1 = reinterpret_cast<uint32_t*>(my_move);
     auto move_put = [&](int slot, const uint32_t (&a)[K]) {
+        if constexpr (K == 8) {
         my_move[(slot * 2) * 64 + lane] = make_uint4(pk_lo_lo(a[0], a[1]), pk_lo_lo(a[2], a[3]), pk_lo_lo(a[4], a[5]), pk_lo_lo(a[6], a[7]));
         my_move[(slot * 2 + 1) * 64 + lane] = make_uint4(pk_hi_hi(a[0], a[1]), pk_hi_hi(a[2], a[3]), pk_hi_hi(a[4], a[5]), pk_hi_hi(a[6], a[7]));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                my_move1[(slot * 2) * (WIN / 2) + 3 * lane + i] = pk_lo_lo(a[2 * i], a[2 * i + 1]);
+                my_move1[(slot * 2 + 1) * (WIN / 2) + 3 * lane + i] = pk_hi_hi(a[2 * i], a[2 * i + 1]);
+            }
+        }
     };
     auto move_get = [&](int slot, const uint32_t shift, uint32_t (&a)[K]) {
         const uint32_t o = shift + K * lane;   // my new columns as columns of the old window
+        if constexpr (K == 8) {
         uint4 v0 = make_uint4(INF2, INF2, INF2, INF2), v1 = v0;
         if (o < WIN) {
             v0 = my_move[(slot * 2) * 64 + (o >> 3)];
@@ -674,6 +790,18 @@ __global__ __launch_bounds__(256) void poa_forward_band2_kernel(FwdParams P, Ban
         }
         a[0] = pk_lo_lo(v0.x, v1.x); a[1] = pk_hi_hi(v0.x, v1.x); a[2] = pk_lo_lo(v0.y, v1.y); a[3] = pk_hi_hi(v0.y, v1.y);
         a[4] = pk_lo_lo(v0.z, v1.z); a[5] = pk_hi_hi(v0.z, v1.z); a[6] = pk_lo_lo(v0.w, v1.w); a[7] = pk_hi_hi(v0.w, v1.w);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint32_t oc = o + 2u * i;   // (unsigned: a column left of the old window tests as outside)
+                uint32_t v0 = INF2, v1 = INF2;
+                if (oc < WIN) {
+                    v0 = my_move1[(slot * 2) * (WIN / 2) + (oc >> 1)];
+                    v1 = my_move1[(slot * 2 + 1) * (WIN / 2) + (oc >> 1)];
+                }
+                a[2 * i] = pk_lo_lo(v0, v1); a[2 * i + 1] = pk_hi_hi(v0, v1);
+            }
+        }
     };
 
     uint32_t MA[K], DA[K], MB[K], DB[K];
