@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "poa_forward_px.hpp"
+#include "poa_forward_sweep.hpp"
 #include "poa_sweep_rows.hpp"
 
 namespace poa_amd {
@@ -431,12 +432,10 @@ __device__ inline TbStep ckpt_step(const CkptCells<T>& c, uint32_t row, uint32_t
     return first;
 }
 
+// Pass 2 of one query, by its wave: the driver of the walk, shared by poa_ckpt_trace_kernel and poa_ckpt_trace_multi_kernel
+// (poa_multi.hpp).  `wq` places the query's strip carries (ckpt_rows).
 template <int Q, typename T>
-__global__ __launch_bounds__(256) void poa_ckpt_trace_kernel(CkptParams P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
-    if (wq >= P.n_queries) return;
-    const uint32_t qi = P.first_query + wq;
+__device__ __forceinline__ void ckpt_trace_query(const CkptParams& P, const uint32_t qi, const uint32_t wq, const uint32_t lane) {
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* __restrict__ q = P.qseq + qbeg;
@@ -447,7 +446,6 @@ __global__ __launch_bounds__(256) void poa_ckpt_trace_kernel(CkptParams P) {
     auto emit_at = [&](uint32_t pos, uint32_t rpos, uint32_t qpos) {
         if (pos < cap) out[cap - 1 - pos] = make_uint2(rpos, qpos);
     };
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     const uint32_t end_node = P.rows[P.end_row].node;
 
     // the walk's state, wave-uniform between the segments
@@ -522,8 +520,8 @@ __global__ __launch_bounds__(256) void poa_ckpt_trace_kernel(CkptParams P) {
                 w_row = bt.row; w_j = bt.j; w_st = bt.st;
             }
         }
-        crow = uni(w_row); cj = uni(w_j); cst = uni(w_st); cnt = uni(w_cnt); flags = uni(w_flags);
-        done = uni(w_done); reached_start = uni(w_reached);
+        crow = wave_uni(w_row); cj = wave_uni(w_j); cst = wave_uni(w_st); cnt = wave_uni(w_cnt); flags = wave_uni(w_flags);
+        done = wave_uni(w_done); reached_start = wave_uni(w_reached);
         first_hop = 0;
     }
     if (!reached_start) flags |= POA_FLAG_TRUNCATED;
@@ -531,6 +529,18 @@ __global__ __launch_bounds__(256) void poa_ckpt_trace_kernel(CkptParams P) {
         P.flags[qi] = flags;
         P.n_pairs[qi] = cnt < cap ? cnt : cap;
     }
+}
+
+// At least three waves per SIMD: every instantiation meets that, <4, uint32_t> with exactly the 168 VGPRs it allows, and without
+// the floor the register allocator settles it at 184 or at 168 by the order of unrelated statements (profiles/pr_ckpt_walk/).
+// The floor binds all five: a change that pushes <2, uint16_t> (166 VGPRs) or <4, uint32_t> past 168 no longer drops a wave, it
+// spills to scratch without a word.  `make resources` (csrc/Makefile) shows it: ScratchSize must stay 0 for these kernels.
+template <int Q, typename T>
+__global__ __launch_bounds__(256, 3) void poa_ckpt_trace_kernel(CkptParams P) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wq = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
+    if (wq >= P.n_queries) return;
+    ckpt_trace_query<Q, T>(P, P.first_query + wq, wq, lane);
 }
 
 }  // namespace poa_amd

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "poa_forward_sweep.hpp"
 #include "poa_sweep_rows.hpp"
 
 namespace poa_amd {
@@ -227,10 +228,10 @@ struct Ckpt2Cells {
     }
 };
 
+// Pass 2 of one query, by its wave: the driver of the walk, shared by poa2_ckpt_trace_kernel and poa2_ckpt_trace_multi_kernel
+// (poa_multi.hpp).  `wq` places the query's strip carries (ckpt2_rows).
 template <typename T, int NP>
-__global__ __launch_bounds__(64) void poa2_ckpt_trace_kernel(Ckpt2Params P) {
-    const uint32_t lane = threadIdx.x, wq = blockIdx.x;
-    const uint32_t qi = P.first_query + wq;
+__device__ __forceinline__ void ckpt2_trace_query(const Ckpt2Params& P, const uint32_t qi, const uint32_t wq, const uint32_t lane) {
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* q = P.qseq + qbeg;
@@ -241,7 +242,6 @@ __global__ __launch_bounds__(64) void poa2_ckpt_trace_kernel(Ckpt2Params P) {
     W.x = P.x; W.o1 = P.o1; W.e1 = P.e1; W.e2 = P.e2;
     W.out = P.scratch + P.scratch_off[qi];
     W.cap = (uint32_t)(P.scratch_off[qi + 1] - P.scratch_off[qi]);
-    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
 
     // the walk's state, wave-uniform between the segments
     TpWalk S{P.end_row, L, TP_SM, 0, 0, false, false};
@@ -263,14 +263,20 @@ __global__ __launch_bounds__(64) void poa2_ckpt_trace_kernel(Ckpt2Params P) {
             if (first_hop) tp_walk_begin(W, C, Wk, P.end_row, L, POA_FLAG_SHORT_QUERY);
             tp_walk_run(W, C, Wk, b0);
         }
-        S.row = uni(Wk.row); S.j = uni(Wk.j); S.st = uni(Wk.st); S.n_out = uni(Wk.n_out); S.fl = uni(Wk.fl);
-        S.done = uni(Wk.done ? 1u : 0u) != 0; S.reached_start = uni(Wk.reached_start ? 1u : 0u) != 0;
+        S.row = wave_uni(Wk.row); S.j = wave_uni(Wk.j); S.st = wave_uni(Wk.st); S.n_out = wave_uni(Wk.n_out); S.fl = wave_uni(Wk.fl);
+        S.done = wave_uni(Wk.done ? 1u : 0u) != 0; S.reached_start = wave_uni(Wk.reached_start ? 1u : 0u) != 0;
         first_hop = false;
     }
     if (lane == 0) {
         P.flags[qi] = tp_walk_flags(S);
         P.n_pairs[qi] = S.n_out < W.cap ? S.n_out : W.cap;
     }
+}
+
+template <typename T, int NP>
+__global__ __launch_bounds__(64) void poa2_ckpt_trace_kernel(Ckpt2Params P) {
+    const uint32_t lane = threadIdx.x, wq = blockIdx.x;
+    ckpt2_trace_query<T, NP>(P, P.first_query + wq, wq, lane);
 }
 
 }  // namespace poa_amd

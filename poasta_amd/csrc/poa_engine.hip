@@ -36,7 +36,6 @@
 #include "poa_checkpoint2.hpp"
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
-#include "poa_multi2.hpp"
 #include "poa_scoreset_plan.hpp"
 #include "poa_scoreset.hpp"
 
@@ -2685,7 +2684,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     return run.end_pairs();
 }
 
-// The same run under the two-piece model (poa_multi2.hpp), on a batch of poa_multi_create_2piece: the cell width by the first
+// The same run under the two-piece model (poa_multi.hpp), on a batch of poa_multi_create_2piece: the cell width by the first
 // piece's bound for every graph that has queries, the chunks of the batch under either width.
 int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");

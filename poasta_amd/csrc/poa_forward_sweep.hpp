@@ -95,6 +95,9 @@ struct SweepBest {
     }
 };
 
+// a wave-uniform value as the compiler sees one: the first active lane's, in an SGPR
+__device__ __forceinline__ uint32_t wave_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
 // minimum over the 64 lanes, uniform: the DPP steps of wave_scan_min_plus without the weights, lane 63 ends with the total
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     v = umin(v, dpp_or_inf<0x111, 0xF>(v));

@@ -1,36 +1,40 @@
-// Multi-graph checkpointed batches (poa_multi_*) for gfx950: the two passes of poa_checkpoint.hpp over the queries of many
-// graphs in one launch.  One wavefront per query in both passes, as there; nothing is ordered between waves,
-// so the four waves of a block may belong to four graphs.
+// Multi-graph checkpointed batches (poa_multi_*, poa_multi_*_2piece) for gfx950: the two passes of poa_checkpoint.hpp, or of
+// poa_checkpoint2.hpp under the two-piece model, over the queries of many graphs in one launch.  One wavefront
+// per query in both passes, as there; nothing is ordered between waves, so the four waves of a block may belong to four graphs.
 //
-// What a single-graph launch passes as its kernel argument, CkptParams, lies here once per graph in a device array.  A wave
-// reads its query's graph id, copies that graph's block into registers, patches what belongs to the launch (the chunk, the
-// costs, its own strip carries) and calls the SAME row body (ckpt_rows) and the SAME walk rule (ckpt_step) as the
-// single-graph kernels, which take `const CkptParams&` and never see where it came from.  The graph id goes through
-// readfirstlane, and so does the wave's query index (threadIdx.x >> 6 is wave-uniform, but not provably so for the compiler):
-// the block's address is then a scalar, the copy is a run of scalar loads into SGPRs, and every table pointer and row count the
-// bodies use stays as uniform as a kernel argument is.
+// What a single-graph launch passes as its kernel argument, CkptParams or Ckpt2Params, lies here once per graph in a device
+// array (MultiGraphBlock).  A wave reads its query's graph id, copies that graph's block into registers and patches what belongs
+// to the launch: the chunk, the costs, its own strip carries (multi_load).  From there on the kernels here ARE the single-graph
+// ones: pass 1 calls the same row body (ckpt_rows, ckpt2_rows), pass 2 the same per-query driver of the walk (ckpt_trace_query,
+// ckpt2_trace_query), which take `const CkptParams&` / `const Ckpt2Params&` and never see where it came from.  The graph id goes
+// through readfirstlane (wave_uni), and so does the wave's query index (threadIdx.x >> 6 is wave-uniform, but not provably so
+// for the compiler): the block's address is then a scalar, the copy is a run of scalar loads into SGPRs, and every table pointer
+// and row count the bodies use stays as uniform as a kernel argument is.
 //
-// Strip carries: ckpt_rows addresses carry + 4 * wq * P.n_rows, a stride that holds for one graph only.  Here every query has
-// its own offset into the chunk's carry buffer (MultiPlan::carry_off: 4 x n_rows(graph) words for a query wider than one
-// strip, nothing for the others); the wave sets P.carry to its own place and calls the body with wq = 0.
-//
-// The driver of the walk — the loop over the segments around ckpt_rows<PASS 2> and ckpt_step, with the first hop's fall-backs —
-// is restated here from poa_ckpt_trace_kernel, statement for statement: it lives inside that __global__ function, and the
-// single-graph kernels stay as they are.  A change to the walk there has to be made here too; tests/test_multi_graph.py
-// compares both families on the same inputs, pair for pair.
+// Strip carries: the row bodies address carry + 4 * wq * P.n_rows (two-piece: 6 *), a stride that holds for one graph only.
+// Here every query has its own offset into the chunk's carry buffer (MultiPlan::carry_off: 4 or 6 x n_rows(graph) words for a
+// query wider than one strip, nothing for the others); the wave sets P.carry to its own place and calls the body with wq = 0.
+// A two-piece strip is 64 lanes x K x NP columns: 1024 for <uint16_t, 2> and <uint32_t, 4>, the widest variants, and at least
+// the chunk's largest pitch for every smaller variant the launch code selects, so a query of pitch <= 1024 never touches a carry.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "poa_checkpoint.hpp"
+#include "poa_checkpoint2.hpp"
 
 namespace poa_amd {
 
-struct MultiGraphParams {
-    CkptParams P;          // everything of the graph and of the batch; first_query, n_queries, carry and the costs are patched per wave
+template <typename KP>
+struct MultiGraphBlock {
+    KP P;                  // everything of the graph and of the batch; first_query, n_queries, carry and the costs are patched per wave
     uint32_t empty;        // the graph has no real nodes: score 4 * len, POA_FLAG_EMPTY_GRAPH, no pairs (PoastaAligner::align, mod.rs:124-142)
     uint32_t pad;
 };
+using MultiGraphParams = MultiGraphBlock<CkptParams>;
+using Multi2GraphParams = MultiGraphBlock<Ckpt2Params>;
+static_assert(sizeof(MultiGraphParams) == sizeof(CkptParams) + 8 && sizeof(Multi2GraphParams) == sizeof(Ckpt2Params) + 8,
+              "a block is its parameters, then empty and pad: what the host fills and uploads");
 
 struct MultiLaunch {
     const MultiGraphParams* graphs;   // [n_graphs]
@@ -41,20 +45,31 @@ struct MultiLaunch {
     uint32_t cost_x, cost_o, cost_e;
 };
 
-__device__ __forceinline__ uint32_t multi_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+struct Multi2Launch {
+    const Multi2GraphParams* graphs;  // [n_graphs]
+    const uint32_t* graph_of, *carry_off;   // as in MultiLaunch
+    uint32_t* carry;
+    uint32_t first_query, n_queries;  // the chunk
+    uint32_t x, oe, o1, e1, e2;
+};
+
+// the costs of the run: the one part of a block's patch that depends on the model
+__device__ __forceinline__ void multi_costs(const MultiLaunch& A, CkptParams& P) { P.cost_x = A.cost_x; P.cost_o = A.cost_o; P.cost_e = A.cost_e; }
+__device__ __forceinline__ void multi_costs(const Multi2Launch& A, Ckpt2Params& P) { P.x = A.x; P.oe = A.oe; P.o1 = A.o1; P.e1 = A.e1; P.e2 = A.e2; }
 
 // the wave's query and its graph's parameter block; false: no query for this wave
-__device__ __forceinline__ bool multi_load(const MultiLaunch& A, uint32_t& qi, CkptParams& P, uint32_t& empty) {
-    const uint32_t wq = multi_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+template <typename Launch, typename KP>
+__device__ __forceinline__ bool multi_load(const Launch& A, uint32_t& qi, KP& P, uint32_t& empty) {
+    const uint32_t wq = wave_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (wq >= A.n_queries) return false;
     qi = A.first_query + wq;
-    const uint32_t gid = multi_uni(A.graph_of[qi]);
-    const MultiGraphParams* __restrict__ gp = A.graphs + gid;
+    const uint32_t gid = wave_uni(A.graph_of[qi]);
+    const MultiGraphBlock<KP>* __restrict__ gp = A.graphs + gid;
     P = gp->P;
     empty = gp->empty;
     P.first_query = A.first_query; P.n_queries = A.n_queries;
-    P.carry = A.carry + multi_uni(A.carry_off[qi]);
-    P.cost_x = A.cost_x; P.cost_o = A.cost_o; P.cost_e = A.cost_e;
+    P.carry = A.carry + wave_uni(A.carry_off[qi]);
+    multi_costs(A, P);
     return true;
 }
 
@@ -77,99 +92,37 @@ __global__ __launch_bounds__(256) void poa_ckpt_sweep_multi_kernel(MultiLaunch A
 
 template <int Q, typename T>
 __global__ __launch_bounds__(256) void poa_ckpt_trace_multi_kernel(MultiLaunch A) {
-    const uint32_t lane = threadIdx.x & 63u;
     uint32_t qi, empty;
     CkptParams P;
     if (!multi_load(A, qi, P, empty)) return;
     if (empty) return;   // pass 1 wrote the result
+    ckpt_trace_query<Q, T>(P, qi, 0u, threadIdx.x & 63u);
+}
+
+template <typename T, int NP>
+__global__ __launch_bounds__(256) void poa2_ckpt_sweep_multi_kernel(Multi2Launch A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t qi, empty;
+    Ckpt2Params P;
+    if (!multi_load(A, qi, P, empty)) return;
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
-    const uint8_t* __restrict__ q = P.qseq + qbeg;
+    if (empty) {
+        if (lane == 0) { P.score[qi] = L * 4u; P.flags[qi] = POA_FLAG_EMPTY_GRAPH; P.n_pairs[qi] = 0; }
+        return;
+    }
     const uint32_t pitch = P.pitch[qi];
-    const CkptRegion<T> R(P, qi, pitch);
-    uint2* out = P.scratch + P.scratch_off[qi];
-    const uint32_t cap = (uint32_t)(P.scratch_off[qi + 1] - P.scratch_off[qi]);
-    auto emit_at = [&](uint32_t pos, uint32_t rpos, uint32_t qpos) {
-        if (pos < cap) out[cap - 1 - pos] = make_uint2(rpos, qpos);
-    };
-    const uint32_t end_node = P.rows[P.end_row].node;
+    const Ckpt2Region<T> R(P, qi, pitch);
+    ckpt2_rows<T, NP, 1>(P, R, qi, 0u, lane, 0u, P.n_rows, pitch, L, P.qseq + qbeg);
+}
 
-    // the walk's state, wave-uniform between the segments (poa_ckpt_trace_kernel)
-    uint32_t crow = P.end_row, cj = L, cst = 0, cnt = 0, flags = 0;
-    uint32_t done = 0, reached_start = 0, first_hop = 1;
-    if (L == 0) { done = 1; reached_start = 1; }
-    else if (L == 1) {
-        flags |= POA_FLAG_SHORT_QUERY;
-        if (lane == 0) emit_at(0, end_node, 0);
-        cnt = 1; done = 1; reached_start = 1;
-    }
-    uint32_t seg = P.n_segments - 1;
-    while (!done) {
-        while (crow < P.boundary[seg]) --seg;
-        const uint32_t b0 = P.boundary[seg], b1 = P.boundary[seg + 1];
-        ckpt_rows<Q, T, 2>(P, R, qi, 0u, lane, b0, b1, pitch, L, q);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // lane 0 reads what all lanes stored
-        uint32_t w_row = crow, w_j = cj, w_st = cst, w_cnt = cnt, w_flags = flags, w_done = 0, w_reached = 0;
-        if (lane == 0) {
-            CkptCells<T> c;
-            c.rows = P.rows; c.pred_rows = P.pred_rows; c.pred_src = P.pred_src;
-            c.win_m = R.win_m; c.win_i = R.win_i; c.win_d = R.win_d; c.snap_m = R.snap_m; c.snap_d = R.snap_d;
-            c.q = q; c.b0 = b0; c.pitch = pitch; c.L = L; c.x = P.cost_x; c.o = P.cost_o; c.e = P.cost_e;
-            if (first_hop) {
-                uint32_t nc, fallback = 0;
-                bool bad = false, pn = false;
-                TbStep cur = ckpt_step<T>(c, w_row, w_j, 0, nc, bad, pn);
-                if (cur.found && !pn && (nc != 1 || bad)) w_flags |= POA_FLAG_AMBIGUOUS;
-                if (!cur.found && !pn) {
-                    cur = ckpt_step<T>(c, w_row, w_j, 2, nc, bad, pn);
-                    if (!cur.found && !pn) cur = ckpt_step<T>(c, w_row, w_j, 1, nc, bad, pn);
-                    if (!pn) {
-                        if (!cur.found) { w_flags |= POA_FLAG_REF_PANIC; fallback = 1; }
-                        else w_flags |= POA_FLAG_AMBIGUOUS;
-                    }
-                }
-                if (pn) { w_flags |= POA_FLAG_REF_PANIC; fallback = 2; }
-                if (fallback) {
-                    if (fallback == 2) w_flags |= POA_FLAG_TRUNCATED;
-                    if (fallback == 1 && L <= 3) {
-                        for (uint32_t k = 0; k < L; ++k) emit_at(k, end_node, L - 1 - k);
-                        w_cnt = L;
-                    }
-                    w_done = 1; w_reached = 1;
-                } else {
-                    w_row = cur.row; w_j = cur.j; w_st = cur.st;
-                }
-            }
-            while (!w_done && w_row >= b0) {
-                uint32_t nc;
-                bool bad = false, pn = false;
-                const TbStep bt = ckpt_step<T>(c, w_row, w_j, w_st, nc, bad, pn);
-                if (pn) { w_flags |= POA_FLAG_REF_PANIC; w_done = 1; break; }
-                if (!bt.found) { w_done = 1; break; }
-                if (nc != 1 || bad) w_flags |= POA_FLAG_AMBIGUOUS;
-                if (w_st == 0 && bt.st != 0) {
-                    w_row = bt.row; w_j = bt.j; w_st = bt.st;
-                    continue;
-                }
-                if (w_st == 0) emit_at(w_cnt, bt.node, w_j - 1);
-                else if (w_st == 2) emit_at(w_cnt, POA_NONE, w_j - 1);
-                else emit_at(w_cnt, bt.node, POA_NONE);
-                w_cnt += 1;
-                if (bt.st == 0 && bt.j == 0 && bt.row != P.start_row && w_st != 1 && (uint32_t)P.rows[bt.row].sym == (uint32_t)q[0])
-                    w_flags |= POA_FLAG_START_QUIRK;
-                if (bt.row == P.start_row) { w_reached = 1; w_done = 1; break; }
-                w_row = bt.row; w_j = bt.j; w_st = bt.st;
-            }
-        }
-        crow = multi_uni(w_row); cj = multi_uni(w_j); cst = multi_uni(w_st); cnt = multi_uni(w_cnt); flags = multi_uni(w_flags);
-        done = multi_uni(w_done); reached_start = multi_uni(w_reached);
-        first_hop = 0;
-    }
-    if (!reached_start) flags |= POA_FLAG_TRUNCATED;
-    if (lane == 0) {
-        P.flags[qi] = flags;
-        P.n_pairs[qi] = cnt < cap ? cnt : cap;
-    }
+template <typename T, int NP>
+__global__ __launch_bounds__(256) void poa2_ckpt_trace_multi_kernel(Multi2Launch A) {
+    uint32_t qi, empty;
+    Ckpt2Params P;
+    if (!multi_load(A, qi, P, empty)) return;
+    if (empty) return;   // pass 1 wrote the result
+    ckpt2_trace_query<T, NP>(P, qi, 0u, threadIdx.x & 63u);
 }
 
 }  // namespace poa_amd

@@ -26,7 +26,7 @@
 //                4 x n_rows(graph) words there.  Every variant the launch code selects for a chunk has strips of at least the
 //                chunk's largest pitch when that pitch is <= 1024, so a query of pitch <= 1024 never touches a carry.
 //
-// The two-piece variant (poa_multi_*_2piece, poa_multi2.hpp; `two_piece` below) is the same plan with the two-piece weights:
+// The two-piece variant (poa_multi_*_2piece, poa_multi.hpp; `two_piece` below) is the same plan with the two-piece weights:
 // per graph the two-piece CheckpointPlan (three kept planes, five window planes: what poa_graph_checkpoint_plan2 gives for
 // that graph alone; MultiGraphIn::own is then the handle's two-piece plan), and 6 x n_rows carry words for a query wider than
 // one strip (ckpt2_rows: two parities of three words per row).  Its strips are 1024 columns under both cell types too.

@@ -55,17 +55,15 @@ struct ScoreSetCapLaunch {
     const RowMeta* rows_base;         // start of the concatenated row tables: a graph's rows - rows_base is its base in check_rows
 };
 
-__device__ __forceinline__ uint32_t scoreset_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
 // the wave's pair, its query and its graph's parameter block; false: nothing to compute for this wave (no pair, or a pair
 // against a graph without real nodes, whose shortcut result is written here)
 __device__ __forceinline__ bool scoreset_load(const ScoreSetLaunch& A, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
                                               const uint8_t*& q) {
-    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t w = wave_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (w >= A.n) return false;
-    p = scoreset_uni(A.list[w]);
-    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
-    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    p = wave_uni(A.list[w]);
+    const uint32_t gid = wave_uni(A.pair_graph[p]);
+    const uint32_t qid = wave_uni(A.pair_query[p]);
     const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
     P = gp->P;
     const uint32_t empty = gp->empty;
@@ -85,11 +83,11 @@ __device__ __forceinline__ bool scoreset_load(const ScoreSetLaunch& A, uint32_t 
 __device__ __forceinline__ bool scoreset_load_capped(const ScoreSetCapLaunch& C, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
                                                      const uint8_t*& q) {
     const ScoreSetLaunch& A = C.A;
-    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t w = wave_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (w >= A.n) return false;
-    p = scoreset_uni(A.list[w]);
-    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
-    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    p = wave_uni(A.list[w]);
+    const uint32_t gid = wave_uni(A.pair_graph[p]);
+    const uint32_t qid = wave_uni(A.pair_query[p]);
     const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
     P = gp->P;
     const uint32_t empty = gp->empty;
@@ -111,7 +109,7 @@ __device__ __forceinline__ bool scoreset_load_capped(const ScoreSetCapLaunch& C,
 
 // the pair's cap and its graph's check rows, uniform like the pair's ids
 __device__ __forceinline__ SweepCap scoreset_cap(const ScoreSetCapLaunch& C, const SweepParams& P, uint32_t p) {
-    return SweepCap{scoreset_uni(C.cap[p]), C.check_rows + (P.rows - C.rows_base), C.swept};
+    return SweepCap{wave_uni(C.cap[p]), C.check_rows + (P.rows - C.rows_base), C.swept};
 }
 
 template <int Q, typename T>
@@ -121,8 +119,8 @@ __global__ __launch_bounds__(256) void poa_scoreset_sweep_kernel(ScoreSetLaunch 
     const uint8_t* q;
     SweepParams P;
     if (!scoreset_load(A, lane, p, P, L, q)) return;
-    sweep_rows<Q, T>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
-                     A.carry + scoreset_uni(A.carry_off[p]));
+    sweep_rows<Q, T>(P, p, lane, L, q, wave_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                     A.carry + wave_uni(A.carry_off[p]));
 }
 
 // pairs of one strip, 512 < pitch <= 1024, on a u16 run: slot rows in the packed kernel's register layout, 2048 bytes each
@@ -143,8 +141,8 @@ __global__ __launch_bounds__(256) void poa_scoreset_sweep_capped_kernel(ScoreSet
     const uint8_t* q;
     SweepParams P;
     if (!scoreset_load_capped(C, lane, p, P, L, q)) return;
-    sweep_rows<Q, T, SweepCap>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
-                           A.carry + scoreset_uni(A.carry_off[p]), scoreset_cap(C, P, p));
+    sweep_rows<Q, T, SweepCap>(P, p, lane, L, q, wave_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                           A.carry + wave_uni(A.carry_off[p]), scoreset_cap(C, P, p));
 }
 
 __global__ __launch_bounds__(256) void poa_scoreset_sweep_px_capped_kernel(ScoreSetCapLaunch C) {
@@ -182,11 +180,11 @@ static_assert(sizeof(ScoreSetBest) == 32, "poa_best_t is 32 bytes");
 __device__ __forceinline__ bool scoreset_load_best(const ScoreSetBestLaunch& B, uint32_t lane, uint32_t& p, SweepParams& P, uint32_t& L,
                                                    const uint8_t*& q, SweepBest& cap) {
     const ScoreSetLaunch& A = B.A;
-    const uint32_t w = scoreset_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t w = wave_uni((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (w >= A.n) return false;
-    p = scoreset_uni(A.list[w]);
-    const uint32_t gid = scoreset_uni(A.pair_graph[p]);
-    const uint32_t qid = scoreset_uni(A.pair_query[p]);
+    p = wave_uni(A.list[w]);
+    const uint32_t gid = wave_uni(A.pair_graph[p]);
+    const uint32_t qid = wave_uni(A.pair_query[p]);
     const ScoreGraphParams* __restrict__ gp = A.graphs + gid;
     P = gp->P;
     const uint32_t empty = gp->empty;
@@ -194,7 +192,7 @@ __device__ __forceinline__ bool scoreset_load_best(const ScoreSetBestLaunch& B, 
     const uint64_t qbeg = A.qoff[qid];
     L = (uint32_t)(A.qoff[qid + 1] - qbeg);
     q = A.qseq + qbeg;
-    cap = SweepBest{B.best + qid, B.slack, scoreset_uni(B.limit[qid]), B.check_rows + (P.rows - B.rows_base), B.swept};
+    cap = SweepBest{B.best + qid, B.slack, wave_uni(B.limit[qid]), B.check_rows + (P.rows - B.rows_base), B.swept};
     if (empty) {
         if (lane == 0) {
             const bool over = L * 4u > cap.now_lane();
@@ -217,8 +215,8 @@ __global__ __launch_bounds__(256) void poa_scoreset_sweep_best_kernel(ScoreSetBe
     SweepParams P;
     SweepBest cap;
     if (!scoreset_load_best(B, lane, p, P, L, q, cap)) return;
-    sweep_rows<Q, T, SweepBest>(P, p, lane, L, q, scoreset_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
-                                A.carry + scoreset_uni(A.carry_off[p]), cap);
+    sweep_rows<Q, T, SweepBest>(P, p, lane, L, q, wave_uni(A.pitch[p]), reinterpret_cast<T*>(A.planes + A.region_off[p]),
+                                A.carry + wave_uni(A.carry_off[p]), cap);
 }
 
 __global__ __launch_bounds__(256) void poa_scoreset_sweep_px_best_kernel(ScoreSetBestLaunch B) {

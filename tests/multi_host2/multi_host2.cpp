@@ -1,7 +1,7 @@
 // Stand-alone check of the multi-graph plan under the two-piece model (poasta_amd/csrc/poa_multi_plan.cpp, two_piece = true):
 // built by tests/test_multi_plan_2piece.py together with the plan, the sweep rows and the graph flattening under
 // -fsanitize=address,undefined, and run on the CPU.  It plans the shapes of tests/test_multi_graph_2piece.py (tests 1-3) and
-// checks what the kernels of poa_multi2.hpp rely on: every offset in bounds, the regions of a chunk disjoint, the chunks
+// checks what the kernels of poa_multi.hpp rely on: every offset in bounds, the regions of a chunk disjoint, the chunks
 // covering every query exactly once, six carry words per graph row for a query wider than one strip and none for the others.
 // Exit code 0 and "multi_host2 ok" on success.
 #include <algorithm>

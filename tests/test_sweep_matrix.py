@@ -1,5 +1,5 @@
 """The one-wavefront-per-query kernels — sweep_rows / sweep_px_rows (poa_forward_sweep.hpp), ckpt_rows and the walk behind it
-(poa_checkpoint.hpp), their copies and wrappers in poa_multi.hpp, poa_multi2.hpp, poa_checkpoint2.hpp and poa_scoreset.hpp — at
+(poa_checkpoint.hpp), their two-piece form in poa_checkpoint2.hpp and their wrappers in poa_multi.hpp and poa_scoreset.hpp — at
 every instantiation the launchers can pick and at the column, strip and segment edges.
 
 CPU: tests/sweep_model.py restates what the eight paths launch; `CASES` lists every batch the GPU tests below run, and one test
