@@ -609,4 +609,5 @@ int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 #endif
 #include "poasta_amd_scoreset_cap.h"
 #include "poasta_amd_scoreset_best.h"
+#include "poasta_amd_tb.h"
 #endif /* POASTA_AMD_H */

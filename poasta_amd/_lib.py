@@ -38,6 +38,9 @@ EXPORTS_SCORESET_CAP = ["poa_scoreset_run_capped", "poa_scoreset_run_2piece_capp
 EXPORTS_SCORESET_BEST = ["poa_scoreset_run_best", "poa_scoreset_run_2piece_best", "poa_scoreset_fetch_best", "poa_scoreset_device_best",
                          "poa_score_best", "poa_score_best_2piece"]
 CFG_BEST_PAIR_ORDER = 2
+# every symbol include/poasta_amd_tb.h declares (checked by tests/test_tb_lean.py)
+EXPORTS_TB = ["poa_batch_tb_info"]
+TB_LEAN_SHIFT = 4
 
 
 class PoaBest(C.Structure):
@@ -88,6 +91,12 @@ def tune_from_env(cfg=None, **overrides):
     if nv is not None and nv != "":
         i = TUNE_KEYS.index("BAND_PAIR")
         vals[i] = (min(vals[i], 1) if i in vals else 2) | ((2 if int(nv) else 1) << 2)
+    # POA_TB_LEAN (0: never the lean traceback kernel, 1: wherever it is eligible) rides in the same entry, above the narrow tier's
+    # bits (poasta_amd_tb.h: POA_TB_LEAN_SHIFT)
+    lv = overrides.get("tb_lean", os.environ.get("POA_TB_LEAN"))
+    if lv is not None and lv != "":
+        i = TUNE_KEYS.index("BAND_PAIR")
+        vals[i] = (vals[i] if i in vals else 2) | ((2 if int(lv) else 1) << TB_LEAN_SHIFT)
     if cfg is None:
         if not vals:
             return None
@@ -125,7 +134,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -226,6 +235,9 @@ def lib():
     if hasattr(L, "poa_batch_band_narrow_info"):
         L.poa_batch_band_narrow_info.restype = C.c_int
         L.poa_batch_band_narrow_info.argtypes = [vp, vp]
+    if hasattr(L, "poa_batch_tb_info"):
+        L.poa_batch_tb_info.restype = C.c_int
+        L.poa_batch_tb_info.argtypes = [vp, vp]
     if hasattr(L, "poa_batch_last_launch"):
         L.poa_batch_last_launch.restype = C.c_int
         L.poa_batch_last_launch.argtypes = [vp, C.c_uint32, vp]

@@ -422,6 +422,13 @@ class ResidentBatch:
         _lib.check(_lib.lib().poa_batch_band_narrow_info(self.handle, out))
         return {"ran": int(out[0]), "certified": int(out[1]), "certified_512": int(out[2]), "chosen_by": (None, "rule", "override")[int(out[3])]}
 
+    def tb_info(self):
+        """The separate traceback launches of the last run's dense pass: {"kernel": None / "generic" / "lean", "lanes", "depth",
+        "walks"} (poa_batch_tb_info)."""
+        out = (C.c_uint32 * 4)()
+        _lib.check(_lib.lib().poa_batch_tb_info(self.handle, out))
+        return {"kernel": (None, "generic", "lean")[int(out[0])], "lanes": int(out[1]), "depth": int(out[2]), "walks": int(out[3])}
+
     def launches(self):
         """What the dense one-piece pass of the last run launched, one dict per chunk (poa_batch_last_launch): "kernel" in
         {"forward", "packed", "px", "pxmw", "band"}, "quads", "fuse", "mw", "waves", "code_fmt", "tb_lanes" (0: no separate

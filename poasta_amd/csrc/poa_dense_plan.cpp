@@ -78,14 +78,24 @@ DenseRunPlan plan_dense_run(uint32_t gap_open, uint32_t gap_extend, uint64_t max
     // two queries of one length per wave (poa_forward_band2_kernel): POA_BAND_PAIR=0 never, 1 whatever the count, else the rule
     // The tune table is full, so the same entry carries the override of the narrow tier (poasta_amd.h: POA_TUNE_BAND_PAIR):
     // bits 0..1 the pairing (0 never, 1 always, 2 by the rule), bits 2..3 the narrow tier (0 by the rule, 1 never, 2 whenever paired)
+    // ... and bits 4..5 the lean walk kernel (poasta_amd_tb.h: POA_TB_LEAN_SHIFT; 0 by the rule, 1 never, 2 wherever eligible)
     R.band_pair = -1;
     R.band_narrow = -1;
+    R.tb_lean = -1;
     if (const int* pv = T.ptr(POA_TUNE_BAND_PAIR)) {
-        const int p = (*pv) & POA_BAND_PAIR_MASK, n = ((*pv) >> POA_BAND_NARROW_SHIFT) & 3;
+        const int p = (*pv) & POA_BAND_PAIR_MASK, n = ((*pv) >> POA_BAND_NARROW_SHIFT) & 3, l = ((*pv) >> POA_TB_LEAN_SHIFT) & 3;
         if (p != POA_BAND_PAIR_RULE) R.band_pair = p != 0 ? 1 : 0;
         if (n) R.band_narrow = n - 1;
+        if (l == 1 || l == 2) R.tb_lean = l - 1;
     }
+    // hybrid and exact runs keep one walk kernel, the generic one, for their dense pass and for the walk after the replay
+    R.tb_lean_mode = mode == POA_MODE_DENSE;
     return R;
+}
+
+// The lean walk kernel wherever it is eligible: it is the same walk in fewer instructions, so the rule has no threshold.
+bool tb_lean_eligible(const DenseRunPlan& R, uint32_t tb_lanes, uint32_t code_fmt, uint64_t plane_elems) {
+    return R.tb_lean_mode && tb_lanes != 0 && R.compact && code_fmt == 4 && !R.relative && plane_elems < (1ull << 32);
 }
 
 // The narrow tier (poa_forward_band2_kernel<6>, a window of 384 columns) for a band class of query length L whose narrow plan has
@@ -107,7 +117,7 @@ uint32_t band_narrow_pairs(const DenseRunPlan& R, bool pair_by_rule, uint32_t n_
     return pair_by_rule ? n_rule : 0;
 }
 
-DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T) {
+DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T, uint64_t plane_elems) {
     // the launch record of this chunk (poa_batch_last_launch): kernel family, quads, fused walk, multi-wave, waves per workgroup
     uint32_t lk = POA_KERNEL_NONE, lq = 0, lwaves = 4, code_fmt = 0;
     bool lfuse = false, lmw = false;
@@ -176,7 +186,8 @@ DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t 
         ltb = R.compact ? (uint32_t)tbg : 64u;
         if (R.compact && !T.ptr(POA_TUNE_TB_DEPTH)) ldepth = tbg == 16 ? 16u : 32u;
     }
-    return {{lk, lq, (lfuse ? POA_LAUNCH_FUSE : 0u) | (lmw ? POA_LAUNCH_MW : 0u), lwaves, code_fmt, ltb, ldepth, count}, mf, lk == POA_KERNEL_BAND, ltb != 0};
+    const bool lean = R.tb_lean != 0 && tb_lean_eligible(R, ltb, code_fmt, plane_elems);   // POA_TB_LEAN=0: never; 1 and the rule: wherever eligible
+    return {{lk, lq, (lfuse ? POA_LAUNCH_FUSE : 0u) | (lmw ? POA_LAUNCH_MW : 0u), lwaves, code_fmt, ltb, ldepth, count}, mf, lk == POA_KERNEL_BAND, ltb != 0, lean};
 }
 
 }  // namespace poa_amd

@@ -29,6 +29,8 @@ struct DenseRunPlan {
     int quads_override, band_pair, tb_group; // 0: no override; -1: by the rule; 0: by the chunk's count
     int band_narrow;                         // the narrow tier of the paired banded pass: -1 by the rule, 0 never, 1 whenever paired
     uint32_t band_cap, spec_depth;
+    int tb_lean;                             // the lean walk kernel (poa_traceback_mf.hpp): -1 by the rule, 0 never, 1 wherever eligible
+    bool tb_lean_mode;                       // the run is one whose walk may be lean at all (POA_MODE_DENSE)
 };
 DenseRunPlan plan_dense_run(uint32_t gap_open, uint32_t gap_extend, uint64_t max_len, uint64_t min_path_nodes, uint32_t mode, bool full_planes,
                             bool plan16_same, const TuneView& T);
@@ -38,8 +40,14 @@ struct DenseChunkPlan {
     int mf;            // flag variant of the px kernel and of the banded pair, -1 where another kernel runs
     bool band;         // the banded pair runs (v[0] == POA_KERNEL_BAND)
     bool separate_tb;  // the traceback is a launch of its own (v[5] != 0)
+    bool lean_tb;      // ... and it is poa_traceback_mf_kernel<v[5]> (tb_lean_eligible), else poa_traceback_kernel
 };
-DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T);
+// plane_elems: 2-byte elements of the largest query's planes in the chunk (compact_plane_elems).  A caller that does not say is
+// taken not to fit 32-bit offsets: it gets the launch record alone and the generic walk, never the lean kernel unchecked
+DenseChunkPlan plan_dense_chunk(const DenseRunPlan& R, uint32_t count, uint32_t max_pitch, const TuneView& T, uint64_t plane_elems = ~0ull);
+// the lean walk kernel's case: a separate launch over u16 compact cells of code_fmt 4, absolute encoding, every element offset
+// within a query's planes below 2^32
+bool tb_lean_eligible(const DenseRunPlan& R, uint32_t tb_lanes, uint32_t code_fmt, uint64_t plane_elems);
 uint32_t band_narrow_class(uint32_t d_n, uint32_t L);
 uint32_t band_narrow_pairs(const DenseRunPlan& R, bool pair_by_rule, uint32_t n_rule, uint32_t n_any);
 }  // namespace poa_amd

@@ -25,6 +25,7 @@
 
 #include "poa_dense_plan.hpp"
 #include "poa_kernels.hpp"
+#include "poa_traceback_mf.hpp"
 #include "poa_forward_packed.hpp"
 #include "poa_forward_px.hpp"
 #include "poa_band_plan.hpp"
@@ -272,6 +273,7 @@ struct poa_batch {
     std::vector<uint32_t> h_band_order;                              // the host's copy of d_band_order
     std::vector<uint32_t> h_band_nnarrow_rule, h_band_nnarrow_any;   // per chunk: its leading pairs whose class takes the tier by the rule / has D_n >= 4
     uint32_t narrow_ran = 0, narrow_how = 0, narrow_chunks = 0;      // the last run (poa_batch_band_narrow_info)
+    uint32_t tb_kernel = 0, tb_lanes = 0, tb_depth = 0, tb_walks = 0; // the dense pass's separate traceback launches of the last run (poa_batch_tb_info)
     // paired banded pass (poa_forward_band2_kernel): per chunk of plan[band_pair_plan] the queries in launch order - the pairs
     // (A, B, A, B, ...), then the singles - built from the lengths alone at the first run that may pair and kept
     int band_pair_plan = -1;
@@ -692,7 +694,11 @@ void launch_traceback(const DenseRunPlan& R, const DenseChunkPlan& c, const TbPa
     const dim3 grid((c.v[7] + per_block - 1) / per_block), block(256);
     TbParams tpg = tp;
     tpg.spec_depth = c.v[6];
-    if (R.compact && lanes == 16) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 16>), grid, block, 0, stream, tpg);
+    if (c.lean_tb && lanes == 16) hipLaunchKernelGGL((poa_traceback_mf_kernel<16>), grid, block, 0, stream, tpg);
+    else if (c.lean_tb && lanes == 32) hipLaunchKernelGGL((poa_traceback_mf_kernel<32>), grid, block, 0, stream, tpg);
+    else if (c.lean_tb && lanes == 8) hipLaunchKernelGGL((poa_traceback_mf_kernel<8>), grid, block, 0, stream, tpg);
+    else if (c.lean_tb) hipLaunchKernelGGL((poa_traceback_mf_kernel<64>), grid, block, 0, stream, tpg);
+    else if (R.compact && lanes == 16) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 16>), grid, block, 0, stream, tpg);
     else if (R.compact && lanes == 32) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 32>), grid, block, 0, stream, tpg);
     else if (R.compact && lanes == 8) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true, 8>), grid, block, 0, stream, tpg);
     else if (R.compact) hipLaunchKernelGGL((poa_traceback_kernel<uint16_t, true>), grid, block, 0, stream, tpg);
@@ -1505,6 +1511,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->pair_paired = 0; b->pair_single = 0;
     b->narrow_ran = 0; b->narrow_how = 0; b->narrow_chunks = 0;
+    b->tb_kernel = POA_TB_KERNEL_NONE; b->tb_lanes = 0; b->tb_depth = 0; b->tb_walks = 0;
     b->active_plan = R.plan;
     const poa_batch::Plan& PL = b->cur();
     if (b->n_queries == 0) return run.end_empty(true);
@@ -1516,7 +1523,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         const auto& ch = PL.chunks[ci];
         uint32_t max_pitch = 0;
         for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) max_pitch = std::max(max_pitch, b->h_pitch[i]);
-        const DenseChunkPlan C = plan_dense_chunk(R, ch.count, max_pitch, T);
+        const DenseChunkPlan C = plan_dense_chunk(R, ch.count, max_pitch, T, compact_plane_elems(fg.n, max_pitch, fg.d_slot.empty() ? fg.n : fg.n_store_d));
         TbParams tp;
         tp.rows = b->d_rows.p; tp.pred_rows = b->d_pred_rows.p; tp.n_rows = fg.n;
         tp.start_row = fg.start_row; tp.end_row = fg.end_row;
@@ -1553,6 +1560,9 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
         if (C.separate_tb) {
             launch_traceback(R, C, tp, stream);
             HIP_TRY(hipGetLastError());
+            if (!C.lean_tb) b->tb_kernel = POA_TB_KERNEL_GENERIC;
+            else if (b->tb_kernel == POA_TB_KERNEL_NONE) b->tb_kernel = POA_TB_KERNEL_LEAN;
+            b->tb_lanes = C.v[5]; b->tb_depth = C.v[6]; b->tb_walks += C.v[7];
         }
         if (mode == POA_MODE_DENSE) b->launches.push_back(C);
         if (const int rc = run.mark()) return rc;
@@ -1716,6 +1726,15 @@ int poa_batch_band_narrow_info(poa_batch_t* b, uint32_t out[4]) {
     uint32_t missed = 0, missed_both = 0;
     for (size_t c = 0; c < n_chunks; ++c) { missed += counts[n_chunks + c]; missed_both += counts[2 * n_chunks + c]; }
     out[1] = b->narrow_ran - std::min(missed, b->narrow_ran); out[2] = missed - std::min(missed_both, missed);
+    return POA_OK;
+}
+
+int poa_batch_tb_info(poa_batch_t* b, uint32_t out[4]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_tb_info: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_tb_info: poa_batch_run has not been called");
+    const bool dense_family = !(b->two_piece || b->sweep || b->ckpt);
+    out[0] = dense_family ? b->tb_kernel : (uint32_t)POA_TB_KERNEL_NONE;
+    out[1] = dense_family ? b->tb_lanes : 0u; out[2] = dense_family ? b->tb_depth : 0u; out[3] = dense_family ? b->tb_walks : 0u;
     return POA_OK;
 }
 
