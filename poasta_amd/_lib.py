@@ -41,6 +41,9 @@ CFG_BEST_PAIR_ORDER = 2
 # every symbol include/poasta_amd_tb.h declares (checked by tests/test_tb_lean.py)
 EXPORTS_TB = ["poa_batch_tb_info"]
 TB_LEAN_SHIFT = 4
+# every symbol include/poasta_amd_multi_dense.h declares (checked by tests/test_multi_dense_plan.py)
+EXPORTS_MULTI_DENSE = ["poa_multi_footprint_dense", "poa_multi_create_dense", "poa_multi_run_dense", "poa_align_multi_dense",
+                       "poa_graph_compact_elems", "poa_multi_last_launch"]
 
 
 class PoaBest(C.Structure):
@@ -134,7 +137,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h", "poasta_amd_multi_dense.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -284,6 +287,20 @@ def lib():
     L.poa_align_multi_2piece.restype = C.c_int
     L.poa_align_multi_2piece.argtypes = [vp, C.c_uint32, vp, C.POINTER(PoaCosts2), C.POINTER(PoaConfig), vp, vp, vp, vp, vp, C.c_uint64, vp,
                                          C.POINTER(PoaStats), C.c_int]
+    if hasattr(L, "poa_multi_create_dense"):   # (POA_LIB_PATH may name the build of an older tree: A/B runs)
+        # the dense batch kind on the same object: the argument lists of the namesakes
+        L.poa_multi_footprint_dense.restype = C.c_int
+        L.poa_multi_footprint_dense.argtypes = L.poa_multi_footprint.argtypes
+        L.poa_multi_create_dense.restype = C.c_int
+        L.poa_multi_create_dense.argtypes = L.poa_multi_create.argtypes
+        L.poa_multi_run_dense.restype = C.c_int
+        L.poa_multi_run_dense.argtypes = L.poa_multi_run.argtypes
+        L.poa_align_multi_dense.restype = C.c_int
+        L.poa_align_multi_dense.argtypes = L.poa_align_multi.argtypes
+        L.poa_graph_compact_elems.restype = C.c_int
+        L.poa_graph_compact_elems.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.poa_multi_last_launch.restype = C.c_int
+        L.poa_multi_last_launch.argtypes = [vp, C.c_uint32, vp]
     # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)
     L.poa_scoreset_footprint.restype = C.c_int
     L.poa_scoreset_footprint.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64),

@@ -511,13 +511,16 @@ class _MultiInput:
         self.pair_capacity = int(self.qoff[-1]) + int(sum(int(c) * dg.graph.n for c, dg in zip(per_graph, self.dgs) if c > 0))
 
 
-def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False):
+def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False):
     """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
     largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan.
-    two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2")."""
+    two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2").
+    dense: the dense batch (poa_multi_footprint_dense; config: None or mode "dense"): compact u16 planes per query."""
+    if dense and two_piece:
+        raise ValueError("multi_footprint: the dense multi-graph batch is one-piece")
     mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
     total, largest = C.c_uint64(0), C.c_uint64(0)
-    fn = _lib.lib().poa_multi_footprint_2piece if two_piece else _lib.lib().poa_multi_footprint
+    fn = _lib.lib().poa_multi_footprint_2piece if two_piece else (_lib.lib().poa_multi_footprint_dense if dense else _lib.lib().poa_multi_footprint)
     _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff), C.byref(config) if config is not None else None,
                   C.byref(total), C.byref(largest)))
     return int(total.value), int(largest.value)
@@ -527,16 +530,21 @@ class MultiGraphBatch:
     """The queries of many graphs resident in HBM (`poa_multi_*`): one checkpointed run covers all of them, one wavefront per
     query.  Queries are grouped by graph — seqs_per_graph[g] are graph g's, or graph_qoff + packed qseq / qoff; results come
     back in query order, rpos = node index in that query's own graph.  two_piece=True: the batch of the two-piece model
-    (`poa_multi_create_2piece`; its footprint differs, so the model is chosen at creation), run with GapAffine2Piece costs."""
+    (`poa_multi_create_2piece`; its footprint differs, so the model is chosen at creation), run with GapAffine2Piece costs.
+    dense=True: the dense batch (`poa_multi_create_dense`): the packed forward pass over compact u16 planes and one walk launch
+    per chunk instead of the two checkpointed passes; queries of at most 1023 symbols, one-piece costs that allow u16 cells."""
 
     def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None,
-                 two_piece=False):
+                 two_piece=False, dense=False):
+        if dense and two_piece:
+            raise ValueError("MultiGraphBatch: the dense multi-graph batch is one-piece")
         mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
         self.input, self.n, self.pair_capacity = mi, mi.n, mi.pair_capacity
         self.graph_qoff, self.qseq, self.qoff = mi.graph_qoff, mi.qseq, mi.qoff
         self.two_piece = bool(two_piece)
+        self.dense = bool(dense)
         h = C.c_void_p()
-        create = _lib.lib().poa_multi_create_2piece if self.two_piece else _lib.lib().poa_multi_create
+        create = _lib.lib().poa_multi_create_2piece if self.two_piece else (_lib.lib().poa_multi_create_dense if self.dense else _lib.lib().poa_multi_create)
         _lib.check(create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
                           C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
@@ -544,12 +552,29 @@ class MultiGraphBatch:
     def run(self, costs, stream=None, config=None):
         """Launch on `stream` without synchronising (config: None or make_config("checkpoint", ...); for a two_piece batch
         make_config("checkpoint2", ...)).  GapAffine2Piece costs run through poa_multi_run_2piece, all others through
-        poa_multi_run: costs of the other model than the batch's are refused by the library (POA_ERR_INVALID_ARG)."""
+        poa_multi_run: costs of the other model than the batch's are refused by the library (POA_ERR_INVALID_ARG).  A dense
+        batch runs one-piece costs through poa_multi_run_dense (config: None or make_config("dense", ...))."""
         c = costs._c()
         if config is None:
-            config = make_config("checkpoint2" if self.two_piece else "checkpoint")   # (carries the POA_<NAME> overrides, if any are set)
-        run = _lib.lib().poa_multi_run_2piece if isinstance(costs, GapAffine2Piece) else _lib.lib().poa_multi_run
+            config = make_config("dense" if self.dense else ("checkpoint2" if self.two_piece else "checkpoint"))   # (carries the POA_<NAME> overrides, if any are set)
+        if isinstance(costs, GapAffine2Piece):
+            run = _lib.lib().poa_multi_run_2piece
+        else:
+            run = _lib.lib().poa_multi_run_dense if self.dense else _lib.lib().poa_multi_run
         _lib.check(run(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
+
+    def launches(self):
+        """What the last run of a dense batch launched, one dict per chunk (poa_multi_last_launch), in the form of
+        ResidentBatch.launches: "kernel" is "packed", "quads" 1 or 2, "tb_lanes" 64, "tb_depth" 32, "queries" the chunk's."""
+        out = []
+        while True:
+            v = (C.c_uint32 * 8)()
+            rc = _lib.lib().poa_multi_last_launch(self.handle, len(out), v)
+            if rc == -1 and (out or (self.n == 0 and self.dense)):   # past the last chunk (a batch without queries launches nothing)
+                return out
+            _lib.check(rc)
+            out.append({"kernel": LAUNCH_KERNELS[v[0]], "quads": int(v[1]), "fuse": bool(v[2] & 1), "mw": bool(v[2] & 2),
+                        "waves": int(v[3]), "code_fmt": int(v[4]), "tb_lanes": int(v[5]), "tb_depth": int(v[6]), "queries": int(v[7])})
 
     def fetch(self, want_pairs=True):
         n = self.n
@@ -826,14 +851,20 @@ class PoastaAligner:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())
 
-    def align_multi(self, graphs, seqs_per_graph, want_pairs=True):
+    def align_multi(self, graphs, seqs_per_graph, want_pairs=True, mode="checkpoint"):
         """Many graphs, a few reads each, in one checkpointed run (poa_align_multi): seqs_per_graph[g] are the queries of
         graphs[g].  Returns a BatchResult over all queries in that order: dense mode's score, alignment and flags of every
         query against its own graph.  Global.  A two-piece config (Affine2PieceDijkstra / Affine2PieceMinGapCost) runs
-        poa_align_multi_2piece: the dense two-piece pass's results."""
+        poa_align_multi_2piece: the dense two-piece pass's results.
+        mode="dense": the same results from the dense batch (poa_align_multi_dense): the packed forward pass over compact
+        planes — more workspace, queries of at most 1023 symbols, one-piece costs only (a two-piece config: ValueError)."""
         if self.aln_type != AlignmentType.Global:
             raise ValueError("align_multi: AlignmentType.Global only")
+        if mode not in ("checkpoint", "dense"):
+            raise ValueError("align_multi: mode is \"checkpoint\" or \"dense\"")
         two_piece = getattr(self.config, "two_piece", False)
+        if mode == "dense" and two_piece:
+            raise ValueError("align_multi: mode=\"dense\" is one-piece; a two-piece config runs the checkpointed batch")
         mi = _MultiInput(graphs, seqs_per_graph)
         n = mi.n
         score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
@@ -841,8 +872,8 @@ class PoastaAligner:
         pairs = np.zeros((max(mi.pair_capacity, 1), 2), np.uint32) if want_pairs else None
         st = _lib.PoaStats()
         c = self.config.costs._c()
-        cfg = make_config("checkpoint2" if two_piece else "checkpoint", self.config.heuristic)
-        fn = _lib.lib().poa_align_multi_2piece if two_piece else _lib.lib().poa_align_multi
+        cfg = make_config("dense" if mode == "dense" else ("checkpoint2" if two_piece else "checkpoint"), self.config.heuristic)
+        fn = _lib.lib().poa_align_multi_2piece if two_piece else (_lib.lib().poa_align_multi_dense if mode == "dense" else _lib.lib().poa_align_multi)
         _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq), _p(mi.qoff), _p(score),
                       _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags), C.byref(st), self.device))
         if want_pairs:
@@ -902,14 +933,16 @@ class PoastaAligner:
         out["graph"] = np.where(won, graph_of, -1).astype(np.int64)
         return out
 
-    def assign_and_align(self, graphs, seqs, pairs=None, max_score=None, want_pairs=True):
+    def assign_and_align(self, graphs, seqs, pairs=None, max_score=None, want_pairs=True, mode="checkpoint"):
         """assign, then the alignments of the assigned queries against their winning graphs in one align_multi run (the
-        two-piece form for a two-piece config).  Returns (assignment, BatchResult), the BatchResult in the order of seqs; a
-        query without a graph has no pairs, score POA_NONE and flags 0."""
+        two-piece form for a two-piece config; mode: align_multi's).  Returns (assignment, BatchResult), the BatchResult in
+        the order of seqs; a query without a graph has no pairs, score POA_NONE and flags 0."""
+        if mode == "dense" and getattr(self.config, "two_piece", False):   # (before the assignment runs for nothing)
+            raise ValueError("assign_and_align: mode=\"dense\" is one-piece; a two-piece config runs the checkpointed batch")
         a = self.assign(graphs, seqs, pairs=pairs, max_score=max_score)
         n = len(seqs)
         order = [np.flatnonzero(a["graph"] == g) for g in range(len(graphs))]
-        res = self.align_multi(graphs, [[seqs[int(i)] for i in idx] for idx in order], want_pairs=want_pairs)
+        res = self.align_multi(graphs, [[seqs[int(i)] for i in idx] for idx in order], want_pairs=want_pairs, mode=mode)
         score, flags = np.full(n, _lib.POA_NONE, np.uint32), np.zeros(n, np.uint32)
         counts = np.zeros(n, np.uint64)
         where = np.concatenate(order).astype(np.int64) if order else np.zeros(0, np.int64)   # where[k]: the query of res' k-th

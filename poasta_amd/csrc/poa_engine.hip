@@ -37,6 +37,7 @@
 #include "poa_checkpoint2.hpp"
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
+#include "poa_multi_dense.hpp"
 #include "poa_scoreset_plan.hpp"
 #include "poa_scoreset.hpp"
 
@@ -2410,6 +2411,10 @@ struct poa_multi {
     DevBuf<uint32_t> d_slot, d_pred_slot, d_graph_of, d_carry_off;
     DevBuf<MultiGraphParams> d_params;
     DevBuf<Multi2GraphParams> d_params2;        // a batch of poa_multi_create_2piece holds these instead (core.ckpt2 is set)
+    // a batch of poa_multi_create_dense (poa_multi_dense.hpp): compact u16 planes in the workspace, d_slot / d_pred_slot hold
+    // FlatGraph::d_slot by row / pred_dslot by edge, one MultiDenseBlock per listed graph; core.ckpt is not set
+    bool dense = false;
+    DevBuf<MultiDenseBlock> d_dense;
 };
 
 namespace {
@@ -2662,6 +2667,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: null argument");
     // (the batch's model first: whatever the mode, this entry point cannot run a two-piece batch)
     if (m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_2piece (it runs through poa_multi_run_2piece only)");
+    if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run");
     if (mrc != POA_OK) return mrc;
     const TuneView T(cfg);
@@ -2707,6 +2713,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
 // piece's bound for every graph that has queries, the chunks of the batch under either width.
 int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");
+    if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
     if (!m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create (a two-piece run needs poa_multi_create_2piece: its footprint differs)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run_2piece", true);
     if (mrc != POA_OK) return mrc;
@@ -2809,6 +2816,296 @@ int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
     int rc = poa_multi_create_2piece(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
     if (rc != POA_OK) return rc;
     rc = poa_multi_run_2piece(m, costs, cfg, nullptr);
+    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
+    poa_multi_destroy(m);
+    return rc;
+}
+
+}  // extern "C"
+
+
+// ---- dense multi-graph batch (poa_multi_dense.hpp, build_multi_dense_plan) --------------------------------------------------
+// The same object as the checkpointed batches above, of a third kind (poa_multi::dense): the workspace holds every query's
+// compact u16 planes, a run is the packed forward launch and the walk launch per chunk, then the scan and compaction of pairs.
+// The core is a dense poa_batch (ckpt not set), so poa_multi_fetch / _stats / _device_results / _workspace_bytes / _destroy
+// serve it unchanged and poa_stats_t.plane_bytes is the planes' own size.
+namespace {
+int multi_dense_mode_check(const poa_config_t* cfg, const char* who) {
+    if (cfg && cfg->mode != POA_MODE_DENSE)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch runs in POA_MODE_DENSE only (the checkpointed batches: poa_multi_create, poa_multi_create_2piece)");
+    if (cfg && cfg->span != POA_SPAN_GLOBAL)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch is Global: an ends-free result is defined by the reference's search");
+    return POA_OK;
+}
+
+int multi_dense_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                        uint64_t workspace_bytes, MultiPlan& plan, const char* who) {
+    if (!graph_qoff || !qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    std::vector<MultiGraphIn> in(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
+        in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, &graphs[g]->ckpt};
+    }
+    std::string err;
+    const int rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
+    if (rc != 0) return fail(rc, std::string(who) + ": " + err);
+    return POA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int poa_graph_compact_elems(const poa_graph_t* g, uint32_t len, uint64_t* elems) {
+    if (!g || !elems) return fail(POA_ERR_INVALID_ARG, "poa_graph_compact_elems: null argument");
+    if (len > 0x7FFFFFF0u) return fail(POA_ERR_UNSUPPORTED, "poa_graph_compact_elems: query longer than 2^31");
+    *elems = multi_dense_query_elems(g->g, len);
+    return POA_OK;
+}
+
+int poa_multi_footprint_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                              const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    const char* who = "poa_multi_footprint_dense";
+    if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    int rc = multi_dense_mode_check(cfg, who);
+    if (rc != POA_OK) return rc;
+    MultiPlan plan;
+    try {
+        rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, 0, plan, who);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    if (bytes) *bytes = plan.bytes_total;
+    if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
+    return POA_OK;
+}
+
+int poa_multi_create_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                           const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    const char* who_c = "poa_multi_create_dense";
+    const std::string who(who_c);
+    if (!out) return fail(POA_ERR_INVALID_ARG, who + ": out is null");
+    *out = nullptr;
+    int rc = multi_dense_mode_check(cfg, who_c);
+    if (rc != POA_OK) return rc;
+    std::unique_ptr<poa_multi> m(new (std::nothrow) poa_multi);
+    if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
+    m->dense = true;
+    MultiPlan& pl = m->plan;
+    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
+    try {
+        rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, 0, pl, who_c);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
+    if (rc != POA_OK) return rc;
+    const uint32_t n = pl.n_queries;
+    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
+    const int ndev = poa_device_count();
+    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, who + ": device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t scratch_total = pl.scratch_off[n];
+    const uint64_t fixed = scratch_total * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + (pl.n_rows_total + pl.n_edges_total) * 32;
+    uint64_t ws = workspace_bytes;
+    if (ws == 0) {
+        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
+        ws = std::min<uint64_t>(pl.bytes_total, avail);
+    }
+    if (ws < pl.largest_query_bytes) {
+        if (pl.largest_query_bytes + fixed > free_b)
+            return fail(POA_ERR_OUT_OF_MEMORY, "the compact planes of the largest query do not fit in device memory");
+        ws = pl.largest_query_bytes;
+    }
+    if (ws < pl.bytes_total) {
+        try {
+            rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, ws, pl, who_c);
+        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
+        if (rc != POA_OK) return rc;
+    }
+
+    // the core batch: queries, results, pair buffers, events
+    poa_batch* b = &m->core;
+    b->graph = nullptr; b->device = device; b->n_queries = n;
+    b->last_mode = POA_MODE_DENSE;
+    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.plane_bytes;
+    b->plan_ws = pl.workspace_bytes;
+    try {
+        b->h_qoff.assign(qoff, qoff + n + 1);
+        b->h_pitch = pl.pitch;
+        b->h_scratch_off = pl.scratch_off;
+        b->plan[0].off = pl.region_off;
+        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
+        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
+    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    b->active_plan = 0;
+    for (uint32_t g = 0; g < n_graphs; ++g) b->max_len = std::max(b->max_len, pl.graphs[g].max_len);
+
+    // concatenated tables, one copy per distinct handle: rows and d_slot by row, pred_rows and pred_dslot by edge
+    std::vector<RowMeta> h_rows(pl.n_rows_total);
+    std::vector<uint32_t> h_dslot(pl.n_rows_total, 0u), h_pred_rows(pl.n_edges_total), h_pred_dslot(pl.n_edges_total, 0u);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        if (gp.n_queries) {
+            m->ub_open.push_back((gp.max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0));
+            m->ub_extend.push_back(gp.max_len + fg.min_path_nodes);
+        }
+        if (gp.table_of != g) continue;
+        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
+        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
+        if (!fg.d_slot.empty()) {   // (else the graph keeps its D rows by row: its blocks carry null table pointers)
+            std::copy(fg.d_slot.begin(), fg.d_slot.end(), h_dslot.begin() + gp.row_base);
+            std::copy(fg.pred_dslot.begin(), fg.pred_dslot.end(), h_pred_dslot.begin() + gp.edge_base);
+        }
+    }
+
+    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
+    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
+    HIP_TRY(m->d_slot.alloc(std::max<size_t>(h_dslot.size(), 1)));
+    HIP_TRY(m->d_pred_slot.alloc(std::max<size_t>(h_pred_dslot.size(), 1)));
+    HIP_TRY(m->d_graph_of.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(m->d_dense.alloc(std::max<uint32_t>(n_graphs, 1)));
+    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n], 1)));
+    HIP_TRY(b->d_qoff.alloc((size_t)n + 1));
+    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_scratch_off.alloc((size_t)n + 1));
+    HIP_TRY(b->d_pair_off.alloc((size_t)n + 1));
+    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n, 1)));
+    HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
+    HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
+    HIP_TRY(b->d_carry.alloc(1));   // FwdParams::strip_carry: a valid address that one-strip queries never touch
+    HIP_TRY(b->d_pipeline_error.alloc(1));
+    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
+    if (n) {
+        std::string werr;
+        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "dense multi-graph workspace: " + werr);
+    }
+
+    // one block per listed graph: what poa_batch_run_ex puts into FwdParams / TbParams for that graph alone, absolute encoding
+    std::vector<MultiDenseBlock> h_blocks(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        MultiDenseBlock& mb = h_blocks[g];
+        std::memset(&mb, 0, sizeof(mb));
+        const bool by_row = fg.d_slot.empty();
+        FwdParams& fp = mb.F;
+        fp.rows = b->d_rows.p + gp.row_base; fp.pred_rows = b->d_pred_rows.p + gp.edge_base; fp.n_rows = fg.n;
+        fp.qseq = b->d_qseq.p; fp.qoff = b->d_qoff.p; fp.pitch = b->d_pitch.p; fp.plane_off = b->plan[0].d_off.p;
+        fp.planes = b->d_planes.p; fp.strip_carry = b->d_carry.p;
+        fp.pred_k = nullptr;
+        fp.d_slot = by_row ? nullptr : m->d_slot.p + gp.row_base; fp.pred_dslot = by_row ? nullptr : m->d_pred_slot.p + gp.edge_base;
+        fp.pipeline_error = b->d_pipeline_error.p;
+        TbParams& tp = mb.T;
+        tp.rows = fp.rows; tp.pred_rows = fp.pred_rows; tp.n_rows = fg.n;
+        tp.start_row = fg.start_row; tp.end_row = fg.end_row;
+        tp.qseq = fp.qseq; tp.qoff = fp.qoff; tp.pitch = fp.pitch; tp.plane_off = fp.plane_off;
+        tp.planes = b->d_planes.p; tp.scratch_off = b->d_scratch_off.p; tp.scratch = b->d_scratch.p;
+        tp.score = b->d_score.p; tp.flags = b->d_flags.p; tp.n_pairs = b->d_npairs.p;
+        tp.exact_pass = 0; tp.ex_status = nullptr; tp.ex_end = nullptr; tp.code_fmt = 0;
+        tp.row_depth = nullptr;
+        tp.d_slot = fp.d_slot; tp.pred_dslot = fp.pred_dslot;
+        mb.empty = fg.n_real == 0 ? 1u : 0u;
+    }
+
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
+    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
+    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
+    HIP_TRY(up(m->d_slot.p, h_dslot.data(), h_dslot.size() * 4));
+    HIP_TRY(up(m->d_pred_slot.p, h_pred_dslot.data(), h_pred_dslot.size() * 4));
+    HIP_TRY(up(m->d_dense.p, h_blocks.data(), h_blocks.size() * sizeof(MultiDenseBlock)));
+    HIP_TRY(up(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n]));
+    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n + 1) * 8));
+    HIP_TRY(up(b->d_scratch_off.p, pl.scratch_off.data(), ((size_t)n + 1) * 8));
+    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
+    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+
+    *out = m.release();
+    return POA_OK;
+}
+
+// per chunk the packed forward launch over the queries of all graphs, then the walk launch; scan and compaction of the pairs
+// over all queries.  Nothing is written into the batch before every refusal has passed.
+int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
+    if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: null argument");
+    if (!m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was not created by poa_multi_create_dense (a checkpointed batch runs through poa_multi_run / poa_multi_run_2piece)");
+    const int mrc = multi_dense_mode_check(cfg, "poa_multi_run_dense");
+    if (mrc != POA_OK) return mrc;
+    const TuneView T(cfg);
+    // the batch is sized for u16 compact cells: every graph's own bound (its longest query and shortest path) must allow them
+    bool narrow = !planes32(T);
+    for (size_t g = 0; g < m->ub_open.size(); ++g)
+        narrow = narrow && u16_cells_suffice(costs->gap_open, costs->gap_extend, m->ub_open[g], m->ub_extend[g]);
+    if (!narrow)
+        return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_dense: the run needs u32 cells (the costs' score bound exceeds 65534 for some graph, or "
+                                         "tune[POA_TUNE_PLANES] = 32) and a dense multi-graph batch holds u16 compact cells only; the checkpointed "
+                                         "batch (poa_multi_create, poa_multi_run) runs either width");
+    poa_batch* b = &m->core;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(b->device));
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_multi_run_dense: call poa_multi_stats/fetch at least every 256 runs")) return rc;
+    const MultiPlan& pl = m->plan;
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
+    b->last_mode = POA_MODE_DENSE;
+    b->two_piece = false;
+    set_layout(b, true, true, false);
+    b->active_plan = 0;
+    b->launches.clear();
+    if (b->n_queries == 0) return run.end_empty(true);
+    for (const auto& ch : pl.chunks) {
+        MultiDenseLaunch ml;
+        ml.graphs = m->d_dense.p; ml.graph_of = m->d_graph_of.p;
+        ml.first_query = ch.first; ml.n_queries = ch.count;
+        ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
+        ml.spec_depth = 32;   // what plan_dense_chunk pairs with 64 lanes per walk on the compact layout
+        ml.code_fmt = 0;
+        const uint32_t quads = ch.max_pitch <= 512 ? 1u : 2u;   // 512 columns per quad; the plan holds every pitch to 1024
+        const dim3 grid((ch.count + 3) / 4), block(256);
+        if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_multi_kernel<1>), grid, block, 0, stream, ml);
+        else hipLaunchKernelGGL((poa_forward_packed_multi_kernel<2>), grid, block, 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        hipLaunchKernelGGL(poa_traceback_multi_kernel, grid, block, 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark(2)) return rc;
+        // the record of poa_batch_last_launch: kernel, quads, launch bits, waves per workgroup, code_fmt, lanes per walk, depth, queries
+        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, 0u, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
+    }
+    return run.end_pairs();
+}
+
+int poa_multi_last_launch(poa_multi_t* m, uint32_t chunk, uint32_t out[8]) {
+    if (!m || !out) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: null argument");
+    if (!m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the batch was not created by poa_multi_create_dense");
+    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: poa_multi_run_dense has not been called");
+    if (chunk >= m->core.launches.size()) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the last run had no such chunk");
+    for (int k = 0; k < 8; ++k) out[k] = m->core.launches[chunk].v[k];
+    return POA_OK;
+}
+
+int poa_align_multi_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs_t* costs,
+                          const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs,
+                          uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi_dense: null argument");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    poa_multi_t* m = nullptr;
+    int rc = poa_multi_create_dense(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
+    if (rc != POA_OK) return rc;
+    rc = poa_multi_run_dense(m, costs, cfg, nullptr);
     if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
     poa_multi_destroy(m);
     return rc;

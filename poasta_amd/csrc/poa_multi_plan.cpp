@@ -104,4 +104,89 @@ int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64
     return 0;
 }
 
+int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                           uint64_t workspace_bytes, MultiPlan& out, std::string& err) {
+    out = MultiPlan();
+    if (!graph_qoff || !qoff || (n_graphs && !graphs)) { err = "dense multi-graph batch: null argument"; return ERR_INVALID_ARG; }
+    if (graph_qoff[0] != 0) { err = "dense multi-graph batch: graph_qoff[0] is not 0"; return ERR_INVALID_ARG; }
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (!graphs[g].g) { err = "dense multi-graph batch: null graph"; return ERR_INVALID_ARG; }
+        if (graph_qoff[g + 1] < graph_qoff[g]) { err = "dense multi-graph batch: graph_qoff is not non-decreasing"; return ERR_INVALID_ARG; }
+    }
+    if (graph_qoff[n_graphs] > 0xFFFFFFF0ull) { err = "dense multi-graph batch: graph_qoff[n_graphs] is not a query count a batch can hold"; return ERR_INVALID_ARG; }
+    const uint32_t n = (uint32_t)graph_qoff[n_graphs];
+    for (uint32_t i = 0; i < n; ++i) {
+        if (qoff[i + 1] < qoff[i]) { err = "dense multi-graph batch: qoff not monotone"; return ERR_INVALID_ARG; }
+        if (qoff[i + 1] - qoff[i] > MULTI_DENSE_MAX_LEN) {
+            err = "dense multi-graph batch: a query of more than 1023 symbols is wider than one strip of the packed forward pass; "
+                  "the checkpointed batch (poa_multi_create) takes queries of any length";
+            return ERR_UNSUPPORTED;
+        }
+    }
+    out.n_queries = n;
+    out.graphs.resize(n_graphs);
+    out.graph_of.resize(n); out.pitch.resize(n); out.carry_off.assign(n, 0u); out.region_off.resize(n);
+    out.scratch_off.resize((size_t)n + 1);
+
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        MultiGraphPlan& gp = out.graphs[g];
+        const FlatGraph& fg = *graphs[g].g;
+        gp.table_of = g;
+        for (uint32_t h = 0; h < g; ++h)
+            if (graphs[h].g == graphs[g].g) { gp.table_of = h; break; }
+        gp.n_rows = fg.n; gp.n_edges = (uint32_t)fg.pred_rows.size();
+        gp.n_queries = (uint32_t)(graph_qoff[g + 1] - graph_qoff[g]);
+        if (gp.table_of != g) {
+            gp.row_base = out.graphs[gp.table_of].row_base; gp.edge_base = out.graphs[gp.table_of].edge_base;
+        } else {
+            gp.row_base = out.n_rows_total; gp.edge_base = out.n_edges_total;
+            out.n_rows_total += gp.n_rows; out.n_edges_total += gp.n_edges;
+        }
+        for (uint64_t i = graph_qoff[g]; i < graph_qoff[g + 1]; ++i) {
+            const uint64_t L = qoff[i + 1] - qoff[i];
+            out.graph_of[i] = g;
+            out.pitch[i] = (uint32_t)(((L + 1 + 63) / 64) * 64);
+            gp.max_len = std::max(gp.max_len, L);
+        }
+    }
+
+    // per query: its compact planes and the padding, in two-byte elements
+    auto elems_of = [&](uint32_t i) { return multi_dense_query_elems(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_DENSE_PAD_ELEMS; };
+    uint64_t scratch = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const MultiGraphPlan& gp = out.graphs[out.graph_of[i]];
+        const uint64_t L = qoff[i + 1] - qoff[i];
+        const uint64_t bytes = elems_of(i) * 2;
+        out.bytes_total += bytes;
+        out.plane_bytes += bytes - MULTI_DENSE_PAD_ELEMS * 2;
+        out.largest_query_bytes = std::max(out.largest_query_bytes, bytes);
+        out.scratch_off[i] = scratch;
+        scratch += L + gp.n_rows;
+        out.total_bases += L;
+        out.total_cells += (uint64_t)gp.n_rows * (L + 1);
+    }
+    out.scratch_off[n] = scratch;
+
+    // chunks: the greedy rule of build_multi_plan; the region offsets restart with every chunk
+    const uint64_t budget = workspace_bytes == 0 ? out.bytes_total : std::max(workspace_bytes, out.largest_query_bytes);
+    MultiPlan::Chunk cur{0, 0, 0, 0, 0};
+    auto close = [&]() {
+        out.chunks.push_back(cur);
+        out.workspace_bytes = std::max(out.workspace_bytes, cur.cells * 2);
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t elems = elems_of(i);
+        if (cur.count && (cur.cells + elems) * 2 > budget) {
+            close();
+            cur = MultiPlan::Chunk{i, 0, 0, 0, 0};
+        }
+        out.region_off[i] = cur.cells;
+        cur.cells += elems;
+        cur.max_pitch = std::max(cur.max_pitch, out.pitch[i]);
+        cur.count++;
+    }
+    if (cur.count) close();
+    return 0;
+}
+
 }  // namespace poa_amd

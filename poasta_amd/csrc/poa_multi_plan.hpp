@@ -30,11 +30,21 @@
 // per graph the two-piece CheckpointPlan (three kept planes, five window planes: what poa_graph_checkpoint_plan2 gives for
 // that graph alone; MultiGraphIn::own is then the handle's two-piece plan), and 6 x n_rows carry words for a query wider than
 // one strip (ckpt2_rows: two parities of three words per row).  Its strips are 1024 columns under both cell types too.
+//
+// The dense variant (poa_multi_*_dense, poa_multi_dense.hpp; build_multi_dense_plan below) lays out the compact u16 planes of
+// the packed forward pass instead: per query compact_plane_elems(n_rows(graph), pitch, kept D rows of the graph) two-byte
+// elements (poa_graph.hpp: the M plane, a quarter plane of flag codes, the kept D rows; a graph without a d_slot table keeps
+// all n_rows of them) + 256 bytes of padding.  region_off and Chunk::cells are then in TWO-byte elements, relative to the
+// query's chunk; chunks are cut by the same greedy rule; Chunk::max_pitch chooses the kernel's quads (1 up to 512 columns,
+// 2 above).  Every query is one strip: a query of more than 1023 symbols (pitch above 1024) is refused, and there are no
+// carries.  The tables a dense graph needs are rows and d_slot by row (row_base), pred_rows and pred_dslot by edge
+// (edge_base); the checkpoint fields of MultiGraphPlan stay empty.
 #pragma once
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "poa_graph.hpp"
 #include "poa_sweep_rows.hpp"
 
 namespace poa_amd {
@@ -71,6 +81,7 @@ struct MultiPlan {
     uint64_t workspace_bytes = 0;       // the largest chunk: what the batch holds
     uint64_t max_carry_words = 0;       // the largest chunk's carries
     uint64_t total_cells = 0, total_bases = 0;
+    uint64_t plane_bytes = 0;           // dense: sum of 2 x compact elems, the padding left out (poa_stats_t.plane_bytes)
 };
 
 // 4-byte cells a query of `len` symbols holds on a graph with that plan, padding included
@@ -82,5 +93,19 @@ inline uint64_t multi_query_cells(const CheckpointPlan& cp, uint64_t len) {
 // Returns 0, or -1 (invalid argument) / -7 (unsupported) — the values of POA_ERR_INVALID_ARG / POA_ERR_UNSUPPORTED — with `err` set.
 int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                      uint32_t segment_rows, uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool two_piece = false);
+
+constexpr uint64_t MULTI_DENSE_PAD_ELEMS = 128;     // 256 bytes behind every query's region, in two-byte elements
+constexpr uint64_t MULTI_DENSE_MAX_LEN = 1023;      // one strip of the packed kernel's widest variant: pitch <= 1024
+
+// D rows a graph keeps in the compact layout: n_store_d with a d_slot table, every row without one
+inline uint32_t multi_dense_d_rows(const FlatGraph& g) { return g.d_slot.empty() ? g.n : g.n_store_d; }
+// two-byte elements a query of `len` symbols holds on that graph, padding NOT included
+inline uint64_t multi_dense_query_elems(const FlatGraph& g, uint64_t len) {
+    return compact_plane_elems(g.n, (uint32_t)(((len + 1 + 63) / 64) * 64), multi_dense_d_rows(g));
+}
+
+// The dense plan: reads MultiGraphIn::g alone (sweep and own may be null).  Same return values as build_multi_plan.
+int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                           uint64_t workspace_bytes, MultiPlan& out, std::string& err);
 
 }  // namespace poa_amd

@@ -14,6 +14,10 @@ profiles/pr_multi_graph/timing.json.
 --two-piece: the same shape and the same four paths under the two-piece model, costs 4 / 6,24 / 2,1: (a) poa_multi_run_2piece +
 poa_multi_fetch on a batch of poa_multi_create_2piece, (a1) poa_align_multi_2piece, (b) the loop of poa_align_batch_2piece_ex in
 POA_MODE_CHECKPOINT2, (c) the loop of the dense poa_align_batch_2piece.  Writes profiles/pr_multi_graph_2piece/timing.json.
+
+--dense: the one-piece paths above and, in the same process on the same workload, the dense multi-graph batch: (d) poa_multi_run_dense
++ poa_multi_fetch on a resident batch of poa_multi_create_dense, (d1) the one-shot poa_align_multi_dense.  Writes
+profiles/pr_multi_dense/timing.json, with both footprints.
 """
 import argparse
 import ctypes as C
@@ -35,11 +39,14 @@ def main():
     ap.add_argument("--steps", type=int, default=11)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--two-piece", action="store_true", help="the two-piece model, costs 4 / 6,24 / 2,1 (poa_multi_*_2piece)")
+    ap.add_argument("--dense", action="store_true", help="add the dense multi-graph batch (poa_multi_*_dense) to the one-piece paths")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     two = args.two_piece
+    if two and args.dense:
+        ap.error("--dense is one-piece")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "pr_multi_graph_2piece" if two else "pr_multi_graph", "timing.json")
+        args.out = os.path.join(ROOT, "profiles", "pr_multi_dense" if args.dense else ("pr_multi_graph_2piece" if two else "pr_multi_graph"), "timing.json")
     import numpy as np
     from poasta_amd import _lib, aligner, workloads as W
 
@@ -69,6 +76,19 @@ def main():
 
     def step_one_shot():
         r = al.align_multi(graphs, seqs)
+        return r, r.stats["ms_forward"], r.stats["ms_traceback"]
+
+    md = aligner.MultiGraphBatch(graphs, seqs, dense=True) if args.dense else None
+    last_dense_stats = {}
+
+    def step_dense():
+        md.run(costs)
+        r = md.fetch()
+        last_dense_stats.update(r.stats)
+        return r, r.stats["ms_forward"], r.stats["ms_traceback"]
+
+    def step_dense_one_shot():
+        r = al.align_multi(graphs, seqs, mode="dense")
         return r, r.stats["ms_forward"], r.stats["ms_traceback"]
 
     def loop(mode):
@@ -104,6 +124,8 @@ def main():
         return step
 
     paths = {"multi_run_fetch": step_multi, "multi_one_shot": step_one_shot, "loop_checkpoint": loop("checkpoint"), "loop_dense": loop("dense")}
+    if args.dense:
+        paths = dict([("dense_run_fetch", step_dense), ("dense_one_shot", step_dense_one_shot)] + list(paths.items()))
     rows = {k: [] for k in paths}
     sums = {}
     for rep in range(args.warmup + args.steps):
@@ -131,11 +153,17 @@ def main():
         out[name] = {"ms_step": med([r[0] for r in rows[name]]), "ms_forward_kernels": med([r[1] for r in rows[name]]),
                      "ms_traceback_kernels": med([r[2] for r in rows[name]])}
         out[name].update(sums[name])
-    for name in ("multi_run_fetch", "multi_one_shot"):
-        for base in ("loop_checkpoint", "loop_dense"):
+    for name in ("multi_run_fetch", "multi_one_shot") + (("dense_run_fetch", "dense_one_shot") if args.dense else ()):
+        for base in ("loop_checkpoint", "loop_dense") + (("multi_run_fetch", "multi_one_shot") if name.startswith("dense") else ()):
             out["ms_step_ratio_%s_over_%s" % (name, base)] = round(out[name]["ms_step"]["median"] / out[base]["ms_step"]["median"], 4)
     # the resident run's own record (poa_stats_t of the last step): cell bytes stored, chunks, the passes
     out["multi_run_stats"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in last_multi_stats.items()}
+    if args.dense:
+        out["dense_workspace_bytes"] = md.workspace_bytes()
+        out["dense_footprint_bytes"] = aligner.multi_footprint(graphs, seqs, dense=True)[0]
+        out["dense_launches"] = md.launches()
+        out["dense_run_stats"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in last_dense_stats.items()}
+        md.close()
     mb.close()
     print(json.dumps(out))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
