@@ -16,6 +16,23 @@ uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n
 bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend) {
     return score_bound(open, extend, n_open, n_extend) <= 65534;
 }
+// The workspace a batch constructor settles on.  requested 0: what the batch needs as one chunk, or 85 % of what the device has
+// free beyond the batch's other buffers (`fixed`) if that is less.  own_footprint: the batch holds its own footprint and never
+// more, so a larger request is a cap only.  Whatever came out is raised to the largest item, which must fit beside `fixed`.
+uint64_t choose_workspace(uint64_t requested, uint64_t free_bytes, uint64_t fixed, uint64_t bytes_total, uint64_t largest, bool own_footprint) {
+    uint64_t ws = requested;
+    if (ws == 0) {
+        const uint64_t avail = free_bytes > fixed ? (uint64_t)((free_bytes - fixed) * 0.85) : 0;
+        ws = std::min<uint64_t>(bytes_total, avail);
+    }
+    if (own_footprint) ws = std::min<uint64_t>(ws, bytes_total);
+    if (ws < largest) {
+        if (largest + fixed > free_bytes) return WORKSPACE_NO_FIT;
+        ws = largest;
+    }
+    return ws;
+}
+
 // POA_PLANES=32 forces u32 cells (debug / A-B)
 bool planes32(const TuneView& T) { const int* pv = T.ptr(POA_TUNE_PLANES); return pv && *pv == 32; }
 

@@ -2,7 +2,9 @@
 // chunk (forward kernel, column groups, waves, cell encoding, traceback lanes and depth).  Host code, no device dependency: the
 // launcher in poa_engine.hip only carries the records out, and tests/dense_plan_host checks the rule on the CPU.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/poasta_amd.h"
 
@@ -18,6 +20,21 @@ constexpr uint32_t DENSE_MW_MAX_WAVES = 16;   // waves per workgroup of a multi-
 uint64_t score_bound(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend);
 bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t n_open, uint64_t n_extend);
 bool planes32(const TuneView& T);
+
+// What the batch constructors share (the create frame in poa_engine.hip; tests/create_host checks both on the CPU).
+// choose_workspace: bytes of plane workspace, or WORKSPACE_NO_FIT when the largest item does not fit in device memory.
+constexpr uint64_t WORKSPACE_NO_FIT = ~0ull;
+uint64_t choose_workspace(uint64_t requested, uint64_t free_bytes, uint64_t fixed, uint64_t bytes_total, uint64_t largest, bool own_footprint);
+// The concatenated table of a batch over many graphs: the table src_of(g) of every graph that owns its tables (a handle's first
+// listing, table_of == g) copied to that graph's base in `dst`, which the plan sized; a repeated handle is copied once.
+template <typename T, typename GraphPlan, typename SrcOf>
+void concat_tables(std::vector<T>& dst, const std::vector<GraphPlan>& graphs, uint64_t GraphPlan::*base, SrcOf&& src_of) {
+    for (uint32_t g = 0; g < graphs.size(); ++g) {
+        if (graphs[g].table_of != g) continue;
+        const std::vector<T>& src = src_of(g);
+        std::copy(src.begin(), src.end(), dst.begin() + (std::ptrdiff_t)(graphs[g].*base));
+    }
+}
 uint32_t mw_waves(uint32_t strips);
 bool pxmw_ok(const TuneView& T, uint32_t count, uint32_t max_pitch);
 

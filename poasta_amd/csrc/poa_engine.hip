@@ -421,9 +421,146 @@ struct RunFrame {
     }
 };
 
+// ---- the frame of a create: every batch constructor goes through here -------------------------------------------------------
+// A constructor is its mode and argument checks (no device needed), its plan callable and `fixed`, the calls below in the order
+// they stand here, and between them what only its kind has: its tables, its carries, its parameter blocks.  Everything behind
+// the null check of `out` runs inside guarded(), and the handle is released into *out by the constructor's last statement.
+struct CreateFrame {
+    std::string who;   // the entry point, as its messages name it
+    int device = 0;
+    struct Events {    // of the timed upload; destroyed on every way out
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() { for (auto ev : e) if (ev) (void)hipEventDestroy(ev); }
+    } timed;
+
+    // nothing but an error code leaves a constructor: a host allocation that fails anywhere in `body` is the refusal `text`
+    template <typename Body>
+    static int guarded(const std::string& text, Body&& body) {
+        try { return body(); } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, text); }
+    }
+    // the C entry of a constructor: the null check of `out`, then `body`, which is all the rest, under that guard
+    template <typename Handle, typename Body>
+    static int enter(const std::string& who, Handle** out, const std::string& text, Body&& body) {
+        if (!out) return fail(POA_ERR_INVALID_ARG, who + ": out is null");
+        *out = nullptr;
+        return guarded(text, body);
+    }
+    // the device check; nothing touches the device before it
+    int open(int dev) {
+        device = dev;
+        const int ndev = poa_device_count();
+        if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
+        if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, who + ": device ordinal out of range");
+        HIP_TRY(hipSetDevice(device));
+        return POA_OK;
+    }
+    // the workspace rule (choose_workspace, poa_dense_plan.cpp) on what the device has free now; `refusal` is the kind's own text
+    int workspace(uint64_t requested, uint64_t fixed, uint64_t bytes_total, uint64_t largest, bool own_footprint, const char* refusal, uint64_t& ws) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        ws = choose_workspace(requested, free_b, fixed, bytes_total, largest, own_footprint);
+        if (ws == WORKSPACE_NO_FIT) return fail(POA_ERR_OUT_OF_MEMORY, refusal);
+        return POA_OK;
+    }
+    // The second pass of the two-pass plan.  The first, plan_of(0, pl), ran in front of the device check: it holds the argument
+    // checks and gave the footprint the workspace is chosen from; the plan is cut again only when that workspace is a cap.
+    template <typename Plan, typename PlanOf>
+    int plan_capped(Plan& pl, uint64_t requested, uint64_t fixed, uint64_t largest, const char* refusal, PlanOf&& plan_of) {
+        uint64_t ws = 0;
+        if (const int rc = workspace(requested, fixed, pl.bytes_total, largest, false, refusal, ws)) return rc;
+        return ws < pl.bytes_total ? plan_of(ws, pl) : POA_OK;
+    }
+    // the core batch of a kind that is built around one: `n` items in the plan's chunks, no graph of its own
+    template <typename Plan>
+    void fill_core(poa_batch* b, const Plan& pl, uint32_t n, uint64_t plane_bytes) const {
+        b->graph = nullptr; b->device = device; b->n_queries = n;
+        b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = plane_bytes;
+        b->plan_ws = pl.workspace_bytes;
+        b->active_plan = 0;
+        for (const auto& c : pl.chunks) {
+            b->plan[0].chunks.push_back({c.first, c.count});
+            b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
+        }
+    }
+    // ... and of a multi-graph batch, whose items are queries: the host's copies of their offsets and pitches as well
+    void fill_core(poa_batch* b, const MultiPlan& pl, uint64_t plane_bytes, const uint64_t* qoff) const {
+        fill_core(b, pl, pl.n_queries, plane_bytes);
+        for (const auto& gp : pl.graphs) b->max_len = std::max(b->max_len, gp.max_len);
+        b->h_qoff.assign(qoff, qoff + pl.n_queries + 1);
+        b->h_pitch = pl.pitch;
+        b->h_scratch_off = pl.scratch_off;
+        b->plan[0].off = pl.region_off;
+    }
+    // `n` elements, and one where there are none: a kernel argument is a valid address even in a batch without queries
+    template <typename... Bufs>
+    static hipError_t alloc_each(uint64_t n, Bufs&... bufs) {
+        hipError_t e = hipSuccess;
+        ((e = e != hipSuccess ? e : bufs.alloc(std::max<uint64_t>(n, 1))), ...);
+        return e;
+    }
+    // what every kind holds: the queries, the items' pitches and regions, their results and, where runs return pairs, the pair
+    // buffers (scratch_total pairs of capacity).  n_queries differs from the items `n` in a score set alone.
+    int alloc_results(poa_batch* b, uint64_t n_bases, uint64_t n_queries, uint64_t n, bool has_pairs, uint64_t scratch_total) const {
+        HIP_TRY(alloc_each(n_bases, b->d_qseq));
+        HIP_TRY(alloc_each(n_queries + 1, b->d_qoff));
+        HIP_TRY(alloc_each(n, b->d_pitch, b->plan[0].d_off, b->d_score, b->d_flags));
+        if (has_pairs) {
+            HIP_TRY(alloc_each(n + 1, b->d_scratch_off, b->d_pair_off));
+            HIP_TRY(alloc_each(n, b->d_npairs));
+            HIP_TRY(alloc_each(scratch_total, b->d_scratch, b->d_pairs));
+        }
+        HIP_TRY(alloc_each(1, b->d_pipeline_error));
+        HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
+        return POA_OK;
+    }
+    // the plane workspace, none for a batch without items; `what` opens the kind's own refusal
+    int acquire_planes(poa_batch* b, uint64_t bytes, bool exact, const char* what) const {
+        if (!b->n_queries) return POA_OK;
+        std::string werr;
+        if (!b->d_planes.acquire(device, bytes, werr, exact)) return fail(POA_ERR_OUT_OF_MEMORY, std::string(what) + ": " + werr);
+        return POA_OK;
+    }
+    // The timed upload: poa_stats_t.ms_h2d is the interval between begin_upload and end_upload, the copies and no allocation.
+    static hipError_t upload(void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; }
+    template <typename T>
+    static hipError_t upload(DevBuf<T>& dst, const std::vector<T>& src) { return upload(dst.p, src.data(), src.size() * sizeof(T)); }
+    int begin_upload() {
+        for (auto& ev : timed.e) HIP_TRY(hipEventCreate(&ev));
+        HIP_TRY(hipEventRecord(timed.e[0], nullptr));
+        return POA_OK;
+    }
+    // the shared part of it: sequences and offsets of n_queries queries, pitch and region of `n` items, scratch_off where there are pairs
+    int upload_queries(poa_batch* b, const uint8_t* qseq, const uint64_t* qoff, size_t n_queries, const uint64_t* scratch_off,
+                       const uint32_t* pitch, const uint64_t* region_off, size_t n) const {
+        HIP_TRY(upload(b->d_qseq.p, qseq, qoff[n_queries]));
+        HIP_TRY(upload(b->d_qoff.p, qoff, (n_queries + 1) * 8));
+        if (scratch_off) HIP_TRY(upload(b->d_scratch_off.p, scratch_off, (n + 1) * 8));
+        HIP_TRY(upload(b->d_pitch.p, pitch, n * 4));
+        HIP_TRY(upload(b->plan[0].d_off.p, region_off, n * 8));
+        return POA_OK;
+    }
+    int end_upload(poa_batch* b) {
+        HIP_TRY(hipEventRecord(timed.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(timed.e[1]));
+        (void)hipEventElapsedTime(&b->ms_h2d, timed.e[0], timed.e[1]);
+        return POA_OK;
+    }
+};
+
 // u16_cells_suffice (poa_dense_plan.cpp) for one graph and the longest query that meets it
 static bool u16_cells_suffice(uint64_t open, uint64_t extend, uint64_t max_len, const FlatGraph& fg) {
     return u16_cells_suffice(open, extend, (max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0), max_len + fg.min_path_nodes);
+}
+// ... and for a batch over many graphs: u16 cells only if every graph's own bound (the longest query that meets it and its shortest
+// path) allows them.  The constructors note a graph's two counts; a run holds them against its costs.
+static void note_graph_bound(std::vector<uint64_t>& ub_open, std::vector<uint64_t>& ub_extend, uint64_t max_len, const FlatGraph& fg) {
+    ub_open.push_back((max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0));
+    ub_extend.push_back(max_len + fg.min_path_nodes);
+}
+static bool all_graphs_u16(const std::vector<uint64_t>& ub_open, const std::vector<uint64_t>& ub_extend, uint64_t open, uint64_t extend) {
+    for (size_t g = 0; g < ub_open.size(); ++g)
+        if (!u16_cells_suffice(open, extend, ub_open[g], ub_extend[g])) return false;
+    return true;
 }
 static_assert(DENSE_MW_MAX_WAVES == MW_MAX_WAVES, "the plan's waves per workgroup are the kernels'");
 
@@ -1102,20 +1239,17 @@ int poa_batch_workspace_bytes(poa_batch_t* b, uint64_t* bytes) {
     return POA_OK;
 }
 
-static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
+// the constructor behind the null check of `out` (batch_create_impl below: CreateFrame::guarded)
+static int batch_create_body(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
                              uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt, uint32_t ckpt_rows, bool ckpt2) {
-    if (!out) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: out is null");
-    *out = nullptr;
     if (!g || !qoff || (n_queries && qoff[n_queries] && !qseq))
         return fail(POA_ERR_INVALID_ARG, "poa_batch_create: null argument");
     for (uint32_t i = 0; i < n_queries; ++i) {
         if (qoff[i + 1] < qoff[i]) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: qoff not monotone");
         if (qoff[i + 1] - qoff[i] > 0x7FFFFFF0ull) return fail(POA_ERR_UNSUPPORTED, "query longer than 2^31");
     }
-    int ndev = poa_device_count();
-    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, "poa_batch_create: device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
+    CreateFrame frame{"poa_batch_create"};
+    if (const int rc = frame.open(device)) return rc;
 
     std::unique_ptr<poa_batch> b(new (std::nothrow) poa_batch);
     if (!b) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -1128,18 +1262,16 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     b->ckpt = ckpt;
     b->ckpt2 = ckpt2;
     b->ckpt_slots = g->sweep.n_slots;
-    try {
-        if (ckpt) {
-            const CheckpointPlan& own = ckpt2 ? g->ckpt2 : g->ckpt;
-            if (ckpt_rows == 0 || ckpt_rows == own.segment_rows) b->ckpt_plan = own;
-            else build_checkpoint_plan(fg, g->sweep, ckpt_rows, b->ckpt_plan, ckpt2);
-        }
-        b->h_qoff.assign(qoff, qoff + n_queries + 1);
-        b->h_pitch.resize(n_queries);
-        b->h_scratch_off.resize((size_t)n_queries + 1);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
+    if (ckpt) {
+        const CheckpointPlan& own = ckpt2 ? g->ckpt2 : g->ckpt;
+        if (ckpt_rows == 0 || ckpt_rows == own.segment_rows) b->ckpt_plan = own;
+        else build_checkpoint_plan(fg, g->sweep, ckpt_rows, b->ckpt_plan, ckpt2);
+    }
+    b->h_qoff.assign(qoff, qoff + n_queries + 1);
+    b->h_pitch.resize(n_queries);
+    b->h_scratch_off.resize((size_t)n_queries + 1);
 
-    uint64_t scratch_total = 0, max_len = 0;
+    uint64_t scratch_total = 0, max_len = 0, biggest = 0;
     std::vector<uint64_t> q_plane_elems(n_queries);
     for (uint32_t i = 0; i < n_queries; ++i) {
         const uint64_t L = qoff[i + 1] - qoff[i];
@@ -1155,12 +1287,11 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
         b->total_bases += L;
         b->total_cells += (uint64_t)rows * (L + 1);
         b->plane_bytes_total += q_plane_elems[i] * 4;
+        biggest = std::max(biggest, q_plane_elems[i] * 4);
     }
     b->h_scratch_off[n_queries] = scratch_total;
 
     // workspace: as many queries' planes as fit; chunks reuse it.
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // score-only: the carries between strips (two parities x two words per row and query in flight, poa_forward_sweep.hpp) exist
     // only when some query is longer than one 1024-column strip; they are part of what the batch holds besides the slots
     // (the two-piece checkpointed passes carry three words per row and parity: poa_checkpoint2.hpp)
@@ -1168,21 +1299,10 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     const uint64_t carry_words = ckpt2 ? 6 : 4;
     const uint64_t fixed = scratch_total * 16 + (uint64_t)n_queries * 64 + qoff[n_queries] + (64ull << 20) +
                            (sweep_carry ? 4ull * carry_words * n_queries * rows : 0);
-    uint64_t ws = workspace_bytes;
-    if (ws == 0) {
-        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
-        ws = std::min<uint64_t>(b->plane_bytes_total, avail);
-    }
-    if (sweep || ckpt) ws = std::min<uint64_t>(ws, b->plane_bytes_total);   // such a batch holds its own footprint, never more (workspace_bytes is a cap)
-    uint64_t biggest = 0;
-    for (uint32_t i = 0; i < n_queries; ++i) biggest = std::max(biggest, q_plane_elems[i] * 4);
-    if (ws < biggest) {
-        if (workspace_bytes == 0 || workspace_bytes < biggest) {
-            if (biggest + fixed > free_b)
-                return fail(POA_ERR_OUT_OF_MEMORY, "score planes of the largest query do not fit in device memory");
-            ws = biggest;
-        }
-    }
+    // (a score-only or checkpointed batch holds its own footprint, never more: workspace_bytes is a cap)
+    uint64_t ws = 0;
+    if (const int rc = frame.workspace(workspace_bytes, fixed, b->plane_bytes_total, biggest, sweep || ckpt,
+                                       "score planes of the largest query do not fit in device memory", ws)) return rc;
     // chunking, once per layout (build_chunk_plan)
     auto make_plan = [&](poa_batch::Plan& pl, uint64_t elem_bytes, bool compact_size) {
         build_chunk_plan(pl, n_queries, ws, elem_bytes, [&](uint32_t i) {
@@ -1216,59 +1336,32 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
         if (!cp.pred_src.empty()) HIP_TRY(hipMemcpy(b->d_ck_pred_src.p, cp.pred_src.data(), cp.pred_src.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b->d_ck_boundary.p, cp.boundary.data(), cp.boundary.size() * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n_queries], 1)));
-    HIP_TRY(b->d_qoff.alloc((size_t)n_queries + 1));
-    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n_queries, 1)));
-    for (int k = 0; k < (b->plan16_same ? 1 : 3); ++k) HIP_TRY(b->plan[k].d_off.alloc(std::max<uint32_t>(n_queries, 1)));
-    HIP_TRY(b->d_scratch_off.alloc((size_t)n_queries + 1));
-    HIP_TRY(b->d_pair_off.alloc((size_t)n_queries + 1));
-    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n_queries, 1)));
-    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n_queries, 1)));
-    HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n_queries, 1)));
-    HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>((sweep_tables ? (sweep_carry ? carry_words : 0ull) : 2ull) * max_chunk_any * rows, 1)));
-    HIP_TRY(b->d_pipeline_error.alloc(1));
-    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
-    if (n_queries) {
-        std::string werr;
-        if (!b->d_planes.acquire(device, ws + 256, werr, sweep_tables)) return fail(POA_ERR_OUT_OF_MEMORY, "score-plane workspace: " + werr);
-    }
+    if (const int rc = frame.alloc_results(b.get(), qoff[n_queries], n_queries, n_queries, true, scratch_total)) return rc;
+    if (!b->plan16_same) HIP_TRY(CreateFrame::alloc_each(n_queries, b->plan[1].d_off, b->plan[2].d_off));
+    HIP_TRY(CreateFrame::alloc_each((sweep_tables ? (sweep_carry ? carry_words : 0ull) : 2ull) * max_chunk_any * rows, b->d_carry));
+    if (const int rc = frame.acquire_planes(b.get(), ws + 256, sweep_tables, "score-plane workspace")) return rc;
 
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    HIP_TRY(hipMemcpy(b->d_rows.p, fg.rows.data(), fg.rows.size() * sizeof(RowMeta), hipMemcpyHostToDevice));
-    if (!fg.pred_rows.empty())
-        HIP_TRY(hipMemcpy(b->d_pred_rows.p, fg.pred_rows.data(), fg.pred_rows.size() * 4, hipMemcpyHostToDevice));
-    if (!fg.pred_k.empty())
-        HIP_TRY(hipMemcpy(b->d_pred_k.p, fg.pred_k.data(), fg.pred_k.size() * 4, hipMemcpyHostToDevice));
-    if (!fg.row_depth.empty())
-        HIP_TRY(hipMemcpy(b->d_row_depth.p, fg.row_depth.data(), fg.row_depth.size() * 4, hipMemcpyHostToDevice));
-    const std::vector<uint32_t>& h_slot = sweep_tables ? g->sweep.slot : fg.d_slot;
-    const std::vector<uint32_t>& h_pred_slot = sweep_tables ? g->sweep.pred_slot : fg.pred_dslot;
-    if (!h_slot.empty())
-        HIP_TRY(hipMemcpy(b->d_dslot.p, h_slot.data(), h_slot.size() * 4, hipMemcpyHostToDevice));
-    if (!h_pred_slot.empty())
-        HIP_TRY(hipMemcpy(b->d_pred_dslot.p, h_pred_slot.data(), h_pred_slot.size() * 4, hipMemcpyHostToDevice));
+    if (const int rc = frame.begin_upload()) return rc;
+    HIP_TRY(CreateFrame::upload(b->d_rows, fg.rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_rows, fg.pred_rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_k, fg.pred_k));
+    HIP_TRY(CreateFrame::upload(b->d_row_depth, fg.row_depth));
+    HIP_TRY(CreateFrame::upload(b->d_dslot, sweep_tables ? g->sweep.slot : fg.d_slot));
+    HIP_TRY(CreateFrame::upload(b->d_pred_dslot, sweep_tables ? g->sweep.pred_slot : fg.pred_dslot));
     if (sweep) HIP_TRY(hipMemset(b->d_pair_off.p, 0, ((size_t)n_queries + 1) * 8));
-    if (qoff[n_queries]) HIP_TRY(hipMemcpy(b->d_qseq.p, qseq, qoff[n_queries], hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_qoff.p, qoff, ((size_t)n_queries + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->d_scratch_off.p, b->h_scratch_off.data(), ((size_t)n_queries + 1) * 8, hipMemcpyHostToDevice));
-    if (n_queries) {
-        HIP_TRY(hipMemcpy(b->d_pitch.p, b->h_pitch.data(), (size_t)n_queries * 4, hipMemcpyHostToDevice));
-        for (int k = 0; k < (b->plan16_same ? 1 : 3); ++k)
-            HIP_TRY(hipMemcpy(b->plan[k].d_off.p, b->plan[k].off.data(), (size_t)n_queries * 8, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (const int rc = frame.upload_queries(b.get(), qseq, qoff, n_queries, b->h_scratch_off.data(), b->h_pitch.data(), b->plan[0].off.data(), n_queries)) return rc;
+    if (!b->plan16_same) for (int k = 1; k < 3; ++k) HIP_TRY(CreateFrame::upload(b->plan[k].d_off, b->plan[k].off));
+    if (const int rc = frame.end_upload(b.get())) return rc;
 
     *out = b.release();
     return POA_OK;
+}
+
+static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_queries, const uint8_t* qseq, const uint64_t* qoff,
+                             uint64_t workspace_bytes, bool sweep, poa_batch_t** out, bool ckpt, uint32_t ckpt_rows, bool ckpt2) {
+    return CreateFrame::enter("poa_batch_create", out, "host allocation failed", [&] {
+        return batch_create_body(g, device, n_queries, qseq, qoff, workspace_bytes, sweep, out, ckpt, ckpt_rows, ckpt2);
+    });
 }
 
 static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_config_t* cfg) {
@@ -2418,6 +2511,8 @@ struct poa_multi {
 };
 
 namespace {
+enum class MultiKind { checkpoint, checkpoint2, dense };   // what a poa_multi holds: its plan, its footprint, its run
+
 int multi_mode_check(const poa_config_t* cfg, const char* who, bool two_piece = false) {
     if (cfg && cfg->mode != (two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT))
         return fail(POA_ERR_UNSUPPORTED, std::string(who) + (two_piece ? ": a two-piece multi-graph batch runs in POA_MODE_CHECKPOINT2 only"
@@ -2426,160 +2521,140 @@ int multi_mode_check(const poa_config_t* cfg, const char* who, bool two_piece = 
         return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": checkpointed mode is Global: an ends-free result is defined by the reference's search");
     return POA_OK;
 }
+int multi_dense_mode_check(const poa_config_t* cfg, const char* who) {
+    if (cfg && cfg->mode != POA_MODE_DENSE)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch runs in POA_MODE_DENSE only (the checkpointed batches: poa_multi_create, poa_multi_create_2piece)");
+    if (cfg && cfg->span != POA_SPAN_GLOBAL)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch is Global: an ends-free result is defined by the reference's search");
+    return POA_OK;
+}
+int multi_mode_check(MultiKind kind, const poa_config_t* cfg, const char* who) {
+    return kind == MultiKind::dense ? multi_dense_mode_check(cfg, who) : multi_mode_check(cfg, who, kind == MultiKind::checkpoint2);
+}
 
-int multi_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                  const poa_config_t* cfg, uint64_t workspace_bytes, MultiPlan& plan, const char* who, bool two_piece = false) {
+// the plan of the kind (build_multi_plan with the model's weights, build_multi_dense_plan) behind the checks of the handles
+int multi_plan_of(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                  const poa_config_t* cfg, uint64_t workspace_bytes, MultiPlan& plan, const char* who) {
     if (!graph_qoff || !qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    const bool two_piece = kind == MultiKind::checkpoint2;
     std::vector<MultiGraphIn> in(n_graphs);
     for (uint32_t g = 0; g < n_graphs; ++g) {
         if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
         in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, two_piece ? &graphs[g]->ckpt2 : &graphs[g]->ckpt};
     }
-    uint32_t seg_rows = 0;
-    { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
     std::string err;
-    const int rc = build_multi_plan(in.data(), n_graphs, graph_qoff, qoff, seg_rows, workspace_bytes, plan, err, two_piece);
+    int rc;
+    if (kind == MultiKind::dense) {
+        rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
+    } else {
+        uint32_t seg_rows = 0;
+        { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
+        rc = build_multi_plan(in.data(), n_graphs, graph_qoff, qoff, seg_rows, workspace_bytes, plan, err, two_piece);
+    }
     if (rc != 0) return fail(rc, std::string(who) + ": " + err);
     return POA_OK;
 }
 
-// poa_multi_footprint and poa_multi_footprint_2piece: the same sum with the plan of the model
-int multi_footprint_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                         const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes, bool two_piece, const char* who_c) {
+// poa_multi_footprint, _2piece and _dense: the same sum with the plan of the kind
+int multi_footprint_impl(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                         const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes, const char* who_c) {
     const std::string who(who_c);
     if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
-    int rc = multi_mode_check(cfg, who_c, two_piece);
-    if (rc != POA_OK) return rc;
-    MultiPlan plan;
-    try {
-        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, who_c, two_piece);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
-    if (rc != POA_OK) return rc;
-    if (bytes) *bytes = plan.bytes_total;
-    if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
+    if (const int rc = multi_mode_check(kind, cfg, who_c)) return rc;
+    return CreateFrame::guarded(who + ": host allocation failed", [&]() -> int {
+        MultiPlan plan;
+        if (const int rc = multi_plan_of(kind, graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, who_c)) return rc;
+        if (bytes) *bytes = plan.bytes_total;
+        if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
+        return POA_OK;
+    });
+}
+
+// What the constructors of a poa_multi share in front of their tables: the handle, the two-pass plan around the device check,
+// the core batch.
+int multi_create_open(CreateFrame& frame, MultiKind kind, std::unique_ptr<poa_multi>& m, const poa_graph_t* const* graphs, uint32_t n_graphs,
+                      const uint64_t* graph_qoff, int device, const uint8_t* qseq, const uint64_t* qoff, const poa_config_t* cfg,
+                      uint64_t workspace_bytes, const char* refusal) {
+    const char* who_c = frame.who.c_str();
+    if (const int rc = multi_mode_check(kind, cfg, who_c)) return rc;
+    m.reset(new (std::nothrow) poa_multi);
+    if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
+    m->dense = kind == MultiKind::dense;
+    MultiPlan& pl = m->plan;
+    auto plan_of = [&](uint64_t ws, MultiPlan& plan) { return multi_plan_of(kind, graphs, n_graphs, graph_qoff, qoff, cfg, ws, plan, who_c); };
+    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
+    if (const int rc = plan_of(0, pl)) return rc;
+    const uint32_t n = pl.n_queries;
+    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, frame.who + ": null argument");
+    if (const int rc = frame.open(device)) return rc;
+    const uint64_t fixed = pl.scratch_off[n] * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + pl.max_carry_words * 4 +
+                           (pl.n_rows_total + pl.n_edges_total) * 32;
+    if (const int rc = frame.plan_capped(pl, workspace_bytes, fixed, pl.largest_query_bytes, refusal, plan_of)) return rc;
+    // the core batch: queries, results, pair buffers, events
+    frame.fill_core(&m->core, pl, m->dense ? pl.plane_bytes : pl.bytes_total, qoff);
     return POA_OK;
+}
+
+// poa_align_multi, _2piece and _dense: create, run, fetch, destroy
+template <typename Create, typename Run>
+int multi_one_shot(Create&& create, Run&& run, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
+                   uint32_t* flags, poa_stats_t* stats) {
+    poa_multi_t* m = nullptr;
+    int rc = create(&m);
+    if (rc != POA_OK) return rc;
+    rc = run(m);
+    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
+    poa_multi_destroy(m);
+    return rc;
 }
 
 // poa_multi_create and poa_multi_create_2piece: one batch, the plan's weights, the carries and the parameter blocks by the model
 int multi_create_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
                       const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out, bool two_piece,
                       const char* who_c) {
-    const std::string who(who_c);
-    if (!out) return fail(POA_ERR_INVALID_ARG, who + ": out is null");
-    *out = nullptr;
-    int rc = multi_mode_check(cfg, who_c, two_piece);
-    if (rc != POA_OK) return rc;
-    std::unique_ptr<poa_multi> m(new (std::nothrow) poa_multi);
-    if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
-    MultiPlan& pl = m->plan;
-    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
-    try {
-        rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, 0, pl, who_c, two_piece);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
-    if (rc != POA_OK) return rc;
+    CreateFrame frame{who_c};
+    std::unique_ptr<poa_multi> m;
+    if (const int rc = multi_create_open(frame, two_piece ? MultiKind::checkpoint2 : MultiKind::checkpoint, m, graphs, n_graphs, graph_qoff, device,
+                                         qseq, qoff, cfg, workspace_bytes, "the checkpointed footprint of the largest query does not fit in device memory"))
+        return rc;
+    const MultiPlan& pl = m->plan;
     const uint32_t n = pl.n_queries;
-    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
-    const int ndev = poa_device_count();
-    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, who + ": device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t scratch_total = pl.scratch_off[n];
-    const uint64_t fixed = scratch_total * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + pl.max_carry_words * 4 +
-                           (pl.n_rows_total + pl.n_edges_total) * 32;
-    uint64_t ws = workspace_bytes;
-    if (ws == 0) {
-        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
-        ws = std::min<uint64_t>(pl.bytes_total, avail);
-    }
-    if (ws < pl.largest_query_bytes) {
-        if (pl.largest_query_bytes + fixed > free_b)
-            return fail(POA_ERR_OUT_OF_MEMORY, "the checkpointed footprint of the largest query does not fit in device memory");
-        ws = pl.largest_query_bytes;
-    }
-    if (ws < pl.bytes_total) {
-        try {
-            rc = multi_plan_of(graphs, n_graphs, graph_qoff, qoff, cfg, ws, pl, who_c, two_piece);
-        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
-        if (rc != POA_OK) return rc;
-    }
-
-    // the core batch: queries, results, pair buffers, events
     poa_batch* b = &m->core;
-    b->graph = nullptr; b->device = device; b->n_queries = n;
     b->ckpt = true; b->ckpt2 = two_piece; b->last_mode = two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT;
-    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.bytes_total;
-    b->plan_ws = pl.workspace_bytes;
-    try {
-        b->h_qoff.assign(qoff, qoff + n + 1);
-        b->h_pitch = pl.pitch;
-        b->h_scratch_off = pl.scratch_off;
-        b->plan[0].off = pl.region_off;
-        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
-        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    b->active_plan = 0;
-    for (uint32_t g = 0; g < n_graphs; ++g) b->max_len = std::max(b->max_len, pl.graphs[g].max_len);
 
-    // concatenated tables, one copy per distinct handle, and the parameter block of every listed graph
+    // concatenated tables, one copy per distinct handle
     std::vector<RowMeta> h_rows(pl.n_rows_total);
     std::vector<uint32_t> h_slot(pl.n_rows_total), h_pred_rows(pl.n_edges_total), h_pred_slot(pl.n_edges_total), h_pred_src(pl.n_edges_total);
     std::vector<uint32_t> h_snap_off(pl.n_snap_off_total), h_snap_dst(pl.n_snap_dst_total), h_boundary(pl.n_boundary_total);
+    using GP = MultiGraphPlan;
+    concat_tables(h_rows, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.rows; });
+    concat_tables(h_slot, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->sweep.slot; });
+    concat_tables(h_pred_rows, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->g.pred_rows; });
+    concat_tables(h_pred_slot, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->sweep.pred_slot; });
+    concat_tables(h_pred_src, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return pl.graphs[g].ckpt.pred_src; });
+    concat_tables(h_snap_off, pl.graphs, &GP::snap_off_base, [&](uint32_t g) -> auto& { return pl.graphs[g].ckpt.snap_off; });
+    concat_tables(h_snap_dst, pl.graphs, &GP::snap_dst_base, [&](uint32_t g) -> auto& { return pl.graphs[g].ckpt.snap_dst; });
+    concat_tables(h_boundary, pl.graphs, &GP::boundary_base, [&](uint32_t g) -> auto& { return pl.graphs[g].ckpt.boundary; });
     for (uint32_t g = 0; g < n_graphs; ++g) {
         const MultiGraphPlan& gp = pl.graphs[g];
         // (two-piece: M, D1, D2 of the kept rows and five window planes, run_ckpt2's rule)
         const uint64_t stored = two_piece ? 3ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 5ull * gp.n_rows
                                           : 2ull * (graphs[g]->sweep.n_slotted + gp.ckpt.n_snap_rows) + 3ull * gp.n_rows;
         for (uint64_t i = graph_qoff[g]; i < graph_qoff[g + 1]; ++i) m->stored_rows_pitch += stored * pl.pitch[i];
-        if (gp.n_queries) {
-            m->ub_open.push_back((gp.max_len ? 1 : 0) + (graphs[g]->g.min_path_nodes ? 1 : 0));
-            m->ub_extend.push_back(gp.max_len + graphs[g]->g.min_path_nodes);
-        }
-        if (gp.table_of != g) continue;
-        const FlatGraph& fg = graphs[g]->g;
-        const SweepRows& sw = graphs[g]->sweep;
-        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
-        std::copy(sw.slot.begin(), sw.slot.end(), h_slot.begin() + gp.row_base);
-        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
-        std::copy(sw.pred_slot.begin(), sw.pred_slot.end(), h_pred_slot.begin() + gp.edge_base);
-        std::copy(gp.ckpt.pred_src.begin(), gp.ckpt.pred_src.end(), h_pred_src.begin() + gp.edge_base);
-        std::copy(gp.ckpt.snap_off.begin(), gp.ckpt.snap_off.end(), h_snap_off.begin() + gp.snap_off_base);
-        std::copy(gp.ckpt.snap_dst.begin(), gp.ckpt.snap_dst.end(), h_snap_dst.begin() + gp.snap_dst_base);
-        std::copy(gp.ckpt.boundary.begin(), gp.ckpt.boundary.end(), h_boundary.begin() + gp.boundary_base);
+        if (gp.n_queries) note_graph_bound(m->ub_open, m->ub_extend, gp.max_len, graphs[g]->g);
     }
 
-    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
-    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
-    HIP_TRY(m->d_slot.alloc(std::max<size_t>(h_slot.size(), 1)));
-    HIP_TRY(m->d_pred_slot.alloc(std::max<size_t>(h_pred_slot.size(), 1)));
-    HIP_TRY(b->d_ck_pred_src.alloc(std::max<size_t>(h_pred_src.size(), 1)));
-    HIP_TRY(b->d_ck_snap_off.alloc(std::max<size_t>(h_snap_off.size(), 1)));
-    HIP_TRY(b->d_ck_snap_dst.alloc(std::max<size_t>(h_snap_dst.size(), 1)));
-    HIP_TRY(b->d_ck_boundary.alloc(std::max<size_t>(h_boundary.size(), 1)));
-    HIP_TRY(m->d_graph_of.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(m->d_carry_off.alloc(std::max<uint32_t>(n, 1)));
-    if (two_piece) HIP_TRY(m->d_params2.alloc(std::max<uint32_t>(n_graphs, 1)));
-    else HIP_TRY(m->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
-    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n], 1)));
-    HIP_TRY(b->d_qoff.alloc((size_t)n + 1));
-    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_scratch_off.alloc((size_t)n + 1));
-    HIP_TRY(b->d_pair_off.alloc((size_t)n + 1));
-    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>(pl.max_carry_words, 1)));
-    HIP_TRY(b->d_pipeline_error.alloc(1));
-    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
-    if (n) {
-        std::string werr;
-        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "checkpointed workspace: " + werr);
-    }
+    HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, b->d_rows, m->d_slot));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_edges_total, b->d_pred_rows, m->d_pred_slot, b->d_ck_pred_src));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_snap_off_total, b->d_ck_snap_off));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_snap_dst_total, b->d_ck_snap_dst));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_boundary_total, b->d_ck_boundary));
+    HIP_TRY(CreateFrame::alloc_each(n, m->d_graph_of, m->d_carry_off));
+    if (two_piece) HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_params2));
+    else HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_params));
+    if (const int rc = frame.alloc_results(b, qoff[n], n, n, true, pl.scratch_off[n])) return rc;
+    HIP_TRY(CreateFrame::alloc_each(pl.max_carry_words, b->d_carry));
+    if (const int rc = frame.acquire_planes(b, pl.workspace_bytes, true, "checkpointed workspace")) return rc;
 
     // one block per listed graph, CkptParams or Ckpt2Params by the model: the same fields but for the type of `scratch`
     std::vector<MultiGraphParams> h_params(two_piece ? 0 : n_graphs);
@@ -2606,33 +2681,95 @@ int multi_create_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const
         else fill(h_params[g], g);
     }
 
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
-    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
-    HIP_TRY(up(m->d_slot.p, h_slot.data(), h_slot.size() * 4));
-    HIP_TRY(up(m->d_pred_slot.p, h_pred_slot.data(), h_pred_slot.size() * 4));
-    HIP_TRY(up(b->d_ck_pred_src.p, h_pred_src.data(), h_pred_src.size() * 4));
-    HIP_TRY(up(b->d_ck_snap_off.p, h_snap_off.data(), h_snap_off.size() * 4));
-    HIP_TRY(up(b->d_ck_snap_dst.p, h_snap_dst.data(), h_snap_dst.size() * 4));
-    HIP_TRY(up(b->d_ck_boundary.p, h_boundary.data(), h_boundary.size() * 4));
-    if (two_piece) HIP_TRY(up(m->d_params2.p, h_params2.data(), h_params2.size() * sizeof(Multi2GraphParams)));
-    else HIP_TRY(up(m->d_params.p, h_params.data(), h_params.size() * sizeof(MultiGraphParams)));
-    HIP_TRY(up(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
-    HIP_TRY(up(m->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
-    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n]));
-    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n + 1) * 8));
-    HIP_TRY(up(b->d_scratch_off.p, pl.scratch_off.data(), ((size_t)n + 1) * 8));
-    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
-    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (const int rc = frame.begin_upload()) return rc;
+    HIP_TRY(CreateFrame::upload(b->d_rows, h_rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_rows, h_pred_rows));
+    HIP_TRY(CreateFrame::upload(m->d_slot, h_slot));
+    HIP_TRY(CreateFrame::upload(m->d_pred_slot, h_pred_slot));
+    HIP_TRY(CreateFrame::upload(b->d_ck_pred_src, h_pred_src));
+    HIP_TRY(CreateFrame::upload(b->d_ck_snap_off, h_snap_off));
+    HIP_TRY(CreateFrame::upload(b->d_ck_snap_dst, h_snap_dst));
+    HIP_TRY(CreateFrame::upload(b->d_ck_boundary, h_boundary));
+    if (two_piece) HIP_TRY(CreateFrame::upload(m->d_params2, h_params2));
+    else HIP_TRY(CreateFrame::upload(m->d_params, h_params));
+    HIP_TRY(CreateFrame::upload(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    HIP_TRY(CreateFrame::upload(m->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
+    if (const int rc = frame.upload_queries(b, qseq, qoff, n, pl.scratch_off.data(), pl.pitch.data(), pl.region_off.data(), n)) return rc;
+    if (const int rc = frame.end_upload(b)) return rc;
+
+    *out = m.release();
+    return POA_OK;
+}
+
+// poa_multi_create_dense: one batch of compact u16 planes, one MultiDenseBlock per listed graph
+int multi_create_dense_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                            const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    CreateFrame frame{"poa_multi_create_dense"};
+    std::unique_ptr<poa_multi> m;
+    if (const int rc = multi_create_open(frame, MultiKind::dense, m, graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes,
+                                         "the compact planes of the largest query do not fit in device memory"))
+        return rc;
+    const MultiPlan& pl = m->plan;
+    const uint32_t n = pl.n_queries;
+    poa_batch* b = &m->core;
+    b->last_mode = POA_MODE_DENSE;
+
+    // concatenated tables, one copy per distinct handle: rows and d_slot by row, pred_rows and pred_dslot by edge
+    // (a graph without a d_slot table keeps its D rows by row: its part stays zero and its blocks carry null table pointers)
+    std::vector<RowMeta> h_rows(pl.n_rows_total);
+    std::vector<uint32_t> h_dslot(pl.n_rows_total, 0u), h_pred_rows(pl.n_edges_total), h_pred_dslot(pl.n_edges_total, 0u);
+    using GP = MultiGraphPlan;
+    concat_tables(h_rows, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.rows; });
+    concat_tables(h_pred_rows, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->g.pred_rows; });
+    concat_tables(h_dslot, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.d_slot; });
+    concat_tables(h_pred_dslot, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->g.pred_dslot; });
+    for (uint32_t g = 0; g < n_graphs; ++g)
+        if (pl.graphs[g].n_queries) note_graph_bound(m->ub_open, m->ub_extend, pl.graphs[g].max_len, graphs[g]->g);
+
+    HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, b->d_rows, m->d_slot));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_edges_total, b->d_pred_rows, m->d_pred_slot));
+    HIP_TRY(CreateFrame::alloc_each(n, m->d_graph_of));
+    HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_dense));
+    if (const int rc = frame.alloc_results(b, qoff[n], n, n, true, pl.scratch_off[n])) return rc;
+    HIP_TRY(CreateFrame::alloc_each(1, b->d_carry));   // FwdParams::strip_carry: a valid address that one-strip queries never touch
+    if (const int rc = frame.acquire_planes(b, pl.workspace_bytes, true, "dense multi-graph workspace")) return rc;
+
+    // one block per listed graph: what poa_batch_run_ex puts into FwdParams / TbParams for that graph alone, absolute encoding
+    std::vector<MultiDenseBlock> h_blocks(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        MultiDenseBlock& mb = h_blocks[g];
+        std::memset(&mb, 0, sizeof(mb));
+        const bool by_row = fg.d_slot.empty();
+        FwdParams& fp = mb.F;
+        fp.rows = b->d_rows.p + gp.row_base; fp.pred_rows = b->d_pred_rows.p + gp.edge_base; fp.n_rows = fg.n;
+        fp.qseq = b->d_qseq.p; fp.qoff = b->d_qoff.p; fp.pitch = b->d_pitch.p; fp.plane_off = b->plan[0].d_off.p;
+        fp.planes = b->d_planes.p; fp.strip_carry = b->d_carry.p;
+        fp.pred_k = nullptr;
+        fp.d_slot = by_row ? nullptr : m->d_slot.p + gp.row_base; fp.pred_dslot = by_row ? nullptr : m->d_pred_slot.p + gp.edge_base;
+        fp.pipeline_error = b->d_pipeline_error.p;
+        TbParams& tp = mb.T;
+        tp.rows = fp.rows; tp.pred_rows = fp.pred_rows; tp.n_rows = fg.n;
+        tp.start_row = fg.start_row; tp.end_row = fg.end_row;
+        tp.qseq = fp.qseq; tp.qoff = fp.qoff; tp.pitch = fp.pitch; tp.plane_off = fp.plane_off;
+        tp.planes = b->d_planes.p; tp.scratch_off = b->d_scratch_off.p; tp.scratch = b->d_scratch.p;
+        tp.score = b->d_score.p; tp.flags = b->d_flags.p; tp.n_pairs = b->d_npairs.p;
+        tp.exact_pass = 0; tp.ex_status = nullptr; tp.ex_end = nullptr; tp.code_fmt = 0;
+        tp.row_depth = nullptr;
+        tp.d_slot = fp.d_slot; tp.pred_dslot = fp.pred_dslot;
+        mb.empty = fg.n_real == 0 ? 1u : 0u;
+    }
+
+    if (const int rc = frame.begin_upload()) return rc;
+    HIP_TRY(CreateFrame::upload(b->d_rows, h_rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_rows, h_pred_rows));
+    HIP_TRY(CreateFrame::upload(m->d_slot, h_dslot));
+    HIP_TRY(CreateFrame::upload(m->d_pred_slot, h_pred_dslot));
+    HIP_TRY(CreateFrame::upload(m->d_dense, h_blocks));
+    HIP_TRY(CreateFrame::upload(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    if (const int rc = frame.upload_queries(b, qseq, qoff, n, pl.scratch_off.data(), pl.pitch.data(), pl.region_off.data(), n)) return rc;
+    if (const int rc = frame.end_upload(b)) return rc;
 
     *out = m.release();
     return POA_OK;
@@ -2643,22 +2780,26 @@ extern "C" {
 
 int poa_multi_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                         const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
-    return multi_footprint_impl(graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, false, "poa_multi_footprint");
+    return multi_footprint_impl(MultiKind::checkpoint, graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, "poa_multi_footprint");
 }
 
 int poa_multi_footprint_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                                const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
-    return multi_footprint_impl(graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, true, "poa_multi_footprint_2piece");
+    return multi_footprint_impl(MultiKind::checkpoint2, graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, "poa_multi_footprint_2piece");
 }
 
 int poa_multi_create(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
                      const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
-    return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, false, "poa_multi_create");
+    const char* who = "poa_multi_create";
+    return CreateFrame::enter(who, out, std::string(who) + ": host allocation failed",
+                              [&] { return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, false, who); });
 }
 
 int poa_multi_create_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
                             const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
-    return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, true, "poa_multi_create_2piece");
+    const char* who = "poa_multi_create_2piece";
+    return CreateFrame::enter(who, out, std::string(who) + ": host allocation failed",
+                              [&] { return multi_create_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, true, who); });
 }
 
 // per chunk the sweep with snapshots (pass 1), then recompute-and-walk (pass 2), over the queries of all graphs; scan and
@@ -2677,9 +2818,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     RunFrame run;
     if (const int rc = run.open(b, "poa_multi_run: call poa_multi_stats/fetch at least every 256 runs")) return rc;
     // u16 cells only if every graph's own bound (that graph's longest query and shortest path) allows them
-    bool narrow = !planes32(T);
-    for (size_t g = 0; g < m->ub_open.size(); ++g)
-        narrow = narrow && u16_cells_suffice(costs->gap_open, costs->gap_extend, m->ub_open[g], m->ub_extend[g]);
+    const bool narrow = !planes32(T) && all_graphs_u16(m->ub_open, m->ub_extend, costs->gap_open, costs->gap_extend);
     const MultiPlan& pl = m->plan;
     if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT;
@@ -2727,9 +2866,7 @@ int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_co
     if (const int rc = run.open(b, "poa_multi_run_2piece: call poa_multi_stats/fetch at least every 256 runs")) return rc;
     // u16 cells only if every graph's own bound (the first piece's costs, that graph's longest query and shortest path) allows
     // them, and neither wide_planes nor the planes tunable asks for u32
-    bool narrow = !costs->wide_planes && !planes32(T);
-    for (size_t g = 0; g < m->ub_open.size(); ++g)
-        narrow = narrow && u16_cells_suffice(costs->gap_open1, costs->gap_extend1, m->ub_open[g], m->ub_extend[g]);
+    const bool narrow = !costs->wide_planes && !planes32(T) && all_graphs_u16(m->ub_open, m->ub_extend, costs->gap_open1, costs->gap_extend1);
     const MultiPlan& pl = m->plan;
     if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
     b->last_mode = POA_MODE_CHECKPOINT2;
@@ -2796,13 +2933,8 @@ int poa_align_multi(const poa_graph_t* const* graphs, uint32_t n_graphs, const u
                     uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
     if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi: null argument");
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    poa_multi_t* m = nullptr;
-    int rc = poa_multi_create(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
-    if (rc != POA_OK) return rc;
-    rc = poa_multi_run(m, costs, cfg, nullptr);
-    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
-    poa_multi_destroy(m);
-    return rc;
+    return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
+                          [&](poa_multi_t* m) { return poa_multi_run(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
 }
 
 int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs2_t* costs,
@@ -2812,13 +2944,8 @@ int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (costs->gap_extend1 < costs->gap_extend2)   // (before a batch is made for it)
         return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
-    poa_multi_t* m = nullptr;
-    int rc = poa_multi_create_2piece(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
-    if (rc != POA_OK) return rc;
-    rc = poa_multi_run_2piece(m, costs, cfg, nullptr);
-    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
-    poa_multi_destroy(m);
-    return rc;
+    return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_2piece(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
+                          [&](poa_multi_t* m) { return poa_multi_run_2piece(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
 }
 
 }  // extern "C"
@@ -2828,31 +2955,8 @@ int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 // The same object as the checkpointed batches above, of a third kind (poa_multi::dense): the workspace holds every query's
 // compact u16 planes, a run is the packed forward launch and the walk launch per chunk, then the scan and compaction of pairs.
 // The core is a dense poa_batch (ckpt not set), so poa_multi_fetch / _stats / _device_results / _workspace_bytes / _destroy
-// serve it unchanged and poa_stats_t.plane_bytes is the planes' own size.
-namespace {
-int multi_dense_mode_check(const poa_config_t* cfg, const char* who) {
-    if (cfg && cfg->mode != POA_MODE_DENSE)
-        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch runs in POA_MODE_DENSE only (the checkpointed batches: poa_multi_create, poa_multi_create_2piece)");
-    if (cfg && cfg->span != POA_SPAN_GLOBAL)
-        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch is Global: an ends-free result is defined by the reference's search");
-    return POA_OK;
-}
-
-int multi_dense_plan_of(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                        uint64_t workspace_bytes, MultiPlan& plan, const char* who) {
-    if (!graph_qoff || !qoff || (n_graphs && !graphs)) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    std::vector<MultiGraphIn> in(n_graphs);
-    for (uint32_t g = 0; g < n_graphs; ++g) {
-        if (!graphs[g]) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null graph");
-        in[g] = MultiGraphIn{&graphs[g]->g, &graphs[g]->sweep, &graphs[g]->ckpt};
-    }
-    std::string err;
-    const int rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
-    if (rc != 0) return fail(rc, std::string(who) + ": " + err);
-    return POA_OK;
-}
-}  // namespace
-
+// serve it unchanged and poa_stats_t.plane_bytes is the planes' own size.  Its mode check, plan and constructor stand with the
+// other two kinds' above (MultiKind::dense, multi_create_dense_impl).
 extern "C" {
 
 int poa_graph_compact_elems(const poa_graph_t* g, uint32_t len, uint64_t* elems) {
@@ -2864,177 +2968,13 @@ int poa_graph_compact_elems(const poa_graph_t* g, uint32_t len, uint64_t* elems)
 
 int poa_multi_footprint_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                               const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
-    const char* who = "poa_multi_footprint_dense";
-    if (!bytes && !largest_query_bytes) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
-    int rc = multi_dense_mode_check(cfg, who);
-    if (rc != POA_OK) return rc;
-    MultiPlan plan;
-    try {
-        rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, 0, plan, who);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
-    if (rc != POA_OK) return rc;
-    if (bytes) *bytes = plan.bytes_total;
-    if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
-    return POA_OK;
+    return multi_footprint_impl(MultiKind::dense, graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, "poa_multi_footprint_dense");
 }
 
 int poa_multi_create_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
                            const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
-    const char* who_c = "poa_multi_create_dense";
-    const std::string who(who_c);
-    if (!out) return fail(POA_ERR_INVALID_ARG, who + ": out is null");
-    *out = nullptr;
-    int rc = multi_dense_mode_check(cfg, who_c);
-    if (rc != POA_OK) return rc;
-    std::unique_ptr<poa_multi> m(new (std::nothrow) poa_multi);
-    if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
-    m->dense = true;
-    MultiPlan& pl = m->plan;
-    // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
-    try {
-        rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, 0, pl, who_c);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
-    if (rc != POA_OK) return rc;
-    const uint32_t n = pl.n_queries;
-    if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, who + ": null argument");
-    const int ndev = poa_device_count();
-    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, who + ": device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t scratch_total = pl.scratch_off[n];
-    const uint64_t fixed = scratch_total * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + (pl.n_rows_total + pl.n_edges_total) * 32;
-    uint64_t ws = workspace_bytes;
-    if (ws == 0) {
-        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
-        ws = std::min<uint64_t>(pl.bytes_total, avail);
-    }
-    if (ws < pl.largest_query_bytes) {
-        if (pl.largest_query_bytes + fixed > free_b)
-            return fail(POA_ERR_OUT_OF_MEMORY, "the compact planes of the largest query do not fit in device memory");
-        ws = pl.largest_query_bytes;
-    }
-    if (ws < pl.bytes_total) {
-        try {
-            rc = multi_dense_plan_of(graphs, n_graphs, graph_qoff, qoff, ws, pl, who_c);
-        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, who + ": host allocation failed"); }
-        if (rc != POA_OK) return rc;
-    }
-
-    // the core batch: queries, results, pair buffers, events
-    poa_batch* b = &m->core;
-    b->graph = nullptr; b->device = device; b->n_queries = n;
-    b->last_mode = POA_MODE_DENSE;
-    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.plane_bytes;
-    b->plan_ws = pl.workspace_bytes;
-    try {
-        b->h_qoff.assign(qoff, qoff + n + 1);
-        b->h_pitch = pl.pitch;
-        b->h_scratch_off = pl.scratch_off;
-        b->plan[0].off = pl.region_off;
-        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
-        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    b->active_plan = 0;
-    for (uint32_t g = 0; g < n_graphs; ++g) b->max_len = std::max(b->max_len, pl.graphs[g].max_len);
-
-    // concatenated tables, one copy per distinct handle: rows and d_slot by row, pred_rows and pred_dslot by edge
-    std::vector<RowMeta> h_rows(pl.n_rows_total);
-    std::vector<uint32_t> h_dslot(pl.n_rows_total, 0u), h_pred_rows(pl.n_edges_total), h_pred_dslot(pl.n_edges_total, 0u);
-    for (uint32_t g = 0; g < n_graphs; ++g) {
-        const MultiGraphPlan& gp = pl.graphs[g];
-        const FlatGraph& fg = graphs[g]->g;
-        if (gp.n_queries) {
-            m->ub_open.push_back((gp.max_len ? 1 : 0) + (fg.min_path_nodes ? 1 : 0));
-            m->ub_extend.push_back(gp.max_len + fg.min_path_nodes);
-        }
-        if (gp.table_of != g) continue;
-        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
-        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
-        if (!fg.d_slot.empty()) {   // (else the graph keeps its D rows by row: its blocks carry null table pointers)
-            std::copy(fg.d_slot.begin(), fg.d_slot.end(), h_dslot.begin() + gp.row_base);
-            std::copy(fg.pred_dslot.begin(), fg.pred_dslot.end(), h_pred_dslot.begin() + gp.edge_base);
-        }
-    }
-
-    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
-    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
-    HIP_TRY(m->d_slot.alloc(std::max<size_t>(h_dslot.size(), 1)));
-    HIP_TRY(m->d_pred_slot.alloc(std::max<size_t>(h_pred_dslot.size(), 1)));
-    HIP_TRY(m->d_graph_of.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(m->d_dense.alloc(std::max<uint32_t>(n_graphs, 1)));
-    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n], 1)));
-    HIP_TRY(b->d_qoff.alloc((size_t)n + 1));
-    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_scratch_off.alloc((size_t)n + 1));
-    HIP_TRY(b->d_pair_off.alloc((size_t)n + 1));
-    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_npairs.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_scratch.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_pairs.alloc(std::max<uint64_t>(scratch_total, 1)));
-    HIP_TRY(b->d_carry.alloc(1));   // FwdParams::strip_carry: a valid address that one-strip queries never touch
-    HIP_TRY(b->d_pipeline_error.alloc(1));
-    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
-    if (n) {
-        std::string werr;
-        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "dense multi-graph workspace: " + werr);
-    }
-
-    // one block per listed graph: what poa_batch_run_ex puts into FwdParams / TbParams for that graph alone, absolute encoding
-    std::vector<MultiDenseBlock> h_blocks(n_graphs);
-    for (uint32_t g = 0; g < n_graphs; ++g) {
-        const MultiGraphPlan& gp = pl.graphs[g];
-        const FlatGraph& fg = graphs[g]->g;
-        MultiDenseBlock& mb = h_blocks[g];
-        std::memset(&mb, 0, sizeof(mb));
-        const bool by_row = fg.d_slot.empty();
-        FwdParams& fp = mb.F;
-        fp.rows = b->d_rows.p + gp.row_base; fp.pred_rows = b->d_pred_rows.p + gp.edge_base; fp.n_rows = fg.n;
-        fp.qseq = b->d_qseq.p; fp.qoff = b->d_qoff.p; fp.pitch = b->d_pitch.p; fp.plane_off = b->plan[0].d_off.p;
-        fp.planes = b->d_planes.p; fp.strip_carry = b->d_carry.p;
-        fp.pred_k = nullptr;
-        fp.d_slot = by_row ? nullptr : m->d_slot.p + gp.row_base; fp.pred_dslot = by_row ? nullptr : m->d_pred_slot.p + gp.edge_base;
-        fp.pipeline_error = b->d_pipeline_error.p;
-        TbParams& tp = mb.T;
-        tp.rows = fp.rows; tp.pred_rows = fp.pred_rows; tp.n_rows = fg.n;
-        tp.start_row = fg.start_row; tp.end_row = fg.end_row;
-        tp.qseq = fp.qseq; tp.qoff = fp.qoff; tp.pitch = fp.pitch; tp.plane_off = fp.plane_off;
-        tp.planes = b->d_planes.p; tp.scratch_off = b->d_scratch_off.p; tp.scratch = b->d_scratch.p;
-        tp.score = b->d_score.p; tp.flags = b->d_flags.p; tp.n_pairs = b->d_npairs.p;
-        tp.exact_pass = 0; tp.ex_status = nullptr; tp.ex_end = nullptr; tp.code_fmt = 0;
-        tp.row_depth = nullptr;
-        tp.d_slot = fp.d_slot; tp.pred_dslot = fp.pred_dslot;
-        mb.empty = fg.n_real == 0 ? 1u : 0u;
-    }
-
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
-    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
-    HIP_TRY(up(m->d_slot.p, h_dslot.data(), h_dslot.size() * 4));
-    HIP_TRY(up(m->d_pred_slot.p, h_pred_dslot.data(), h_pred_dslot.size() * 4));
-    HIP_TRY(up(m->d_dense.p, h_blocks.data(), h_blocks.size() * sizeof(MultiDenseBlock)));
-    HIP_TRY(up(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
-    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n]));
-    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n + 1) * 8));
-    HIP_TRY(up(b->d_scratch_off.p, pl.scratch_off.data(), ((size_t)n + 1) * 8));
-    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
-    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-
-    *out = m.release();
-    return POA_OK;
+    return CreateFrame::enter("poa_multi_create_dense", out, "poa_multi_create_dense: host allocation failed",
+                              [&] { return multi_create_dense_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out); });
 }
 
 // per chunk the packed forward launch over the queries of all graphs, then the walk launch; scan and compaction of the pairs
@@ -3046,9 +2986,7 @@ int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
     if (mrc != POA_OK) return mrc;
     const TuneView T(cfg);
     // the batch is sized for u16 compact cells: every graph's own bound (its longest query and shortest path) must allow them
-    bool narrow = !planes32(T);
-    for (size_t g = 0; g < m->ub_open.size(); ++g)
-        narrow = narrow && u16_cells_suffice(costs->gap_open, costs->gap_extend, m->ub_open[g], m->ub_extend[g]);
+    const bool narrow = !planes32(T) && all_graphs_u16(m->ub_open, m->ub_extend, costs->gap_open, costs->gap_extend);
     if (!narrow)
         return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_dense: the run needs u32 cells (the costs' score bound exceeds 65534 for some graph, or "
                                          "tune[POA_TUNE_PLANES] = 32) and a dense multi-graph batch holds u16 compact cells only; the checkpointed "
@@ -3102,13 +3040,8 @@ int poa_align_multi_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, c
                           uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
     if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi_dense: null argument");
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    poa_multi_t* m = nullptr;
-    int rc = poa_multi_create_dense(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, &m);
-    if (rc != POA_OK) return rc;
-    rc = poa_multi_run_dense(m, costs, cfg, nullptr);
-    if (rc == POA_OK) rc = poa_multi_fetch(m, score, pairs, pair_off, pair_capacity, flags, stats);
-    poa_multi_destroy(m);
-    return rc;
+    return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_dense(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
+                          [&](poa_multi_t* m) { return poa_multi_run_dense(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
 }
 
 }  // extern "C"
@@ -3255,9 +3188,7 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
         } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, std::string(who) + ": host allocation failed"); }
     }
     // u16 cells only if every graph's own bound (the longest query paired with it and its shortest path) allows them
-    bool narrow = !planes32(T);
-    for (size_t g = 0; g < s->ub_open.size(); ++g)
-        narrow = narrow && u16_cells_suffice(cost_o, cost_e, s->ub_open[g], s->ub_extend[g]);
+    const bool narrow = !planes32(T) && all_graphs_u16(s->ub_open, s->ub_extend, cost_o, cost_e);
     bool want_px = true;
     if (const int* xv = T.ptr(POA_TUNE_PX)) want_px = (*xv) != 0;
     const ScoreSetPlan& pl = s->plan;
@@ -3352,127 +3283,59 @@ int scoreset_run(poa_scoreset* s, uint32_t cost_x, uint32_t cost_o, uint32_t cos
     }
     return run.end();
 }
-}  // namespace
 
-extern "C" {
-
-int poa_scoreset_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff, uint64_t n_pairs,
-                           const uint32_t* pair_query, const uint32_t* pair_graph, const poa_config_t* cfg, uint64_t* bytes,
-                           uint64_t* largest_pair_bytes) {
-    if (!bytes && !largest_pair_bytes) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_footprint: null argument");
-    int rc = scoreset_mode_check(cfg, "poa_scoreset_footprint");
-    if (rc != POA_OK) return rc;
-    ScoreSetPlan plan;
-    try {
-        rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, 0, plan, "poa_scoreset_footprint");
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_footprint: host allocation failed"); }
-    if (rc != POA_OK) return rc;
-    if (bytes) *bytes = plan.bytes_total;
-    if (largest_pair_bytes) *largest_pair_bytes = plan.largest_pair_bytes;
-    return POA_OK;
-}
-
-int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int device, uint32_t n_queries, const uint8_t* qseq,
-                        const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph,
-                        const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out) {
-    if (!out) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: out is null");
-    *out = nullptr;
-    int rc = scoreset_mode_check(cfg, "poa_scoreset_create");
-    if (rc != POA_OK) return rc;
+// poa_scoreset_create behind the null check of `out`
+int scoreset_create_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, int device, uint32_t n_queries, const uint8_t* qseq,
+                         const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph,
+                         const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out) {
+    CreateFrame frame{"poa_scoreset_create"};
+    if (const int rc = scoreset_mode_check(cfg, "poa_scoreset_create")) return rc;
     std::unique_ptr<poa_scoreset> s(new (std::nothrow) poa_scoreset);
     if (!s) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
     ScoreSetPlan& pl = s->plan;
+    auto plan_of = [&](uint64_t ws, ScoreSetPlan& plan) {
+        return scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, ws, plan, "poa_scoreset_create");
+    };
     // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
-    try {
-        rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, 0, pl, "poa_scoreset_create");
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_create: host allocation failed"); }
-    if (rc != POA_OK) return rc;
+    if (const int rc = plan_of(0, pl)) return rc;
     const uint32_t n = pl.n_pairs;
     if (n_queries && qoff[n_queries] && !qseq) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: null argument");
-    const int ndev = poa_device_count();
-    if (ndev <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device visible: the gfx950 path has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_create: device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (const int rc = frame.open(device)) return rc;
     const uint64_t fixed = (uint64_t)n * 64 + (uint64_t)n_queries * 8 + qoff[n_queries] + (64ull << 20) + pl.max_carry_words * 4 +
                            (pl.n_rows_total + pl.n_edges_total) * 32;
-    uint64_t ws = workspace_bytes;
-    if (ws == 0) {
-        const uint64_t avail = free_b > fixed ? (uint64_t)((free_b - fixed) * 0.85) : 0;
-        ws = std::min<uint64_t>(pl.bytes_total, avail);
-    }
-    if (ws < pl.largest_pair_bytes) {
-        if (pl.largest_pair_bytes + fixed > free_b)
-            return fail(POA_ERR_OUT_OF_MEMORY, "the slot footprint of the largest pair does not fit in device memory");
-        ws = pl.largest_pair_bytes;
-    }
-    if (ws < pl.bytes_total) {
-        try {
-            rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, ws, pl, "poa_scoreset_create");
-        } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "poa_scoreset_create: host allocation failed"); }
-        if (rc != POA_OK) return rc;
-    }
+    if (const int rc = frame.plan_capped(pl, workspace_bytes, fixed, pl.largest_pair_bytes,
+                                         "the slot footprint of the largest pair does not fit in device memory", plan_of)) return rc;
 
     // the core batch: one "query" per pair — results, events, statistics
     poa_batch* b = &s->core;
-    b->graph = nullptr; b->device = device; b->n_queries = n;
+    frame.fill_core(b, pl, n, pl.bytes_total);
     b->sweep = true; b->last_mode = POA_MODE_SCORE;
-    b->total_bases = pl.total_bases; b->total_cells = pl.total_cells; b->plane_bytes_total = pl.bytes_total;
-    b->plan_ws = pl.workspace_bytes;
-    try {
-        for (const auto& c : pl.chunks) b->plan[0].chunks.push_back({c.first, c.count});
-        for (const auto& c : pl.chunks) b->plan[0].max_chunk = std::max(b->plan[0].max_chunk, c.count);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    b->active_plan = 0;
 
-    // concatenated tables, one copy per distinct handle, and the parameter block of every listed graph
+    // concatenated tables, one copy per distinct handle
     std::vector<RowMeta> h_rows(pl.n_rows_total);
     std::vector<uint32_t> h_slot(pl.n_rows_total), h_pred_rows(pl.n_edges_total), h_pred_slot(pl.n_edges_total);
-    try {
-        s->cut.assign(pl.n_rows_total, 0);
-    } catch (const std::bad_alloc&) { return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
-    for (uint32_t g = 0; g < n_graphs; ++g)
-        if (pl.graphs[g].table_of == g) std::copy(graphs[g]->sweep.cut.begin(), graphs[g]->sweep.cut.end(), s->cut.begin() + pl.graphs[g].row_base);
+    s->cut.assign(pl.n_rows_total, 0);
+    using GP = ScoreSetGraphPlan;
+    concat_tables(s->cut, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->sweep.cut; });
+    concat_tables(h_rows, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.rows; });
+    concat_tables(h_slot, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->sweep.slot; });
+    concat_tables(h_pred_rows, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->g.pred_rows; });
+    concat_tables(h_pred_slot, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->sweep.pred_slot; });
     for (uint32_t g = 0; g < n_graphs; ++g) {
         const ScoreSetGraphPlan& gp = pl.graphs[g];
-        if (gp.n_pairs) {
-            s->ub_open.push_back((gp.max_len ? 1 : 0) + (graphs[g]->g.min_path_nodes ? 1 : 0));
-            s->ub_extend.push_back(gp.max_len + graphs[g]->g.min_path_nodes);
-            b->max_len = std::max(b->max_len, gp.max_len);
-        }
-        if (gp.table_of != g) continue;
-        const FlatGraph& fg = graphs[g]->g;
-        const SweepRows& sw = graphs[g]->sweep;
-        std::copy(fg.rows.begin(), fg.rows.end(), h_rows.begin() + gp.row_base);
-        std::copy(sw.slot.begin(), sw.slot.end(), h_slot.begin() + gp.row_base);
-        std::copy(fg.pred_rows.begin(), fg.pred_rows.end(), h_pred_rows.begin() + gp.edge_base);
-        std::copy(sw.pred_slot.begin(), sw.pred_slot.end(), h_pred_slot.begin() + gp.edge_base);
+        if (!gp.n_pairs) continue;
+        note_graph_bound(s->ub_open, s->ub_extend, gp.max_len, graphs[g]->g);
+        b->max_len = std::max(b->max_len, gp.max_len);
     }
 
-    HIP_TRY(b->d_rows.alloc(std::max<size_t>(h_rows.size(), 1)));
-    HIP_TRY(b->d_pred_rows.alloc(std::max<size_t>(h_pred_rows.size(), 1)));
-    HIP_TRY(s->d_slot.alloc(std::max<size_t>(h_slot.size(), 1)));
-    HIP_TRY(s->d_pred_slot.alloc(std::max<size_t>(h_pred_slot.size(), 1)));
-    HIP_TRY(s->d_pair_graph.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(s->d_pair_query.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(s->d_carry_off.alloc(std::max<uint32_t>(n, 1)));
-    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(s->d_class_list[v].alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(s->d_params.alloc(std::max<uint32_t>(n_graphs, 1)));
-    HIP_TRY(b->d_qseq.alloc(std::max<uint64_t>(qoff[n_queries], 1)));
-    HIP_TRY(b->d_qoff.alloc((size_t)n_queries + 1));
-    HIP_TRY(b->d_pitch.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->plan[0].d_off.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_score.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_flags.alloc(std::max<uint32_t>(n, 1)));
-    HIP_TRY(b->d_carry.alloc(std::max<uint64_t>(pl.max_carry_words, 1)));
-    HIP_TRY(b->d_pipeline_error.alloc(1));
-    HIP_TRY(hipMemset(b->d_pipeline_error.p, 0, 4));
-    if (n) {
-        std::string werr;
-        if (!b->d_planes.acquire(device, pl.workspace_bytes, werr, true)) return fail(POA_ERR_OUT_OF_MEMORY, "score-set workspace: " + werr);
-    }
+    HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, b->d_rows, s->d_slot));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_edges_total, b->d_pred_rows, s->d_pred_slot));
+    HIP_TRY(CreateFrame::alloc_each(n, s->d_pair_graph, s->d_pair_query, s->d_carry_off));
+    for (auto& list : s->d_class_list) HIP_TRY(CreateFrame::alloc_each(n, list));
+    HIP_TRY(CreateFrame::alloc_each(n_graphs, s->d_params));
+    if (const int rc = frame.alloc_results(b, qoff[n_queries], n_queries, n, false, 0)) return rc;
+    HIP_TRY(CreateFrame::alloc_each(pl.max_carry_words, b->d_carry));
+    if (const int rc = frame.acquire_planes(b, pl.workspace_bytes, true, "score-set workspace")) return rc;
 
     std::vector<ScoreGraphParams> h_params(n_graphs);
     for (uint32_t g = 0; g < n_graphs; ++g) {
@@ -3489,32 +3352,46 @@ int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int
         sp.empty = gp.empty ? 1u : 0u;
     }
 
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    auto up = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess; };
-    HIP_TRY(up(b->d_rows.p, h_rows.data(), h_rows.size() * sizeof(RowMeta)));
-    HIP_TRY(up(b->d_pred_rows.p, h_pred_rows.data(), h_pred_rows.size() * 4));
-    HIP_TRY(up(s->d_slot.p, h_slot.data(), h_slot.size() * 4));
-    HIP_TRY(up(s->d_pred_slot.p, h_pred_slot.data(), h_pred_slot.size() * 4));
-    HIP_TRY(up(s->d_params.p, h_params.data(), h_params.size() * sizeof(ScoreGraphParams)));
-    HIP_TRY(up(s->d_pair_graph.p, pl.pair_graph.data(), (size_t)n * 4));
-    HIP_TRY(up(s->d_pair_query.p, pl.pair_query.data(), (size_t)n * 4));
-    HIP_TRY(up(s->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
-    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(up(s->d_class_list[v].p, pl.class_list[v].data(), (size_t)n * 4));
-    HIP_TRY(up(b->d_qseq.p, qseq, qoff[n_queries]));
-    HIP_TRY(up(b->d_qoff.p, qoff, ((size_t)n_queries + 1) * 8));
-    HIP_TRY(up(b->d_pitch.p, pl.pitch.data(), (size_t)n * 4));
-    HIP_TRY(up(b->plan[0].d_off.p, pl.region_off.data(), (size_t)n * 8));
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    (void)hipEventElapsedTime(&b->ms_h2d, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    if (const int rc = frame.begin_upload()) return rc;
+    HIP_TRY(CreateFrame::upload(b->d_rows, h_rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_rows, h_pred_rows));
+    HIP_TRY(CreateFrame::upload(s->d_slot, h_slot));
+    HIP_TRY(CreateFrame::upload(s->d_pred_slot, h_pred_slot));
+    HIP_TRY(CreateFrame::upload(s->d_params, h_params));
+    HIP_TRY(CreateFrame::upload(s->d_pair_graph.p, pl.pair_graph.data(), (size_t)n * 4));
+    HIP_TRY(CreateFrame::upload(s->d_pair_query.p, pl.pair_query.data(), (size_t)n * 4));
+    HIP_TRY(CreateFrame::upload(s->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
+    for (uint32_t v = 0; v < SS_N_VARIANTS; ++v) HIP_TRY(CreateFrame::upload(s->d_class_list[v].p, pl.class_list[v].data(), (size_t)n * 4));
+    if (const int rc = frame.upload_queries(b, qseq, qoff, n_queries, nullptr, pl.pitch.data(), pl.region_off.data(), n)) return rc;
+    if (const int rc = frame.end_upload(b)) return rc;
 
     *out = s.release();
     return POA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int poa_scoreset_footprint(const poa_graph_t* const* graphs, uint32_t n_graphs, uint32_t n_queries, const uint64_t* qoff, uint64_t n_pairs,
+                           const uint32_t* pair_query, const uint32_t* pair_graph, const poa_config_t* cfg, uint64_t* bytes,
+                           uint64_t* largest_pair_bytes) {
+    if (!bytes && !largest_pair_bytes) return fail(POA_ERR_INVALID_ARG, "poa_scoreset_footprint: null argument");
+    if (const int rc = scoreset_mode_check(cfg, "poa_scoreset_footprint")) return rc;
+    return CreateFrame::guarded("poa_scoreset_footprint: host allocation failed", [&]() -> int {
+        ScoreSetPlan plan;
+        if (const int rc = scoreset_plan_of(graphs, n_graphs, n_queries, qoff, n_pairs, pair_query, pair_graph, 0, plan, "poa_scoreset_footprint")) return rc;
+        if (bytes) *bytes = plan.bytes_total;
+        if (largest_pair_bytes) *largest_pair_bytes = plan.largest_pair_bytes;
+        return POA_OK;
+    });
+}
+
+int poa_scoreset_create(const poa_graph_t* const* graphs, uint32_t n_graphs, int device, uint32_t n_queries, const uint8_t* qseq,
+                        const uint64_t* qoff, uint64_t n_pairs, const uint32_t* pair_query, const uint32_t* pair_graph,
+                        const poa_config_t* cfg, uint64_t workspace_bytes, poa_scoreset_t** out) {
+    return CreateFrame::enter("poa_scoreset_create", out, "poa_scoreset_create: host allocation failed", [&] {
+        return scoreset_create_impl(graphs, n_graphs, device, n_queries, qseq, qoff, n_pairs, pair_query, pair_graph, cfg, workspace_bytes, out);
+    });
 }
 
 int poa_scoreset_run(poa_scoreset_t* s, const poa_costs_t* costs, const poa_config_t* cfg, void* stream) {
