@@ -611,4 +611,5 @@ int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 #include "poasta_amd_scoreset_best.h"
 #include "poasta_amd_tb.h"
 #include "poasta_amd_multi_dense.h"
+#include "poasta_amd_multi_exact.h"
 #endif /* POASTA_AMD_H */

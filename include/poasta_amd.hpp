@@ -349,6 +349,68 @@ public:
         return out;
     }
 
+    // Many graphs, a few reads each, in ONE exact multi-graph run (poa_multi_*_exact, include/poasta_amd_multi_exact.h):
+    // seqs_per_graph[g] are the reads of *graphs[g]; the results come back in that order and are, read for read, what
+    // align_batch returns for the read's graph alone in the aligner's mode (Mode::Exact or Mode::Hybrid), counters included.
+    // This is the call under lock-step POA builds (poasta_align_amd align-many): one read of every graph per round, the graph
+    // updates between rounds.  One-piece configs, Global, reads of at most 1023 symbols.  Mode::Dense and the checkpointed
+    // modes, two-piece configs and ends-free spans throw: those callers keep align_batch.
+    std::vector<AstarResult> align_multi(const std::vector<const graphs::POAGraph*>& graphs, const std::vector<std::vector<std::string>>& seqs_per_graph,
+                                         bool pruning = true, poa_stats_t* stats = nullptr) const {
+        if constexpr (Config::two_piece) {
+            (void)pruning; (void)stats;
+            throw PoastaError("align_multi: the exact multi-graph batch is one-piece: a two-piece config aligns graph by graph (align_batch)");
+        } else {
+            if (mode_ != Mode::Exact && mode_ != Mode::Hybrid)
+                throw PoastaError("align_multi: the exact multi-graph batch runs in Mode::Exact or Mode::Hybrid: every other mode aligns graph by graph (align_batch)");
+            if (aln_type_.ends_free)
+                throw PoastaError("align_multi: the exact multi-graph batch is Global: an ends-free span aligns graph by graph (align_batch)");
+            if (graphs.size() != seqs_per_graph.size()) throw PoastaError("align_multi: one list of reads per graph");
+            const uint32_t ng = (uint32_t)graphs.size();
+            std::vector<const poa_graph_t*> handles(ng);
+            std::vector<uint64_t> graph_qoff(ng + 1, 0), qoff(1, 0);
+            std::string qseq;
+            uint64_t cap = 1;
+            for (uint32_t g = 0; g < ng; ++g) {
+                handles[g] = graphs[g]->device_graph();
+                for (const std::string& s : seqs_per_graph[g]) { qseq += s; qoff.push_back(qseq.size()); cap += s.size() + graphs[g]->node_count_with_start_and_end(); }
+                graph_qoff[g + 1] = qoff.size() - 1;
+            }
+            const uint32_t n = (uint32_t)qoff.size() - 1;
+            if (stats) *stats = poa_stats_t{};
+            if (n == 0) return {};
+            poa_config_t cfg{};
+            cfg.mode = (uint32_t)mode_; cfg.heuristic = Config::heuristic; cfg.pruning = pruning ? 1u : 0u;
+            cfg.queue_entries_per_cell = queue_entries_per_cell_;
+            const poa_costs_t c{config_.costs.mismatch(), config_.costs.gap_open(), config_.costs.gap_extend(), 0};
+            std::vector<uint32_t> score(n), flags(n), counters(4 * (size_t)n);
+            std::vector<uint64_t> pair_off(n + 1, 0);
+            std::vector<poa_aln_pair_t> pairs(cap);
+            // the one-shot call's sequence, with the search counters read between run and fetch
+            poa_multi_t* m = nullptr;
+            int rc = poa_multi_create_exact(handles.data(), ng, graph_qoff.data(), device_, (const uint8_t*)qseq.data(), qoff.data(), &cfg, 0, &m);
+            if (rc == POA_OK) rc = poa_multi_run_exact(m, &c, &cfg, nullptr);
+            if (rc == POA_OK) rc = poa_multi_fetch_search_counters(m, counters.data());
+            if (rc == POA_OK) rc = poa_multi_fetch(m, score.data(), pairs.data(), pair_off.data(), cap, flags.data(), stats);
+            const std::string err = rc == POA_OK ? std::string() : std::string(poa_last_error());
+            poa_multi_destroy(m);
+            if (rc != POA_OK) throw PoastaError("poa_align_multi_exact: " + err);
+            std::vector<AstarResult> out(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                out[i].score = score[i]; out[i].flags = flags[i];
+                out[i].num_queued = counters[4 * (size_t)i]; out[i].num_visited = counters[4 * (size_t)i + 1]; out[i].num_pruned = counters[4 * (size_t)i + 2];
+                for (uint64_t k = pair_off[i]; k < pair_off[i + 1]; ++k) {
+                    AlignedPair ap;
+                    if (pairs[k].rpos != POA_NONE) ap.rpos = pairs[k].rpos;
+                    if (pairs[k].qpos != POA_NONE) ap.qpos = pairs[k].qpos;
+                    out[i].alignment.push_back(ap);
+                }
+                if (flags[i] & POA_FLAG_REF_PANIC) out[i].num_pruned = 0;
+            }
+            return out;
+        }
+    }
+
     // scores only (POA_MODE_SCORE): the forward sweep over the rows still alive, no score planes, no traceback.  score = what
     // align_batch returns in Mode::Dense; alignment empty; flags limited to POA_FLAG_EMPTY_GRAPH | POA_FLAG_SHORT_QUERY.
     std::vector<AstarResult> score_batch(const graphs::POAGraph& g, const std::vector<std::string>& seqs, poa_stats_t* stats = nullptr) const {

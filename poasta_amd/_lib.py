@@ -44,6 +44,9 @@ TB_LEAN_SHIFT = 4
 # every symbol include/poasta_amd_multi_dense.h declares (checked by tests/test_multi_dense_plan.py)
 EXPORTS_MULTI_DENSE = ["poa_multi_footprint_dense", "poa_multi_create_dense", "poa_multi_run_dense", "poa_align_multi_dense",
                        "poa_graph_compact_elems", "poa_multi_last_launch"]
+# every symbol include/poasta_amd_multi_exact.h declares (checked by tests/test_multi_exact_plan.py)
+EXPORTS_MULTI_EXACT = ["poa_multi_footprint_exact", "poa_multi_create_exact", "poa_multi_run_exact", "poa_multi_fetch_search_counters",
+                       "poa_align_multi_exact"]
 
 
 class PoaBest(C.Structure):
@@ -137,7 +140,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h", "poasta_amd_multi_dense.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h", "poasta_amd_multi_dense.h", "poasta_amd_multi_exact.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -301,6 +304,18 @@ def lib():
         L.poa_graph_compact_elems.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]
         L.poa_multi_last_launch.restype = C.c_int
         L.poa_multi_last_launch.argtypes = [vp, C.c_uint32, vp]
+    if hasattr(L, "poa_multi_create_exact"):   # (as above)
+        # the exact batch kind on the same object: the argument lists of the namesakes
+        L.poa_multi_footprint_exact.restype = C.c_int
+        L.poa_multi_footprint_exact.argtypes = L.poa_multi_footprint.argtypes
+        L.poa_multi_create_exact.restype = C.c_int
+        L.poa_multi_create_exact.argtypes = L.poa_multi_create.argtypes
+        L.poa_multi_run_exact.restype = C.c_int
+        L.poa_multi_run_exact.argtypes = L.poa_multi_run.argtypes
+        L.poa_multi_fetch_search_counters.restype = C.c_int
+        L.poa_multi_fetch_search_counters.argtypes = [vp, vp]
+        L.poa_align_multi_exact.restype = C.c_int
+        L.poa_align_multi_exact.argtypes = L.poa_align_multi.argtypes
     # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)
     L.poa_scoreset_footprint.restype = C.c_int
     L.poa_scoreset_footprint.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64),

@@ -511,16 +511,22 @@ class _MultiInput:
         self.pair_capacity = int(self.qoff[-1]) + int(sum(int(c) * dg.graph.n for c, dg in zip(per_graph, self.dgs) if c > 0))
 
 
-def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False):
+def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False, exact=False):
     """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
     largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan.
     two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2").
-    dense: the dense batch (poa_multi_footprint_dense; config: None or mode "dense"): compact u16 planes per query."""
-    if dense and two_piece:
-        raise ValueError("multi_footprint: the dense multi-graph batch is one-piece")
+    dense: the dense batch (poa_multi_footprint_dense; config: None or mode "dense"): compact u16 planes per query.
+    exact: the exact batch (poa_multi_footprint_exact; config: None or mode "exact" / "hybrid"): the dense region and the u32
+    visited table per query, plus the replay workspace of every slot (queue_entries_per_cell from config)."""
+    if (dense or exact) and two_piece:
+        raise ValueError("multi_footprint: the dense and exact multi-graph batches are one-piece")
+    if dense and exact:
+        raise ValueError("multi_footprint: dense and exact are two kinds of batch")
     mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
     total, largest = C.c_uint64(0), C.c_uint64(0)
     fn = _lib.lib().poa_multi_footprint_2piece if two_piece else (_lib.lib().poa_multi_footprint_dense if dense else _lib.lib().poa_multi_footprint)
+    if exact:
+        fn = _lib.lib().poa_multi_footprint_exact
     _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff), C.byref(config) if config is not None else None,
                   C.byref(total), C.byref(largest)))
     return int(total.value), int(largest.value)
@@ -532,19 +538,27 @@ class MultiGraphBatch:
     back in query order, rpos = node index in that query's own graph.  two_piece=True: the batch of the two-piece model
     (`poa_multi_create_2piece`; its footprint differs, so the model is chosen at creation), run with GapAffine2Piece costs.
     dense=True: the dense batch (`poa_multi_create_dense`): the packed forward pass over compact u16 planes and one walk launch
-    per chunk instead of the two checkpointed passes; queries of at most 1023 symbols, one-piece costs that allow u16 cells."""
+    per chunk instead of the two checkpointed passes; queries of at most 1023 symbols, one-piece costs that allow u16 cells.
+    exact=True: the exact batch (`poa_multi_create_exact`): the dense batch with the replay of the reference's search behind it;
+    run with make_config("exact" | "hybrid", heuristic, pruning, ...): per query what align_batch returns in that mode for the
+    query's graph alone, and search_counters() the replay's counters."""
 
     def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None,
-                 two_piece=False, dense=False):
-        if dense and two_piece:
-            raise ValueError("MultiGraphBatch: the dense multi-graph batch is one-piece")
+                 two_piece=False, dense=False, exact=False):
+        if (dense or exact) and two_piece:
+            raise ValueError("MultiGraphBatch: the dense and exact multi-graph batches are one-piece")
+        if dense and exact:
+            raise ValueError("MultiGraphBatch: dense and exact are two kinds of batch")
         mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
         self.input, self.n, self.pair_capacity = mi, mi.n, mi.pair_capacity
         self.graph_qoff, self.qseq, self.qoff = mi.graph_qoff, mi.qseq, mi.qoff
         self.two_piece = bool(two_piece)
         self.dense = bool(dense)
+        self.exact = bool(exact)
         h = C.c_void_p()
         create = _lib.lib().poa_multi_create_2piece if self.two_piece else (_lib.lib().poa_multi_create_dense if self.dense else _lib.lib().poa_multi_create)
+        if self.exact:
+            create = _lib.lib().poa_multi_create_exact
         _lib.check(create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
                           C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
@@ -553,12 +567,15 @@ class MultiGraphBatch:
         """Launch on `stream` without synchronising (config: None or make_config("checkpoint", ...); for a two_piece batch
         make_config("checkpoint2", ...)).  GapAffine2Piece costs run through poa_multi_run_2piece, all others through
         poa_multi_run: costs of the other model than the batch's are refused by the library (POA_ERR_INVALID_ARG).  A dense
-        batch runs one-piece costs through poa_multi_run_dense (config: None or make_config("dense", ...))."""
+        batch runs one-piece costs through poa_multi_run_dense (config: None or make_config("dense", ...)), an exact batch
+        through poa_multi_run_exact (config: None = make_config("exact"), or make_config("hybrid", ...))."""
         c = costs._c()
         if config is None:
-            config = make_config("dense" if self.dense else ("checkpoint2" if self.two_piece else "checkpoint"))   # (carries the POA_<NAME> overrides, if any are set)
+            config = make_config("exact" if self.exact else ("dense" if self.dense else ("checkpoint2" if self.two_piece else "checkpoint")))   # (carries the POA_<NAME> overrides, if any are set)
         if isinstance(costs, GapAffine2Piece):
             run = _lib.lib().poa_multi_run_2piece
+        elif self.exact:
+            run = _lib.lib().poa_multi_run_exact
         else:
             run = _lib.lib().poa_multi_run_dense if self.dense else _lib.lib().poa_multi_run
         _lib.check(run(self.handle, C.byref(c), C.byref(config), C.c_void_p(stream or 0)))
@@ -570,11 +587,20 @@ class MultiGraphBatch:
         while True:
             v = (C.c_uint32 * 8)()
             rc = _lib.lib().poa_multi_last_launch(self.handle, len(out), v)
-            if rc == -1 and (out or (self.n == 0 and self.dense)):   # past the last chunk (a batch without queries launches nothing)
+            if rc == -1 and (out or (self.n == 0 and (self.dense or self.exact))):   # past the last chunk (a batch without queries launches nothing)
                 return out
             _lib.check(rc)
             out.append({"kernel": LAUNCH_KERNELS[v[0]], "quads": int(v[1]), "fuse": bool(v[2] & 1), "mw": bool(v[2] & 2),
                         "waves": int(v[3]), "code_fmt": int(v[4]), "tb_lanes": int(v[5]), "tb_depth": int(v[6]), "queries": int(v[7])})
+            if self.exact:   # the launch bits of an exact batch name the replay kernel instead
+                out[-1].update(fuse=False, mw=False, replay={1: "lds", 2: "generic"}[int(v[2])])
+
+    def search_counters(self):
+        """[n, 4] num_queued, num_visited, num_pruned, steps of the last run of an exact batch (poa_multi_fetch_search_counters);
+        zeros for a query that was not replayed."""
+        out = np.zeros((self.n, 4), np.uint32)
+        _lib.check(_lib.lib().poa_multi_fetch_search_counters(self.handle, _p(out)))
+        return out
 
     def fetch(self, want_pairs=True):
         n = self.n
@@ -851,20 +877,38 @@ class PoastaAligner:
             pairs = pairs[:int(pair_off[n])]
         return BatchResult(score, pairs, pair_off, flags, st.as_dict())
 
-    def align_multi(self, graphs, seqs_per_graph, want_pairs=True, mode="checkpoint"):
+    def align_multi(self, graphs, seqs_per_graph, want_pairs=True, mode="checkpoint", pruning=True):
         """Many graphs, a few reads each, in one checkpointed run (poa_align_multi): seqs_per_graph[g] are the queries of
         graphs[g].  Returns a BatchResult over all queries in that order: dense mode's score, alignment and flags of every
         query against its own graph.  Global.  A two-piece config (Affine2PieceDijkstra / Affine2PieceMinGapCost) runs
         poa_align_multi_2piece: the dense two-piece pass's results.
         mode="dense": the same results from the dense batch (poa_align_multi_dense): the packed forward pass over compact
-        planes — more workspace, queries of at most 1023 symbols, one-piece costs only (a two-piece config: ValueError)."""
+        planes — more workspace, queries of at most 1023 symbols, one-piece costs only (a two-piece config: ValueError).
+        mode="exact" | "hybrid": the replay of the reference's search behind the dense batch (poa_align_multi_exact): per query
+        what align_batch returns on a PoastaAligner of that mode for the query's graph alone; heuristic and pruning come from
+        the aligner's config as there, queue_entries_per_cell from the aligner.  One-piece, Global, at most 1023 symbols."""
         if self.aln_type != AlignmentType.Global:
             raise ValueError("align_multi: AlignmentType.Global only")
-        if mode not in ("checkpoint", "dense"):
-            raise ValueError("align_multi: mode is \"checkpoint\" or \"dense\"")
+        if mode not in ("checkpoint", "dense", "exact", "hybrid"):
+            raise ValueError("align_multi: mode is \"checkpoint\", \"dense\", \"exact\" or \"hybrid\"")
         two_piece = getattr(self.config, "two_piece", False)
-        if mode == "dense" and two_piece:
-            raise ValueError("align_multi: mode=\"dense\" is one-piece; a two-piece config runs the checkpointed batch")
+        if mode != "checkpoint" and two_piece:
+            raise ValueError("align_multi: mode=\"%s\" is one-piece; a two-piece config runs the checkpointed batch" % mode)
+        if mode in ("exact", "hybrid"):
+            mi = _MultiInput(graphs, seqs_per_graph)
+            n = mi.n
+            score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            pair_off = np.zeros(n + 1, np.uint64)
+            pairs = np.zeros((max(mi.pair_capacity, 1), 2), np.uint32) if want_pairs else None
+            st = _lib.PoaStats()
+            c = self.config.costs._c()
+            cfg = make_config(mode, self.config.heuristic, pruning, self.queue_entries_per_cell)
+            _lib.check(_lib.lib().poa_align_multi_exact(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq),
+                                                        _p(mi.qoff), _p(score), _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags),
+                                                        C.byref(st), self.device))
+            if want_pairs:
+                pairs = pairs[:int(pair_off[n])]
+            return BatchResult(score, pairs, pair_off, flags, st.as_dict())
         mi = _MultiInput(graphs, seqs_per_graph)
         n = mi.n
         score, flags = np.zeros(n, np.uint32), np.zeros(n, np.uint32)

@@ -38,6 +38,7 @@
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
 #include "poa_multi_dense.hpp"
+#include "poa_multi_exact.hpp"
 #include "poa_scoreset_plan.hpp"
 #include "poa_scoreset.hpp"
 
@@ -2508,10 +2509,22 @@ struct poa_multi {
     // FlatGraph::d_slot by row / pred_dslot by edge, one MultiDenseBlock per listed graph; core.ckpt is not set
     bool dense = false;
     DevBuf<MultiDenseBlock> d_dense;
+    // a batch of poa_multi_create_exact (poa_multi_exact.hpp): the dense batch's buffers (`dense` is NOT set: the kinds refuse each
+    // other's run calls), behind every chunk's dense regions the u32 visited tables, the ExactGraph arrays of all graphs
+    // concatenated, one MultiExactBlock per listed graph, and the slots' replay workspace in one buffer (MultiExactSlot)
+    bool exact = false;
+    DevBuf<MultiExactBlock> d_exact;
+    DevBuf<uint64_t> d_table_off;
+    DevBuf<uint8_t> d_x_sym, d_x_ws;
+    DevBuf<uint32_t> d_x_succ_off, d_x_nbm_off, d_x_succ, d_x_dist_min, d_x_dist_max, d_x_exit_idx;
+    DevBuf<FlatGraph::NodeBubble> d_x_nbm;
+    DevBuf<FlatGraph::RowRec> d_x_rec;
+    std::vector<MultiExactBlock> h_exact;   // the host's copy: LDS sizes per graph
+    MultiExactSlot x_slot;                  // what d_x_ws is laid out for
 };
 
 namespace {
-enum class MultiKind { checkpoint, checkpoint2, dense };   // what a poa_multi holds: its plan, its footprint, its run
+enum class MultiKind { checkpoint, checkpoint2, dense, Exact };   // what a poa_multi holds: its plan, its footprint, its run
 
 int multi_mode_check(const poa_config_t* cfg, const char* who, bool two_piece = false) {
     if (cfg && cfg->mode != (two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT))
@@ -2528,7 +2541,18 @@ int multi_dense_mode_check(const poa_config_t* cfg, const char* who) {
         return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": a dense multi-graph batch is Global: an ends-free result is defined by the reference's search");
     return POA_OK;
 }
+// the exact kind: POA_MODE_EXACT (NULL cfg too) or POA_MODE_HYBRID, Global, a known heuristic
+int multi_exact_mode_check(const poa_config_t* cfg, const char* who) {
+    if (cfg && cfg->mode != POA_MODE_EXACT && cfg->mode != POA_MODE_HYBRID)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": an exact multi-graph batch runs in POA_MODE_EXACT or POA_MODE_HYBRID only (every other mode of one "
+                                         "graph: poa_align_batch_ex; the dense and checkpointed batches: poa_multi_create_dense, poa_multi_create)");
+    if (cfg && cfg->span != POA_SPAN_GLOBAL)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": an exact multi-graph batch is Global: an ends-free replay runs one graph at a time (poa_align_batch_ex)");
+    if (cfg && cfg->heuristic > POA_HEURISTIC_MINGAP) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": unknown heuristic");
+    return POA_OK;
+}
 int multi_mode_check(MultiKind kind, const poa_config_t* cfg, const char* who) {
+    if (kind == MultiKind::Exact) return multi_exact_mode_check(cfg, who);
     return kind == MultiKind::dense ? multi_dense_mode_check(cfg, who) : multi_mode_check(cfg, who, kind == MultiKind::checkpoint2);
 }
 
@@ -2544,7 +2568,17 @@ int multi_plan_of(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_g
     }
     std::string err;
     int rc;
-    if (kind == MultiKind::dense) {
+    if (kind == MultiKind::Exact) {
+        // the bubble index of every listed graph, under the handle's lock as prepare_exact builds it
+        for (uint32_t g = 0; g < n_graphs; ++g) {
+            poa_graph* gr = const_cast<poa_graph*>(graphs[g]);
+            std::lock_guard<std::mutex> lk(gr->bubble_mu);
+            if (const int brc = build_bubble_index(gr->g, err)) return fail(brc, std::string(who) + ": " + err);
+        }
+        MultiExactCosts xc;   // the default costs' ring (64 priorities): a run with other costs recomputes the slot
+        xc.queue_entries_per_cell = cfg ? cfg->queue_entries_per_cell : 0.f;
+        rc = build_multi_exact_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, xc, plan, err);
+    } else if (kind == MultiKind::dense) {
         rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
     } else {
         uint32_t seg_rows = 0;
@@ -2564,7 +2598,7 @@ int multi_footprint_impl(MultiKind kind, const poa_graph_t* const* graphs, uint3
     return CreateFrame::guarded(who + ": host allocation failed", [&]() -> int {
         MultiPlan plan;
         if (const int rc = multi_plan_of(kind, graphs, n_graphs, graph_qoff, qoff, cfg, 0, plan, who_c)) return rc;
-        if (bytes) *bytes = plan.bytes_total;
+        if (bytes) *bytes = plan.bytes_total + plan.exact_bytes;   // (exact_bytes: the exact kind's slots, 0 for the others)
         if (largest_query_bytes) *largest_query_bytes = plan.largest_query_bytes;
         return POA_OK;
     });
@@ -2580,6 +2614,7 @@ int multi_create_open(CreateFrame& frame, MultiKind kind, std::unique_ptr<poa_mu
     m.reset(new (std::nothrow) poa_multi);
     if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
     m->dense = kind == MultiKind::dense;
+    m->exact = kind == MultiKind::Exact;
     MultiPlan& pl = m->plan;
     auto plan_of = [&](uint64_t ws, MultiPlan& plan) { return multi_plan_of(kind, graphs, n_graphs, graph_qoff, qoff, cfg, ws, plan, who_c); };
     // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
@@ -2588,10 +2623,11 @@ int multi_create_open(CreateFrame& frame, MultiKind kind, std::unique_ptr<poa_mu
     if (n && qoff[n] && !qseq) return fail(POA_ERR_INVALID_ARG, frame.who + ": null argument");
     if (const int rc = frame.open(device)) return rc;
     const uint64_t fixed = pl.scratch_off[n] * 16 + (uint64_t)n * 64 + qoff[n] + (64ull << 20) + pl.max_carry_words * 4 +
-                           (pl.n_rows_total + pl.n_edges_total) * 32;
+                           (pl.n_rows_total + pl.n_edges_total) * 32 +
+                           (kind == MultiKind::Exact ? pl.exact_bytes + pl.n_rows_total * 64 + (pl.n_succ_total + pl.n_nbm_total) * 16 : 0);
     if (const int rc = frame.plan_capped(pl, workspace_bytes, fixed, pl.largest_query_bytes, refusal, plan_of)) return rc;
     // the core batch: queries, results, pair buffers, events
-    frame.fill_core(&m->core, pl, m->dense ? pl.plane_bytes : pl.bytes_total, qoff);
+    frame.fill_core(&m->core, pl, (m->dense || m->exact) ? pl.plane_bytes : pl.bytes_total, qoff);
     return POA_OK;
 }
 
@@ -2702,17 +2738,21 @@ int multi_create_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const
 }
 
 // poa_multi_create_dense: one batch of compact u16 planes, one MultiDenseBlock per listed graph
+int multi_create_exact_tables(poa_multi* m, const poa_graph_t* const* graphs, uint32_t n_graphs);
+
+// (exact: the same batch with the exact kind's plan; its own tables follow the dense ones, multi_create_exact_tables)
 int multi_create_dense_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
-                            const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
-    CreateFrame frame{"poa_multi_create_dense"};
+                            const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out, bool exact = false) {
+    CreateFrame frame{exact ? "poa_multi_create_exact" : "poa_multi_create_dense"};
     std::unique_ptr<poa_multi> m;
-    if (const int rc = multi_create_open(frame, MultiKind::dense, m, graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes,
-                                         "the compact planes of the largest query do not fit in device memory"))
+    if (const int rc = multi_create_open(frame, exact ? MultiKind::Exact : MultiKind::dense, m, graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes,
+                                         exact ? "the compact planes and the visited table of the largest query do not fit in device memory"
+                                               : "the compact planes of the largest query do not fit in device memory"))
         return rc;
     const MultiPlan& pl = m->plan;
     const uint32_t n = pl.n_queries;
     poa_batch* b = &m->core;
-    b->last_mode = POA_MODE_DENSE;
+    b->last_mode = exact ? POA_MODE_EXACT : POA_MODE_DENSE;
 
     // concatenated tables, one copy per distinct handle: rows and d_slot by row, pred_rows and pred_dslot by edge
     // (a graph without a d_slot table keeps its D rows by row: its part stays zero and its blocks carry null table pointers)
@@ -2769,9 +2809,78 @@ int multi_create_dense_impl(const poa_graph_t* const* graphs, uint32_t n_graphs,
     HIP_TRY(CreateFrame::upload(m->d_dense, h_blocks));
     HIP_TRY(CreateFrame::upload(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
     if (const int rc = frame.upload_queries(b, qseq, qoff, n, pl.scratch_off.data(), pl.pitch.data(), pl.region_off.data(), n)) return rc;
+    if (exact) { if (const int rc = multi_create_exact_tables(m.get(), graphs, n_graphs)) return rc; }
     if (const int rc = frame.end_upload(b)) return rc;
 
     *out = m.release();
+    return POA_OK;
+}
+
+// what an exact batch holds beside the dense batch's buffers: the ExactGraph arrays of all graphs concatenated (graph-local
+// values, one copy per distinct handle), one MultiExactBlock per listed graph, the table offsets, the per-query replay results
+int multi_create_exact_tables(poa_multi* m, const poa_graph_t* const* graphs, uint32_t n_graphs) {
+    const MultiPlan& pl = m->plan;
+    const uint32_t n = pl.n_queries;
+    poa_batch* b = &m->core;
+    using GP = MultiGraphPlan;
+    std::vector<uint8_t> h_sym(pl.n_sym_total, 0);
+    std::vector<uint32_t> h_succ_off(pl.n_off_total), h_nbm_off(pl.n_off_total), h_succ(pl.n_succ_total), h_dmin(pl.n_rows_total),
+        h_dmax(pl.n_rows_total), h_exit(pl.n_rows_total);
+    std::vector<FlatGraph::NodeBubble> h_nbm(pl.n_nbm_total);
+    std::vector<FlatGraph::RowRec> h_rec(pl.n_rows_total);   // (a graph without records leaves its part zero and its block a null pointer)
+    std::vector<std::vector<uint8_t>> row_sym(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        if (pl.graphs[g].table_of != g) continue;
+        const FlatGraph& fg = graphs[g]->g;
+        row_sym[g].resize(fg.n);
+        for (uint32_t r = 0; r < fg.n; ++r) row_sym[g][r] = fg.rows[r].sym;
+    }
+    concat_tables(h_sym, pl.graphs, &GP::sym_base, [&](uint32_t g) -> auto& { return row_sym[g]; });
+    concat_tables(h_succ_off, pl.graphs, &GP::off_base, [&](uint32_t g) -> auto& { return graphs[g]->g.succ_row_off; });
+    concat_tables(h_nbm_off, pl.graphs, &GP::off_base, [&](uint32_t g) -> auto& { return graphs[g]->g.nbm_off; });
+    concat_tables(h_succ, pl.graphs, &GP::succ_base, [&](uint32_t g) -> auto& { return graphs[g]->g.succ_rows; });
+    concat_tables(h_dmin, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.dist_min; });
+    concat_tables(h_dmax, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.dist_max; });
+    concat_tables(h_exit, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.exit_idx; });
+    concat_tables(h_nbm, pl.graphs, &GP::nbm_base, [&](uint32_t g) -> auto& { return graphs[g]->g.nbm; });
+    concat_tables(h_rec, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.row_rec; });
+
+    HIP_TRY(CreateFrame::alloc_each(pl.n_sym_total, m->d_x_sym));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_off_total, m->d_x_succ_off, m->d_x_nbm_off));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_succ_total, m->d_x_succ));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, m->d_x_dist_min, m->d_x_dist_max, m->d_x_exit_idx, m->d_x_rec));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_nbm_total, m->d_x_nbm));
+    HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_exact));
+    HIP_TRY(CreateFrame::alloc_each(n, m->d_table_off, b->d_ex_status));
+    HIP_TRY(CreateFrame::alloc_each(2 * (uint64_t)n, b->d_ex_end));
+    HIP_TRY(CreateFrame::alloc_each(4 * (uint64_t)n, b->d_ex_counters));
+
+    m->h_exact.assign(n_graphs, MultiExactBlock());
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        MultiExactBlock& xb = m->h_exact[g];
+        std::memset(&xb, 0, sizeof(xb));
+        xb.G = ExactGraph{fg.n, fg.start_row, fg.end_row, m->d_x_sym.p + gp.sym_base, m->d_x_succ_off.p + gp.off_base, m->d_x_succ.p + gp.succ_base,
+                          m->d_x_dist_min.p + gp.row_base, m->d_x_dist_max.p + gp.row_base, m->d_x_exit_idx.p + gp.row_base, fg.n_exit,
+                          m->d_x_nbm_off.p + gp.off_base, m->d_x_nbm.p + gp.nbm_base, nullptr, nullptr,   // (node_row, sp_to_end: ends-free spans only)
+                          fg.row_rec.empty() ? nullptr : m->d_x_rec.p + gp.row_base};
+        xb.n_succ = gp.n_succ; xb.n_nbm = gp.n_nbm;
+        xb.graph_lds = exact_lds_bytes(fg.n, gp.n_succ, gp.n_nbm);
+        xb.rec_lds = fg.row_rec.empty() ? 0u : (uint32_t)((fg.row_rec.size() * sizeof(FlatGraph::RowRec) + 15) & ~15ull);
+        xb.empty = fg.n_real == 0 ? 1u : 0u;
+    }
+    HIP_TRY(CreateFrame::upload(m->d_x_sym, h_sym));
+    HIP_TRY(CreateFrame::upload(m->d_x_succ_off, h_succ_off));
+    HIP_TRY(CreateFrame::upload(m->d_x_nbm_off, h_nbm_off));
+    HIP_TRY(CreateFrame::upload(m->d_x_succ, h_succ));
+    HIP_TRY(CreateFrame::upload(m->d_x_dist_min, h_dmin));
+    HIP_TRY(CreateFrame::upload(m->d_x_dist_max, h_dmax));
+    HIP_TRY(CreateFrame::upload(m->d_x_exit_idx, h_exit));
+    HIP_TRY(CreateFrame::upload(m->d_x_nbm, h_nbm));
+    HIP_TRY(CreateFrame::upload(m->d_x_rec, h_rec));
+    HIP_TRY(CreateFrame::upload(m->d_exact, m->h_exact));
+    HIP_TRY(CreateFrame::upload(m->d_table_off.p, pl.table_off.data(), (size_t)n * 8));
     return POA_OK;
 }
 }  // namespace
@@ -2809,6 +2918,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     // (the batch's model first: whatever the mode, this entry point cannot run a two-piece batch)
     if (m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_2piece (it runs through poa_multi_run_2piece only)");
     if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
+    if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run");
     if (mrc != POA_OK) return mrc;
     const TuneView T(cfg);
@@ -2853,6 +2963,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
 int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");
     if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
+    if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
     if (!m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create (a two-piece run needs poa_multi_create_2piece: its footprint differs)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run_2piece", true);
     if (mrc != POA_OK) return mrc;
@@ -2981,6 +3092,7 @@ int poa_multi_create_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 // over all queries.  Nothing is written into the batch before every refusal has passed.
 int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: null argument");
+    if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
     if (!m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was not created by poa_multi_create_dense (a checkpointed batch runs through poa_multi_run / poa_multi_run_2piece)");
     const int mrc = multi_dense_mode_check(cfg, "poa_multi_run_dense");
     if (mrc != POA_OK) return mrc;
@@ -3028,8 +3140,8 @@ int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
 
 int poa_multi_last_launch(poa_multi_t* m, uint32_t chunk, uint32_t out[8]) {
     if (!m || !out) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: null argument");
-    if (!m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the batch was not created by poa_multi_create_dense");
-    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: poa_multi_run_dense has not been called");
+    if (!m->dense && !m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the batch was not created by poa_multi_create_dense or poa_multi_create_exact");
+    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the batch has not been run");
     if (chunk >= m->core.launches.size()) return fail(POA_ERR_INVALID_ARG, "poa_multi_last_launch: the last run had no such chunk");
     for (int k = 0; k < 8; ++k) out[k] = m->core.launches[chunk].v[k];
     return POA_OK;
@@ -3042,6 +3154,174 @@ int poa_align_multi_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, c
     if (stats) std::memset(stats, 0, sizeof(*stats));
     return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_dense(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
                           [&](poa_multi_t* m) { return poa_multi_run_dense(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
+}
+
+}  // extern "C"
+
+
+// ---- exact multi-graph batch (poa_multi_exact.hpp, build_multi_exact_plan) --------------------------------------------------
+// The dense batch above with the replay of the reference's search behind every chunk's dense pass (poa_multi::exact): per chunk
+// the dense kind's two launches unchanged, the INF-fill of the replayed queries' u32 tables, ONE replay launch (a wave per query,
+// every wave on its own graph's tables), ONE u32 walk launch over the replayed tables, then the scan and compaction.  It mirrors
+// replay_chunk for one graph.  The core's last_mode is EXACT or HYBRID, so poa_multi_fetch counts n_exact and
+// poa_batch_fetch_search_counters serves the counters.
+extern "C" {
+
+int poa_multi_footprint_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                              const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    return multi_footprint_impl(MultiKind::Exact, graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, "poa_multi_footprint_exact");
+}
+
+int poa_multi_create_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                           const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    return CreateFrame::enter("poa_multi_create_exact", out, "poa_multi_create_exact: host allocation failed",
+                              [&] { return multi_create_dense_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out, true); });
+}
+
+int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
+    const char* who = "poa_multi_run_exact";
+    if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_exact: null argument");
+    if (!m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_exact: the batch was not created by poa_multi_create_exact (a dense batch runs through poa_multi_run_dense, a checkpointed one through poa_multi_run / poa_multi_run_2piece)");
+    if (const int mrc = multi_exact_mode_check(cfg, who)) return mrc;
+    const TuneView T(cfg);
+    if (const int* iv = T.ptr(POA_TUNE_EXACT_IMPL)) {
+        if (*iv != 0 && *iv != 2)
+            return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_exact: the lane and flat replay implementations run one graph at a time (poa_align_batch_ex); a multi-graph batch runs the wave search only");
+    }
+    if (const int* gv = T.ptr(POA_TUNE_WS_GROUP)) {
+        if (*gv != 64)
+            return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_exact: several queries per wave run one graph at a time (poa_align_batch_ex); a multi-graph batch runs one query per wave");
+    }
+    const bool narrow = !planes32(T) && all_graphs_u16(m->ub_open, m->ub_extend, costs->gap_open, costs->gap_extend);
+    if (!narrow)
+        return fail(POA_ERR_UNSUPPORTED, "poa_multi_run_exact: the dense pass needs u32 cells (the costs' score bound exceeds 65534 for some graph, or "
+                                         "tune[POA_TUNE_PLANES] = 32) and an exact multi-graph batch holds u16 compact cells only; poa_align_batch_ex "
+                                         "runs either width, one graph at a time");
+    poa_batch* b = &m->core;
+    const MultiPlan& pl = m->plan;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(b->device));
+    // one slot's workspace under these costs: the maxima over the graphs that have queries (poa_multi_plan.hpp)
+    MultiExactSlot slot;
+    {
+        MultiExactCosts xc;
+        xc.x = costs->mismatch; xc.o = costs->gap_open; xc.e = costs->gap_extend;
+        xc.queue_entries_per_cell = cfg ? cfg->queue_entries_per_cell : 0.f;
+        std::string err;
+        if (const int rc = multi_exact_slot(pl, xc, slot, err)) return fail(rc, std::string(who) + ": " + err);
+    }
+    const uint64_t slots = pl.exact_slots;
+    if (b->n_queries && m->d_x_ws.n < slot.buffer_bytes(slots)) {
+        // the buffer is re-allocated: nothing of an earlier run on this batch may still be in flight (prepare_exact's rule)
+        if (b->ran) HIP_TRY(hipStreamSynchronize(b->last_stream));
+        const hipError_t e = m->d_x_ws.alloc(slot.buffer_bytes(slots));
+        if (e != hipSuccess)
+            return fail(POA_ERR_OUT_OF_MEMORY, std::string("poa_multi_run_exact: the replay workspace does not fit (create the batch with a smaller workspace_bytes: fewer "
+                                                           "queries per chunk, or lower queue_entries_per_cell): ") + hipGetErrorString(e));
+    }
+    m->x_slot = slot;
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_multi_run_exact: call poa_multi_stats/fetch at least every 256 runs")) return rc;
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
+    const uint32_t hybrid = (cfg && cfg->mode == POA_MODE_HYBRID) ? 1u : 0u;
+    b->last_mode = hybrid ? POA_MODE_HYBRID : POA_MODE_EXACT;
+    b->prof_on = false;
+    b->two_piece = false;
+    set_layout(b, true, true, false);
+    b->active_plan = 0;
+    b->launches.clear();
+    if (b->n_queries == 0) return run.end_empty(true);
+
+    int lds_cap = 64 * 1024;
+    (void)hipDeviceGetAttribute(&lds_cap, hipDeviceAttributeMaxSharedMemoryPerBlock, b->device);
+    MultiExactLaunch xl;
+    xl.graphs = m->d_exact.p;
+    xl.tables = b->d_planes.p; xl.table_off = m->d_table_off.p;
+    xl.hybrid = hybrid; xl.dense_flags = b->d_flags.p;
+    xl.qseq = b->d_qseq.p; xl.qoff = b->d_qoff.p; xl.pitch = b->d_pitch.p;
+    uint8_t* ws = m->d_x_ws.p;
+    xl.reached = reinterpret_cast<uint64_t*>(ws + slot.off_reached(slots));
+    xl.rsum = reinterpret_cast<uint64_t*>(ws + slot.off_rsum(slots));
+    xl.reached_stride = slot.reached_stride; xl.rsum_stride = slot.rsum_stride;
+    xl.wpn = slot.wpn; xl.swpn = slot.swpn;
+    xl.stack = reinterpret_cast<ExStackEntry*>(ws + slot.off_stack(slots)); xl.stack_cap = slot.stack_cap;
+    xl.chunks = reinterpret_cast<ExU4*>(ws + slot.off_pool(slots)); xl.chunk_cap = slot.pool_cap / BQ_CHUNK;
+    if (const int* cv = T.ptr(POA_TUNE_WS_CHUNK_CAP)) { const int v = (*cv); if (v >= 1 && (uint32_t)v < xl.chunk_cap) xl.chunk_cap = (uint32_t)v; }
+    xl.win = slot.win;
+    xl.max_lanes = 32; xl.adapt_lanes = 4;   // replay_wave's defaults and overrides
+    if (const int* lv = T.ptr(POA_TUNE_WS_LANES)) { const int v = (*lv); if (v >= 1 && v <= 63) xl.max_lanes = (uint32_t)v; }
+    if (const int* av = T.ptr(POA_TUNE_WS_ADAPT)) { const int v = (*av); if (v >= 0 && v <= 63) xl.adapt_lanes = (uint32_t)v; }
+    xl.C = ExactCosts{costs->mismatch, costs->gap_open, costs->gap_extend, cfg ? cfg->heuristic : POA_HEURISTIC_MINGAP, cfg ? cfg->pruning : 1u, 0, 0, 0, 0, 0, 0};
+    xl.status = b->d_ex_status.p; xl.end_cell = b->d_ex_end.p; xl.counters = b->d_ex_counters.p;
+    const uint64_t ring_b = 3ull * slot.win * 4;
+    const bool want_lds = !(T.ptr(POA_TUNE_EXACT_LDS) && *T.ptr(POA_TUNE_EXACT_LDS) == 0) && !T.ptr(POA_TUNE_WS_RING_GLOBAL);
+    const bool want_rec = !(T.ptr(POA_TUNE_WS_REC) && *T.ptr(POA_TUNE_WS_REC) == 0);
+
+    for (const auto& ch : pl.chunks) {
+        MultiDenseLaunch& ml = xl.D;
+        ml.graphs = m->d_dense.p; ml.graph_of = m->d_graph_of.p;
+        ml.first_query = ch.first; ml.n_queries = ch.count;
+        ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
+        ml.spec_depth = 32; ml.code_fmt = 0;
+        const uint32_t quads = ch.max_pitch <= 512 ? 1u : 2u;
+        const dim3 grid((ch.count + 3) / 4), block(256);
+        // 1. the dense kind's forward and walk launches
+        if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_multi_kernel<1>), grid, block, 0, stream, ml);
+        else hipLaunchKernelGGL((poa_forward_packed_multi_kernel<2>), grid, block, 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        hipLaunchKernelGGL(poa_traceback_multi_kernel, grid, block, 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        // 2. the replayed queries' tables, the chunk's statuses, counters, reached sets (and rings, where they are global)
+        HIP_TRY(hipMemsetAsync(b->d_ex_status.p + ch.first, 0xFF, (size_t)ch.count * 4, stream));
+        HIP_TRY(hipMemsetAsync(b->d_ex_counters.p + 4 * (size_t)ch.first, 0, (size_t)ch.count * 16, stream));
+        hipLaunchKernelGGL(poa_fill_tables_multi_kernel, dim3(ch.count, 16), dim3(256), 0, stream, xl);
+        HIP_TRY(hipGetLastError());
+        if (slot.reached_stride) HIP_TRY(hipMemsetAsync(xl.reached, 0, (size_t)ch.count * slot.reached_stride * 8, stream));
+        if (slot.rsum_stride) HIP_TRY(hipMemsetAsync(xl.rsum, 0, (size_t)ch.count * slot.rsum_stride * 8, stream));
+        // 3. one replay launch.  The all-in-LDS instantiation when the chunk's largest graph, its records and the ring fit the
+        // launch's LDS budget (replay_wave's: 80 KB for graph and ring, 150 KB with the records), else the generic-pointer one
+        uint64_t g_lds = 0, g_rec = 0;
+        for (uint32_t i = ch.first; i < ch.first + ch.count; ++i) {
+            const MultiExactBlock& xb = m->h_exact[pl.graph_of[i]];
+            if (xb.empty) continue;
+            g_lds = std::max<uint64_t>(g_lds, xb.graph_lds);
+            g_rec = std::max<uint64_t>(g_rec, (uint64_t)xb.graph_lds + xb.rec_lds);
+        }
+        const bool lds_all = want_lds && g_lds + ring_b <= std::min<uint64_t>((uint64_t)lds_cap, 80u * 1024u);
+        xl.stage_rec = (lds_all && want_rec && g_rec + ring_b <= std::min<uint64_t>((uint64_t)lds_cap, 150u * 1024u)) ? 1u : 0u;
+        xl.ring_global = lds_all ? nullptr : reinterpret_cast<uint32_t*>(ws + slot.off_ring(slots));
+        const uint32_t lds_bytes = lds_all ? (uint32_t)((xl.stage_rec ? g_rec : g_lds) + ring_b) : 0u;
+        const void* kfn = lds_all ? reinterpret_cast<const void*>(poa_wsearch_multi_kernel<true>) : reinterpret_cast<const void*>(poa_wsearch_multi_kernel<false>);
+        if (lds_bytes > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (lds_all) hipLaunchKernelGGL((poa_wsearch_multi_kernel<true>), dim3(ch.count), dim3(64), lds_bytes, stream, xl);
+        else hipLaunchKernelGGL((poa_wsearch_multi_kernel<false>), dim3(ch.count), dim3(64), 0, stream, xl);
+        HIP_TRY(hipGetLastError());
+        // 4. one u32 walk launch over the replayed tables
+        hipLaunchKernelGGL(poa_traceback_multi_exact_kernel, grid, block, 0, stream, xl);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        // the record of poa_multi_last_launch: the dense kind's, with the replay kernel in the launch bits (1: all in LDS, 2: generic pointers)
+        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, lds_all ? 1u : 2u, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
+    }
+    return run.end_pairs();
+}
+
+int poa_multi_fetch_search_counters(poa_multi_t* m, uint32_t* out) {
+    if (!m || !out) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch_search_counters: null argument");
+    if (!m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch_search_counters: the batch was not created by poa_multi_create_exact");
+    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_fetch_search_counters: poa_multi_run_exact has not been called");
+    return poa_batch_fetch_search_counters(&m->core, out);
+}
+
+int poa_align_multi_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs_t* costs,
+                          const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs,
+                          uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi_exact: null argument");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_exact(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
+                          [&](poa_multi_t* m) { return poa_multi_run_exact(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
 }
 
 }  // extern "C"

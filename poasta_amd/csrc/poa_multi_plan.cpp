@@ -189,4 +189,101 @@ int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
     return 0;
 }
 
+int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiExactSlot& out, std::string& err) {
+    out = MultiExactSlot();
+    const uint64_t maxc = std::max<uint64_t>(costs.x, (uint64_t)costs.o + costs.e);
+    const float f = costs.queue_entries_per_cell > 0.f ? costs.queue_entries_per_cell : 0.25f;
+    uint64_t max_len = 0, pool64 = 256, stack = 8;
+    for (size_t g = 0; g < plan.graphs.size(); ++g) {
+        const MultiGraphPlan& gp = plan.graphs[g];
+        if (!gp.n_queries) continue;
+        const uint64_t n = gp.n_rows, len = gp.max_len;
+        // the replay's own size limits, per graph (prepare_exact)
+        const uint64_t n_prio = (n + len + 2) * maxc + costs.o + (n + len) * costs.e + 64;
+        if (n_prio > (1ull << 26)) { err = "exact multi-graph batch: priority range too large for a graph / query size (poa_align_batch_ex refuses it too)"; return ERR_UNSUPPORTED; }
+        if (3ull * n * ((len + 64) & ~63ull) >= (1ull << 32)) { err = "exact multi-graph batch: the visited table of one query exceeds 2^32 cells (poa_align_batch_ex refuses it too)"; return ERR_UNSUPPORTED; }
+        if ((uint64_t)gp.n_exit * ((len + 64) / 64) >= (1ull << 32)) { err = "exact multi-graph batch: reached sets of one query exceed 2^32 words (poa_align_batch_ex refuses it too)"; return ERR_UNSUPPORTED; }
+        out.skew = std::max(out.skew, gp.skew);
+        out.n_exit = std::max(out.n_exit, gp.n_exit);
+        max_len = std::max(max_len, len);
+        stack = std::max(stack, n + len + 8);
+        pool64 = std::max<uint64_t>(pool64, (uint64_t)(f * (double)n * (double)(len + 1)));
+    }
+    out.win = multi_exact_win(costs.x, costs.o, costs.e, out.skew);
+    const uint64_t pool_ws = (pool64 + (uint64_t)64 * (3ull * out.win + 8) + 63) & ~63ull;   // BQ_CHUNK = 64 entries per chunk
+    if (pool_ws > 0xFFFFFFF0ull) { err = "exact multi-graph batch: queue pool too large (lower queue_entries_per_cell, or poa_align_batch_ex per graph)"; return ERR_UNSUPPORTED; }
+    out.pool_cap = (uint32_t)pool_ws;
+    out.stack_cap = (uint32_t)stack;
+    out.wpn = (uint32_t)((max_len + 1 + 63) / 64);
+    out.swpn = (out.wpn + 63) / 64;
+    out.reached_stride = ((uint64_t)out.n_exit * out.wpn + 1) & ~1ull;   // (an even count of 8-byte words: every slot 16-byte aligned)
+    out.rsum_stride = ((uint64_t)out.n_exit * out.swpn + 1) & ~1ull;
+    out.bytes = out.reached_stride * 8 + out.rsum_stride * 8 + (uint64_t)out.stack_cap * 12 + (uint64_t)out.pool_cap * 16 + 3ull * out.win * 4;
+    return 0;
+}
+
+int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err) {
+    // the dense plan as one chunk: the argument checks, the graphs' row and edge bases, pitches, pair scratch, the totals
+    if (const int rc = build_multi_dense_plan(graphs, n_graphs, graph_qoff, qoff, 0, out, err)) {
+        if (rc == ERR_UNSUPPORTED) err = "exact multi-graph batch: a query of more than 1023 symbols is wider than one strip of the packed forward pass; "
+                                         "poa_align_batch_ex takes queries of any length, one graph at a time";
+        return rc;
+    }
+    const uint32_t n = out.n_queries;
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const FlatGraph& fg = *graphs[g].g;
+        if (!fg.bubbles_built) { err = "exact multi-graph batch: a graph's bubble index is not built"; return ERR_INVALID_ARG; }
+        MultiGraphPlan& gp = out.graphs[g];
+        gp.n_succ = (uint32_t)fg.succ_rows.size(); gp.n_nbm = (uint32_t)fg.nbm.size(); gp.n_exit = fg.n_exit;
+        for (uint32_t r = 0; r < fg.n; ++r) gp.skew = std::max<uint32_t>(gp.skew, fg.dist_max[r] - std::min(fg.dist_min[r], fg.dist_max[r]));
+        if (gp.table_of != g) {
+            const MultiGraphPlan& first = out.graphs[gp.table_of];
+            gp.sym_base = first.sym_base; gp.off_base = first.off_base; gp.succ_base = first.succ_base; gp.nbm_base = first.nbm_base;
+        } else {
+            gp.sym_base = out.n_sym_total; gp.off_base = out.n_off_total; gp.succ_base = out.n_succ_total; gp.nbm_base = out.n_nbm_total;
+            out.n_sym_total += ((uint64_t)fg.n + 4 + 3) & ~3ull;   // the staging loop reads whole words
+            out.n_off_total += (uint64_t)fg.n + 1; out.n_succ_total += gp.n_succ; out.n_nbm_total += gp.n_nbm;
+        }
+    }
+    if (const int rc = multi_exact_slot(out, costs, out.exact, err)) return rc;
+
+    auto dense_elems = [&](uint32_t i) { return multi_dense_query_elems(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_DENSE_PAD_ELEMS; };
+    auto table_cells = [&](uint32_t i) { return multi_exact_table_cells(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_EXACT_PAD_CELLS; };
+    out.bytes_total = 0; out.largest_query_bytes = 0; out.workspace_bytes = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t bytes = dense_elems(i) * 2 + table_cells(i) * 4;
+        out.bytes_total += bytes;
+        out.largest_query_bytes = std::max(out.largest_query_bytes, bytes);
+    }
+    // chunks: greedy by the sum of both footprints; the dense regions first, the tables behind them
+    out.chunks.clear();
+    out.table_off.assign(n, 0);
+    const uint64_t budget = workspace_bytes == 0 ? out.bytes_total : std::max(workspace_bytes, out.largest_query_bytes);
+    MultiPlan::Chunk cur{0, 0, 0, 0, 0, 0};
+    auto close = [&]() {
+        // (cells is a multiple of 16 two-byte elements: every part of a compact region is, and so is the padding)
+        for (uint32_t i = cur.first; i < cur.first + cur.count; ++i) out.table_off[i] += cur.cells / 2;
+        out.chunks.push_back(cur);
+        out.workspace_bytes = std::max(out.workspace_bytes, cur.cells * 2 + cur.table_cells * 4);
+        out.exact_slots = std::max(out.exact_slots, cur.count);
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t elems = dense_elems(i), cells = table_cells(i);
+        if (cur.count && (cur.cells + elems) * 2 + (cur.table_cells + cells) * 4 > budget) {
+            close();
+            cur = MultiPlan::Chunk{i, 0, 0, 0, 0, 0};
+        }
+        out.region_off[i] = cur.cells;
+        out.table_off[i] = cur.table_cells;
+        cur.cells += elems;
+        cur.table_cells += cells;
+        cur.max_pitch = std::max(cur.max_pitch, out.pitch[i]);
+        cur.count++;
+    }
+    if (cur.count) close();
+    out.exact_bytes = n ? out.exact.buffer_bytes(out.exact_slots) : 0;
+    return 0;
+}
+
 }  // namespace poa_amd

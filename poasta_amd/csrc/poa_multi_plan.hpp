@@ -39,6 +39,25 @@
 // 2 above).  Every query is one strip: a query of more than 1023 symbols (pitch above 1024) is refused, and there are no
 // carries.  The tables a dense graph needs are rows and d_slot by row (row_base), pred_rows and pred_dslot by edge
 // (edge_base); the checkpoint fields of MultiGraphPlan stay empty.
+//
+// The exact variant (poa_multi_*_exact, poa_multi_exact.hpp; build_multi_exact_plan below) is the dense plan plus what the
+// replay of the reference's search needs (poa_wsearch.hpp):
+//   per query    a second region behind the chunk's dense regions: the u32 visited table of the search, 3 x n_rows(graph) x
+//                pitch four-byte cells + 256 bytes of padding.  table_off[q] is in FOUR-byte cells from the start of the
+//                workspace (the chunk's dense regions end at Chunk::cells two-byte elements, a multiple of 16 bytes).
+//   chunks       greedy by the sum of both footprints.
+//   per graph    the bases of its ExactGraph arrays in the concatenated tables: sym (sym_base, padded to four bytes), the two
+//                CSR offset arrays of n_rows + 1 entries (off_base), successors (succ_base), node-bubble entries (nbm_base);
+//                dist_min / dist_max / exit_idx / the row records lie at row_base.  The values stay graph-local.
+//   per slot     the replay workspace of one wave (MultiExactSlot): reached sets, their summaries, the DFA stack, the chunked
+//                queue pool and a descriptor ring for launches that keep the ring in global memory.  ONE size for every slot:
+//                the maxima over the graphs that have queries of what prepare_exact (poa_engine.hip) computes per graph.
+//                THE STRIDE RULE: ws_search_query addresses a slot's reached sets as base + slot * n_exit(graph) * wpn, and
+//                n_exit differs from graph to graph, so the slots of a multi-graph launch would overlap.  Every slot therefore
+//                owns reached_stride = max n_exit x wpn words (rsum_stride likewise), and the kernel hands the search a base
+//                biased by slot * (stride - n_exit(graph) * wpn) so that its expression lands on base + slot * stride.
+//                Slots = the largest chunk's queries.  The sizes depend on the costs (ring width, queue pool): the plan holds
+//                them for the costs it was given, and a run with other costs recomputes them (multi_exact_slot).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -65,10 +84,34 @@ struct MultiGraphPlan {
     uint64_t row_base = 0, edge_base = 0, snap_off_base = 0, snap_dst_base = 0, boundary_base = 0;
     uint64_t max_len = 0;        // longest query of this graph (0: none)
     uint32_t n_queries = 0;
+    // exact variant: bases of the graph's ExactGraph arrays (see the head of this file) and their lengths
+    uint64_t sym_base = 0, off_base = 0, succ_base = 0, nbm_base = 0;
+    uint32_t n_succ = 0, n_nbm = 0, n_exit = 0;
+    uint32_t skew = 0;           // max over rows of dist_max - dist_min (bounds the descriptor ring, prepare_exact)
 };
 
+// The replay workspace of one slot of an exact multi-graph batch, and where the five arrays of `slots` slots lie in one buffer.
+struct MultiExactSlot {
+    uint32_t n_exit = 0;          // largest over the graphs that have queries
+    uint32_t wpn = 1, swpn = 1;   // words per exit row for the longest query of the batch, and of the summary
+    uint32_t stack_cap = 0;       // DFA stack entries (12 bytes each)
+    uint32_t skew = 0;            // max over those graphs' rows of dist_max - dist_min
+    uint32_t win = 64;            // descriptor ring: priorities (power of two)
+    uint32_t pool_cap = 0;        // queue pool entries (16 bytes each), a multiple of 64: chunk_cap = pool_cap / 64
+    uint64_t reached_stride = 0, rsum_stride = 0;   // 8-byte words per slot: n_exit x wpn, n_exit x swpn
+    uint64_t bytes = 0;           // of one slot, all five arrays
+    // byte offsets of the arrays of `slots` slots in one buffer, each 16-byte aligned; the last returns the buffer's size
+    uint64_t off_reached(uint64_t) const { return 0; }
+    uint64_t off_rsum(uint64_t slots) const { return slots * reached_stride * 8; }
+    uint64_t off_stack(uint64_t slots) const { return off_rsum(slots) + slots * rsum_stride * 8; }
+    uint64_t off_pool(uint64_t slots) const { return (off_stack(slots) + slots * stack_cap * 12 + 15) & ~15ull; }
+    uint64_t off_ring(uint64_t slots) const { return off_pool(slots) + slots * pool_cap * 16; }
+    uint64_t buffer_bytes(uint64_t slots) const { return off_ring(slots) + slots * 3 * win * 4 + 16; }
+};
+struct MultiExactCosts { uint32_t x = 4, o = 6, e = 2; float queue_entries_per_cell = 0.f; };   // (0: the engine's 0.25)
+
 struct MultiPlan {
-    struct Chunk { uint32_t first, count; uint64_t cells; uint64_t carry_words; uint32_t max_pitch; };
+    struct Chunk { uint32_t first, count; uint64_t cells; uint64_t carry_words; uint32_t max_pitch; uint64_t table_cells; };   // table_cells: exact variant, four-byte cells of the chunk's visited tables
     uint32_t n_queries = 0;
     std::vector<MultiGraphPlan> graphs;
     uint64_t n_rows_total = 0, n_edges_total = 0, n_snap_off_total = 0, n_snap_dst_total = 0, n_boundary_total = 0;
@@ -82,6 +125,12 @@ struct MultiPlan {
     uint64_t max_carry_words = 0;       // the largest chunk's carries
     uint64_t total_cells = 0, total_bases = 0;
     uint64_t plane_bytes = 0;           // dense: sum of 2 x compact elems, the padding left out (poa_stats_t.plane_bytes)
+    // exact variant
+    std::vector<uint64_t> table_off;    // [n] four-byte cells from the start of the workspace
+    uint64_t n_sym_total = 0, n_off_total = 0, n_succ_total = 0, n_nbm_total = 0;
+    MultiExactSlot exact;               // one slot under the plan's costs
+    uint32_t exact_slots = 0;           // the largest chunk's queries
+    uint64_t exact_bytes = 0;           // exact.buffer_bytes(exact_slots): counted into the footprint beside bytes_total
 };
 
 // 4-byte cells a query of `len` symbols holds on a graph with that plan, padding included
@@ -107,5 +156,26 @@ inline uint64_t multi_dense_query_elems(const FlatGraph& g, uint64_t len) {
 // The dense plan: reads MultiGraphIn::g alone (sweep and own may be null).  Same return values as build_multi_plan.
 int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                            uint64_t workspace_bytes, MultiPlan& out, std::string& err);
+
+constexpr uint64_t MULTI_EXACT_PAD_CELLS = 64;      // 256 bytes behind every query's visited table, in four-byte cells
+// four-byte cells of the visited table of a query of `len` symbols on that graph, padding NOT included
+inline uint64_t multi_exact_table_cells(const FlatGraph& g, uint64_t len) { return 3ull * g.n * (((len + 1 + 63) / 64) * 64); }
+// the descriptor ring's width under those costs for a graph spread `skew` (prepare_exact's rule)
+inline uint32_t multi_exact_win(uint32_t x, uint32_t o, uint32_t e, uint32_t skew) {
+    const uint64_t maxc = x > o + e ? x : o + e;
+    const uint64_t need = maxc + o + ((uint64_t)skew + 3) * e + 8;
+    uint32_t win = 64;
+    while (win < need && win < (1u << 24)) win *= 2;
+    return win;
+}
+
+// One slot's sizes under `costs`, from what an exact plan holds of its graphs (rows, exits, spread, longest query).  The
+// replay's own size limits are checked per graph as prepare_exact checks them.  Returns 0 or -7 with `err` set.
+int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiExactSlot& out, std::string& err);
+
+// The exact plan: build_multi_dense_plan plus the table regions, the chunks by both footprints, the ExactGraph table bases and
+// the slot workspace under `costs`.  Reads MultiGraphIn::g alone; every listed graph's bubble index must be built.
+int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err);
 
 }  // namespace poa_amd

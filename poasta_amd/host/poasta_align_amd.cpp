@@ -8,7 +8,15 @@
 //
 //   poasta_align_amd align [-n MISMATCH] [-g OPEN[,OPEN2]] [-e EXTEND[,EXTEND2]] [-H mingap|dijkstra] [-m global|semi-global|ends-free] [-I graph.msa.fa] [-o OUT] [--mode dense|exact|hybrid]
 //                          [--device N] [--alignments FILE] READS.fa
+//   poasta_align_amd align-many [the align options but -I, -o, --alignments] [--timing FILE] LIST.tsv
 //   poasta_align_amd replay ALIGNMENTS.txt          (no GPU: graph update + export from recorded alignments)
+//
+// align-many builds many graphs in lock step.  LIST.tsv holds one line per build, READS.fa<TAB>OUT.fa[<TAB>SEED.msa.fa].  Round r
+// takes read r of every build that still has one: a build whose graph is empty seeds it, as `align` does; every other build
+// contributes one (graph, read) to a single PoastaAligner::align_multi call (the exact multi-graph batch: one replay launch for
+// the reads of all graphs) and then gets its add_alignment_with_weights.  Builds drop out as their reads run out.  Every output
+// is what `align` writes for that file alone.  A read that comes back with EXACT_OVERFLOW or REF_PANIC stops its own build with
+// the message `align` prints; the other builds go on and the exit status is 2.  One-piece costs, Global, --mode exact | hybrid.
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -78,8 +86,10 @@ static int replay(const std::string& path) {
 int main(int argc, char** argv) {
     try {
         if (argc >= 3 && std::strcmp(argv[1], "replay") == 0) return replay(argv[2]);
-        if (argc < 3 || std::strcmp(argv[1], "align") != 0) {
+        const bool many = argc >= 3 && std::strcmp(argv[1], "align-many") == 0;
+        if (argc < 3 || (std::strcmp(argv[1], "align") != 0 && !many)) {
             std::fprintf(stderr, "usage: poasta_align_amd align [-n 4] [-g 6 | 6,24] [-e 2 | 2,1] [-H mingap|dijkstra] [-m global|semi-global|ends-free] [-I graph.msa.fa] [-o out.fa] [--mode dense|exact|hybrid] [--queue-entries-per-cell F] [--device 0] [--alignments file] [--timing file.tsv] reads.fa\n"
+                                 "       poasta_align_amd align-many [-n -g -e -H -m --mode --queue-entries-per-cell --device as above] [--timing file.tsv] list.tsv   (lines: reads.fa<TAB>out.fa[<TAB>seed.msa.fa])\n"
                                  "       poasta_align_amd replay alignments.txt\n");
             return 2;
         }
@@ -105,7 +115,9 @@ int main(int argc, char** argv) {
             else if (a == "--timing") timing_path = need("--timing");
             else pos.push_back(a);
         }
-        if (pos.size() != 1) throw PoastaError("expected one FASTA of reads");
+        if (pos.size() != 1) throw PoastaError(many ? "expected one list of builds" : "expected one FASTA of reads");
+        if (many && (!out_path.empty() || !msa_path.empty() || !aln_path.empty()))
+            throw PoastaError("align-many: -o, -I and --alignments belong to a build: name them in the list (reads.fa<TAB>out.fa[<TAB>seed.msa.fa])");
         const aligner::Mode m = mode == "dense" ? aligner::Mode::Dense : (mode == "exact" ? aligner::Mode::Exact : aligner::Mode::Hybrid);
         const bool mode_dense = mode == "dense";
         bool warned_dense = false;
@@ -144,6 +156,83 @@ int main(int argc, char** argv) {
             if (two_piece) return dij ? al2_d.align_batch(gr, {seq}, true, st).at(0) : al2_m.align_batch(gr, {seq}, true, st).at(0);
             return dij ? al_d.align_batch(gr, {seq}, true, st).at(0) : al_m.align_batch(gr, {seq}, true, st).at(0);
         };
+        if (many) {
+            // refused before anything is read: the PoastaError of align_multi for a mode, a cost model or a span it does not take
+            if (two_piece) (void)al2_m.align_multi({}, {});
+            (void)al_m.align_multi({}, {});
+            struct Build { std::vector<std::pair<std::string, std::string>> reads; std::string out; graphs::POAGraph graph; size_t next = 0; bool failed = false; };
+            std::vector<Build> builds;
+            {
+                std::ifstream lf(pos[0]);
+                if (!lf) throw PoastaError("could not open " + pos[0]);
+                std::string line;
+                while (std::getline(lf, line)) {
+                    if (!line.empty() && line.back() == '\r') line.pop_back();
+                    if (line.empty()) continue;
+                    const size_t t1 = line.find('\t');
+                    if (t1 == std::string::npos) throw PoastaError("align-many: a line of the list is READS.fa<TAB>OUT.fa[<TAB>SEED.msa.fa]");
+                    const size_t t2 = line.find('\t', t1 + 1);
+                    builds.emplace_back();
+                    Build& b = builds.back();
+                    b.reads = read_fasta(line.substr(0, t1));
+                    b.out = line.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
+                    if (t2 != std::string::npos && t2 + 1 < line.size()) b.graph = io::load_graph_from_fasta_msa(read_fasta(line.substr(t2 + 1)));
+                }
+            }
+            std::ofstream tlog;
+            if (!timing_path.empty()) { tlog.open(timing_path); tlog << "round\tgraphs\tus_graph_refresh\tus_align_call\tus_graph_update\tus_h2d\tus_dense_kernels\tus_replay\tus_d2h\tn_replayed\n"; }
+            using clk = std::chrono::steady_clock;
+            auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+            int status = 0;
+            for (size_t round = 0;; ++round) {
+                std::vector<Build*> act;
+                bool any = false;
+                for (Build& b : builds) {
+                    if (b.failed || b.next >= b.reads.size()) continue;
+                    any = true;
+                    if (b.graph.is_empty()) {   // poasta.rs:209-211
+                        const auto& rec = b.reads[b.next++];
+                        b.graph.add_alignment_with_weights(rec.first, rec.second, nullptr, std::vector<size_t>(rec.second.size(), 1));
+                    } else act.push_back(&b);
+                }
+                if (!any) break;
+                if (act.empty()) continue;
+                const auto t0 = clk::now();
+                std::vector<const graphs::POAGraph*> gs;
+                std::vector<std::vector<std::string>> seqs;
+                for (Build* b : act) { (void)b->graph.device_graph(); gs.push_back(&b->graph); seqs.push_back({b->reads[b->next].second}); }
+                const auto t1 = clk::now();
+                poa_stats_t st{};
+                const std::vector<aligner::AstarResult> rs = dij ? al_d.align_multi(gs, seqs, true, &st) : al_m.align_multi(gs, seqs, true, &st);
+                const auto t2 = clk::now();
+                for (size_t k = 0; k < act.size(); ++k) {
+                    Build& b = *act[k];
+                    const auto& rec = b.reads[b.next++];
+                    const aligner::AstarResult& r = rs[k];
+                    std::fprintf(stderr, "Aligned '%s' (len=%zu) - Score: %u, Alignment length: %zu, flags 0x%x\n", rec.first.c_str(), rec.second.size(), r.score,
+                                 r.alignment.size(), r.flags);
+                    if (r.flags & (POA_FLAG_EXACT_OVERFLOW | POA_FLAG_REF_PANIC)) {   // this build stops, as `align` does; the others go on
+                        std::fprintf(stderr, "poasta_align_amd: read '%s': %s — not adding it to the graph\n", rec.first.c_str(),
+                                     (r.flags & POA_FLAG_REF_PANIC) ? "the reference would panic on this input (u32 score wrap)"
+                                                                    : "the replay ran out of workspace (raise --queue-entries-per-cell)");
+                        b.failed = true;
+                        status = 2;
+                        continue;
+                    }
+                    b.graph.add_alignment_with_weights(rec.first, rec.second, &r.alignment, std::vector<size_t>(rec.second.size(), 1));
+                }
+                const auto t3 = clk::now();
+                if (tlog) tlog << round << '\t' << act.size() << '\t' << us(t0, t1) << '\t' << us(t1, t2) << '\t' << us(t2, t3) << '\t' << st.ms_h2d * 1e3 << '\t'
+                               << (st.ms_forward + st.ms_traceback) * 1e3 << '\t' << st.ms_exact * 1e3 << '\t' << st.ms_d2h * 1e3 << '\t' << st.n_exact << '\n';
+            }
+            for (const Build& b : builds) {
+                if (b.failed) continue;
+                std::ofstream o(b.out);
+                if (!o) throw PoastaError("could not write " + b.out);
+                o << io::poa_graph_to_fasta(b.graph);
+            }
+            return status;
+        }
         std::ofstream alog, tlog;
         if (!timing_path.empty()) { tlog.open(timing_path); tlog << "read\tlen\tgraph_nodes\tus_graph_refresh\tus_align_call\tus_h2d\tus_dense_kernels\tus_replay\tus_d2h\tus_graph_update\n"; }
         if (!aln_path.empty()) alog.open(aln_path);

@@ -18,6 +18,12 @@ POA_MODE_CHECKPOINT2, (c) the loop of the dense poa_align_batch_2piece.  Writes 
 --dense: the one-piece paths above and, in the same process on the same workload, the dense multi-graph batch: (d) poa_multi_run_dense
 + poa_multi_fetch on a resident batch of poa_multi_create_dense, (d1) the one-shot poa_align_multi_dense.  Writes
 profiles/pr_multi_dense/timing.json, with both footprints.
+
+--exact: the exact multi-graph batch in POA_MODE_HYBRID on the same graphs, in two shapes in one process: one read per graph (the
+shape of a round of lock-step POA builds) and --reads reads per graph.  Per shape (e) poa_multi_run_exact + poa_multi_fetch on a
+resident batch of poa_multi_create_exact, (e1) the one-shot poa_align_multi_exact, (f) the loop over the graphs of the one-shot
+poa_align_batch_ex in POA_MODE_HYBRID; how many reads were replayed; the results of the three compared.  Writes
+profiles/pr_multi_exact/timing.json.
 """
 import argparse
 import ctypes as C
@@ -40,8 +46,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--two-piece", action="store_true", help="the two-piece model, costs 4 / 6,24 / 2,1 (poa_multi_*_2piece)")
     ap.add_argument("--dense", action="store_true", help="add the dense multi-graph batch (poa_multi_*_dense) to the one-piece paths")
+    ap.add_argument("--exact", action="store_true", help="the exact multi-graph batch in hybrid mode against the per-graph hybrid loop, 1 and --reads reads per graph")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.exact:
+        if args.two_piece or args.dense:
+            ap.error("--exact stands alone")
+        return exact_main(args)
     two = args.two_piece
     if two and args.dense:
         ap.error("--dense is one-piece")
@@ -171,6 +182,99 @@ def main():
         json.dump(out, f, indent=1)
         f.write("\n")
     return 0 if out["results_equal"] else 1
+
+
+def exact_main(args):
+    import numpy as np
+    from poasta_amd import _lib, aligner, workloads as W
+
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pr_multi_exact", "timing.json")
+    costs = aligner.GapAffine(4, 2, 6)
+    c = costs._c()
+    L = _lib.lib()
+    al = aligner.PoastaAligner(aligner.AffineMinGapCost(costs), mode="hybrid")
+
+    def med(v):
+        v = sorted(v)
+        return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+    out = {"costs": "4 / 6 / 2 (mismatch / open / extend)", "mode": "hybrid, min-gap heuristic, pruning", "graphs": args.graphs, "steps": args.steps,
+           "warmup": args.warmup, "shapes": {}}
+    ok = True
+    for reads in sorted({1, args.reads}):
+        graphs, packed, seqs = [], [], []
+        for k in range(args.graphs):
+            g, (qseq, qoff) = W.scaled_linearish(190, 10, 5, reads, args.length, graph_seed=100 + k, query_seed=5000 + k)
+            graphs.append(g)
+            packed.append((qseq, qoff))
+            seqs.append([qseq[int(qoff[i]):int(qoff[i + 1])] for i in range(reads)])
+        dgs = [aligner._device_graph(g) for g in graphs]
+        cfg = aligner.make_config("hybrid")
+        mb = aligner.MultiGraphBatch(graphs, seqs, exact=True, config=cfg)
+        last = {}
+
+        def step_resident():
+            mb.run(costs, config=cfg)
+            r = mb.fetch()
+            last.update(r.stats)
+            return r, r.stats
+
+        def step_one_shot():
+            r = al.align_multi(graphs, seqs, mode="hybrid")
+            return r, r.stats
+
+        def step_loop():
+            score, flags, pairs, counts = [], [], [], []
+            tot = {"ms_forward": 0.0, "ms_traceback": 0.0, "ms_exact": 0.0, "n_exact": 0}
+            for dg, (qseq, qoff) in zip(dgs, packed):
+                n = len(qoff) - 1
+                cap = int(qoff[-1]) + n * dg.graph.n
+                s, f, po = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n + 1, np.uint64)
+                pr = np.zeros((cap, 2), np.uint32)
+                st = _lib.PoaStats()
+                _lib.check(L.poa_align_batch_ex(dg.handle, C.byref(c), C.byref(cfg), n, aligner._p(qseq), aligner._p(qoff), aligner._p(s),
+                                                aligner._p(pr), aligner._p(po), cap, aligner._p(f), C.byref(st), 0))
+                for k in tot:
+                    tot[k] += getattr(st, k)
+                score.append(s); flags.append(f); pairs.append(pr[:int(po[n])]); counts.append(np.diff(po.astype(np.int64)))
+            off = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.uint64)
+            return aligner.BatchResult(np.concatenate(score), np.concatenate(pairs), off, np.concatenate(flags), {}), tot
+
+        paths = {"exact_run_fetch": step_resident, "exact_one_shot": step_one_shot, "loop_hybrid_one_shot": step_loop}
+        rows = {k: [] for k in paths}
+        sums = {}
+        for rep in range(args.warmup + args.steps):
+            for name, step in paths.items():
+                t0 = time.perf_counter()
+                res, st = step()
+                wall = (time.perf_counter() - t0) * 1e3
+                if rep >= args.warmup:
+                    rows[name].append((wall, st["ms_forward"] + st["ms_traceback"], st["ms_exact"]))
+                sums[name] = {"score_sum": int(res.score.astype(np.uint64).sum()), "flags_crc32": zlib.crc32(res.flags.tobytes()),
+                              "n_pairs": int(res.pair_off[-1]), "pairs_crc32": zlib.crc32(np.ascontiguousarray(res.pairs).tobytes()),
+                              "n_replayed": int(st["n_exact"])}
+                del res
+        shape = {"workload": "%d graphs x %d reads of %d bp, LinearishPOA backbone 190" % (args.graphs, reads, args.length), "queries": args.graphs * reads,
+                 "rows_per_graph": {"min": min(g.n for g in graphs), "max": max(g.n for g in graphs)},
+                 "results_equal": all(sums[k] == sums["loop_hybrid_one_shot"] for k in sums),
+                 "footprint_bytes": aligner.multi_footprint(graphs, seqs, exact=True, config=cfg)[0], "plane_workspace_bytes": mb.workspace_bytes(),
+                 "launches": mb.launches(), "run_stats": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in last.items()}}
+        for name in paths:
+            shape[name] = {"ms_step": med([r[0] for r in rows[name]]), "ms_dense_kernels": med([r[1] for r in rows[name]]),
+                           "ms_replay_kernels": med([r[2] for r in rows[name]])}
+            shape[name].update(sums[name])
+        for name in ("exact_run_fetch", "exact_one_shot"):
+            shape["ms_step_ratio_%s_over_loop" % name] = round(shape[name]["ms_step"]["median"] / shape["loop_hybrid_one_shot"]["ms_step"]["median"], 4)
+        ok = ok and shape["results_equal"]
+        out["shapes"]["%d_reads_per_graph" % reads] = shape
+        mb.close()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
