@@ -176,6 +176,10 @@ typedef struct poa_config {
 } poa_config_t;
 #define POA_CFG_FULL_PLANES 1u /* keep all three score planes in memory (needed by poa_batch_fetch_planes); the default
                                   u16 layout stores M, a 4-bit code per cell instead of I, and only the D rows read back */
+#define POA_CFG_WIDE_QUERIES 2u /* a dense or exact multi-graph batch takes queries of more than 1023 symbols: the forward pass
+                                  walks such a query strip by strip (poasta_amd_multi_dense.h).  Read by poa_multi_footprint_dense /
+                                  _create_dense / poa_align_multi_dense and their _exact namesakes, by no other entry point
+                                  (POA_CFG_BEST_PAIR_ORDER shares the value: the score-set calls that read it never read this one) */
 
 /* AlignedPair (alignment.rs:4-13): rpos = node index of the host graph, qpos = 0-based query position */
 typedef struct poa_aln_pair {
@@ -420,6 +424,7 @@ enum {
 };
 #define POA_LAUNCH_FUSE 1u   /* the forward kernel walked the traceback of its queries in its epilogue */
 #define POA_LAUNCH_MW 2u     /* one workgroup per query, its strips pipelined over the waves */
+#define POA_LAUNCH_STRIPS 4u /* poa_multi_last_launch only: the chunk ran the strip loop of a POA_CFG_WIDE_QUERIES batch */
 int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
 /* the paired banded pass of the last dense run (two queries of one length per wave, one per 16-bit half of every register):
  * out[0] = queries that ran paired, out[1] = queries of banded chunks that ran one per wave, out[2] = the default rule's

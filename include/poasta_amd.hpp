@@ -353,7 +353,8 @@ public:
     // seqs_per_graph[g] are the reads of *graphs[g]; the results come back in that order and are, read for read, what
     // align_batch returns for the read's graph alone in the aligner's mode (Mode::Exact or Mode::Hybrid), counters included.
     // This is the call under lock-step POA builds (poasta_align_amd align-many): one read of every graph per round, the graph
-    // updates between rounds.  One-piece configs, Global, reads of at most 1023 symbols.  Mode::Dense and the checkpointed
+    // updates between rounds.  One-piece configs, Global.  A read of more than 1023 symbols sets POA_CFG_WIDE_QUERIES on the
+    // batch (its dense pass then walks such a read strip by strip); shorter reads leave it clear.  Mode::Dense and the checkpointed
     // modes, two-piece configs and ends-free spans throw: those callers keep align_batch.
     std::vector<AstarResult> align_multi(const std::vector<const graphs::POAGraph*>& graphs, const std::vector<std::vector<std::string>>& seqs_per_graph,
                                          bool pruning = true, poa_stats_t* stats = nullptr) const {
@@ -371,9 +372,13 @@ public:
             std::vector<uint64_t> graph_qoff(ng + 1, 0), qoff(1, 0);
             std::string qseq;
             uint64_t cap = 1;
+            bool wide = false;   // a read wider than one strip of the packed forward pass
             for (uint32_t g = 0; g < ng; ++g) {
                 handles[g] = graphs[g]->device_graph();
-                for (const std::string& s : seqs_per_graph[g]) { qseq += s; qoff.push_back(qseq.size()); cap += s.size() + graphs[g]->node_count_with_start_and_end(); }
+                for (const std::string& s : seqs_per_graph[g]) {
+                    qseq += s; qoff.push_back(qseq.size()); cap += s.size() + graphs[g]->node_count_with_start_and_end();
+                    wide = wide || s.size() > 1023;
+                }
                 graph_qoff[g + 1] = qoff.size() - 1;
             }
             const uint32_t n = (uint32_t)qoff.size() - 1;
@@ -382,6 +387,7 @@ public:
             poa_config_t cfg{};
             cfg.mode = (uint32_t)mode_; cfg.heuristic = Config::heuristic; cfg.pruning = pruning ? 1u : 0u;
             cfg.queue_entries_per_cell = queue_entries_per_cell_;
+            if (wide) cfg.flags |= POA_CFG_WIDE_QUERIES;
             const poa_costs_t c{config_.costs.mismatch(), config_.costs.gap_open(), config_.costs.gap_extend(), 0};
             std::vector<uint32_t> score(n), flags(n), counters(4 * (size_t)n);
             std::vector<uint64_t> pair_off(n + 1, 0);

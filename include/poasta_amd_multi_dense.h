@@ -32,6 +32,15 @@ extern "C" {
  * POA_ERR_INVALID_ARG: the argument errors of poa_multi_create; poa_multi_run / poa_multi_run_2piece on a dense batch and
  * poa_multi_run_dense on a checkpointed one; a fetch before a run.  poa_multi_create, poa_multi_run and poa_align_multi keep
  * refusing POA_MODE_DENSE.
+ *
+ * POA_CFG_WIDE_QUERIES in cfg->flags of the footprint, create and one-shot calls lifts the 1023-symbol limit (any length up to
+ * 0x7FFFFFF0 symbols).  The flag belongs to the batch: poa_multi_run_dense needs nothing in its cfg.  The footprint rule is
+ * unchanged.  A chunk whose widest query has at most 1024 columns launches exactly what it launches without the flag; a chunk
+ * with a wider query launches poa_forward_packed_multi_wide_kernel once for all its queries: one wavefront per query walks the
+ * query's strips of 1024 columns in sequence and hands 2 x rows(graph) four-byte words per such query from strip to strip
+ * (the insertion-scan carry and I of the strip's last column); queries of one strip in that chunk take no carry words.  The
+ * carries of one chunk must stay below 2^32 words (POA_ERR_UNSUPPORTED otherwise: cap workspace_bytes).  Results are those of
+ * poa_align_batch_ex in POA_MODE_DENSE bit for bit, as for every other query.  Without the flag nothing changes.
  * poa_multi_run_dense launches on `stream` without synchronising, allocates nothing and may be called again with other costs.
  * poa_stats_t: cells = sum rows(graph_i) x (len_i + 1), plane_bytes = sum 2 x poa_graph_compact_elems, n_chunks, ms_forward
  * and ms_traceback as for every resident run. */
@@ -51,7 +60,8 @@ int poa_align_multi_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, c
 int poa_graph_compact_elems(const poa_graph_t* g, uint32_t len, uint64_t* elems);
 /* what chunk `chunk` of the last poa_multi_run_dense launched, in the record format of poa_batch_last_launch:
  * POA_KERNEL_PACKED, quads (1 or 2), 0, 4 waves per workgroup, code_fmt 0, 64 lanes per walk, depth 32, queries of the chunk.
- * POA_ERR_INVALID_ARG on a checkpointed batch, before a run, and past the last chunk.  Host side only. */
+ * A chunk that ran the strip loop (POA_CFG_WIDE_QUERIES, a query wider than 1024 columns) reports quads 2 and POA_LAUNCH_STRIPS
+ * in out[2].  POA_ERR_INVALID_ARG on a checkpointed batch, before a run, and past the last chunk.  Host side only. */
 int poa_multi_last_launch(poa_multi_t* m, uint32_t chunk, uint32_t out[8]);
 
 #ifdef __cplusplus

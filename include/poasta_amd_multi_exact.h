@@ -41,7 +41,9 @@ extern "C" {
  * the slot at the run that uses them.  Host only, no device needed.
  *
  * POA_ERR_UNSUPPORTED, each naming the single-graph call that takes the case: a mode other than EXACT / HYBRID,
- * POA_SPAN_ENDS_FREE, a query of more than 1023 symbols, the replay's own size limits checked per graph (priority range, visited
+ * POA_SPAN_ENDS_FREE, a query of more than 1023 symbols unless cfg->flags has POA_CFG_WIDE_QUERIES (read by the footprint,
+ * create and one-shot calls as poasta_amd_multi_dense.h describes; the dense pass then walks such a query strip by strip, the
+ * replay and the u32 walk are sized by the plan as before), the replay's own size limits checked per graph (priority range, visited
  * table, reached sets, queue pool); at poa_multi_run_exact costs under which some graph needs u32 dense cells or
  * tune[POA_TUNE_PLANES] = 32, tune[POA_TUNE_EXACT_IMPL] other than 0 / 2 (wave) and tune[POA_TUNE_WS_GROUP] other than 64.  The
  * two-piece model has no such batch.  POA_TUNE_EXACT_LDS = 0 and POA_TUNE_WS_RING_GLOBAL force the generic-pointer replay kernel;
@@ -51,7 +53,7 @@ extern "C" {
  * poa_multi_run_exact launches on `stream` without synchronising; it allocates only when the costs need a larger slot than any
  * run before (it then waits for the previous run).  It may be called again with other costs and with the other mode.
  * poa_multi_last_launch serves the batch: the dense kind's record with the replay kernel in out[2] (1: graph, records and ring
- * in LDS; 2: generic pointers). */
+ * in LDS; 2: generic pointers) in its low two bits, POA_LAUNCH_STRIPS on top for a chunk that ran the strip loop. */
 int poa_multi_footprint_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
                               const uint64_t* qoff, const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes);
 int poa_multi_create_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device,

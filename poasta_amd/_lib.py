@@ -120,6 +120,8 @@ MODE_DENSE, MODE_EXACT, MODE_HYBRID, MODE_SCORE, MODE_CHECKPOINT, MODE_CHECKPOIN
 HEURISTIC_DIJKSTRA, HEURISTIC_MINGAP = 0, 1
 FLAG_EXACT_OVERFLOW = 0x40
 CFG_FULL_PLANES = 1
+CFG_WIDE_QUERIES = 2    # POA_CFG_WIDE_QUERIES: dense and exact multi-graph batches with queries of more than 1023 symbols
+LAUNCH_STRIPS = 4       # POA_LAUNCH_STRIPS in out[2] of poa_multi_last_launch
 
 
 class PoaStats(C.Structure):

@@ -158,15 +158,17 @@ MODES = {"dense": _lib.MODE_DENSE, "exact": _lib.MODE_EXACT, "hybrid": _lib.MODE
 
 
 def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, queue_entries_per_cell=0.0, full_planes=False,
-                aln_type=AlignmentType.Global, **tune):
+                aln_type=AlignmentType.Global, wide_queries=False, **tune):
     """poa_config_t: `mode` "dense" | "exact" (replay the reference's A* for every query: bit-identical
     tie-breaks) | "hybrid" (replay only the queries the dense pass could not certify) | "score" (forward sweep only: dense
     mode's scores, no alignment, memory for the live rows only) | "checkpoint" (dense mode's results from a slot-sized
     workspace: sweep with snapshots, then recompute-and-walk per segment; ckpt_rows=k overrides the segment length) |
     "checkpoint2" (the same for the two-piece model: the dense two-piece pass's results, two-piece entry points only);
-    `aln_type` Global or EndsFree(...)."""
+    `aln_type` Global or EndsFree(...).  `wide_queries`: POA_CFG_WIDE_QUERIES, read when a dense or exact multi-graph batch is
+    sized or created (queries of more than 1023 symbols); multi_footprint and MultiGraphBatch set it themselves where needed."""
     cfg = _lib.PoaConfig(MODES[mode] if isinstance(mode, str) else int(mode), int(heuristic), 1 if pruning else 0,
-                         float(queue_entries_per_cell), _lib.CFG_FULL_PLANES if full_planes else 0)
+                         float(queue_entries_per_cell),
+                         (_lib.CFG_FULL_PLANES if full_planes else 0) | (_lib.CFG_WIDE_QUERIES if wide_queries else 0))
     if isinstance(aln_type, EndsFree):
         cfg.span = _lib.SPAN_ENDS_FREE
         for name, (kind, value) in zip(("qry_free_begin", "qry_free_end", "graph_free_begin", "graph_free_end"), aln_type.bounds):
@@ -511,18 +513,43 @@ class _MultiInput:
         self.pair_capacity = int(self.qoff[-1]) + int(sum(int(c) * dg.graph.n for c, dg in zip(per_graph, self.dgs) if c > 0))
 
 
-def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False, exact=False):
+MULTI_ONE_STRIP_MAX_LEN = 1023   # longest query of a dense or exact multi-graph batch without POA_CFG_WIDE_QUERIES
+
+
+def _multi_wide_config(who, mi, config, dense, exact, wide):
+    """(config, flag) for the footprint / create call of a multi-graph batch.  wide None: POA_CFG_WIDE_QUERIES is set iff the
+    kind is dense or exact and a query is longer than 1023 symbols; True / False force it.  The caller's config is not modified:
+    where the flag has to change, a copy carries it (mode "exact" / "dense" when there is no config, as the library reads NULL)."""
+    if not (dense or exact):
+        if wide:
+            raise ValueError(who + ": wide=True is for the dense and exact kinds; a checkpointed batch takes queries of any length")
+        return config, False
+    if wide is None:
+        wide = mi.n > 0 and int(np.diff(mi.qoff.astype(np.int64)).max()) > MULTI_ONE_STRIP_MAX_LEN
+    has = config is not None and bool(config.flags & _lib.CFG_WIDE_QUERIES)
+    if bool(wide) != has:
+        src = config if config is not None else make_config("exact" if exact else "dense")
+        config = type(src).from_buffer_copy(src)
+        config.flags = (config.flags | _lib.CFG_WIDE_QUERIES) if wide else (config.flags & ~_lib.CFG_WIDE_QUERIES)
+    return config, bool(wide)
+
+
+def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False, exact=False,
+                    wide=None):
     """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
     largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan.
     two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2").
     dense: the dense batch (poa_multi_footprint_dense; config: None or mode "dense"): compact u16 planes per query.
     exact: the exact batch (poa_multi_footprint_exact; config: None or mode "exact" / "hybrid"): the dense region and the u32
-    visited table per query, plus the replay workspace of every slot (queue_entries_per_cell from config)."""
+    visited table per query, plus the replay workspace of every slot (queue_entries_per_cell from config).
+    wide: POA_CFG_WIDE_QUERIES for the dense and exact kinds (None: set iff a query is longer than 1023 symbols; True / False
+    force it; True with a checkpointed kind is a ValueError: that kind takes any length already)."""
     if (dense or exact) and two_piece:
         raise ValueError("multi_footprint: the dense and exact multi-graph batches are one-piece")
     if dense and exact:
         raise ValueError("multi_footprint: dense and exact are two kinds of batch")
     mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
+    config, _ = _multi_wide_config("multi_footprint", mi, config, dense, exact, wide)
     total, largest = C.c_uint64(0), C.c_uint64(0)
     fn = _lib.lib().poa_multi_footprint_2piece if two_piece else (_lib.lib().poa_multi_footprint_dense if dense else _lib.lib().poa_multi_footprint)
     if exact:
@@ -538,13 +565,15 @@ class MultiGraphBatch:
     back in query order, rpos = node index in that query's own graph.  two_piece=True: the batch of the two-piece model
     (`poa_multi_create_2piece`; its footprint differs, so the model is chosen at creation), run with GapAffine2Piece costs.
     dense=True: the dense batch (`poa_multi_create_dense`): the packed forward pass over compact u16 planes and one walk launch
-    per chunk instead of the two checkpointed passes; queries of at most 1023 symbols, one-piece costs that allow u16 cells.
+    per chunk instead of the two checkpointed passes; one-piece costs that allow u16 cells.  Queries of more than 1023 symbols
+    need POA_CFG_WIDE_QUERIES at creation (`wide`: None sets it iff such a query is there, True / False force it; `self.wide`
+    says what the batch was created with): a chunk with such a query runs the strip loop, every other chunk what it always ran.
     exact=True: the exact batch (`poa_multi_create_exact`): the dense batch with the replay of the reference's search behind it;
     run with make_config("exact" | "hybrid", heuristic, pruning, ...): per query what align_batch returns in that mode for the
     query's graph alone, and search_counters() the replay's counters."""
 
     def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None,
-                 two_piece=False, dense=False, exact=False):
+                 two_piece=False, dense=False, exact=False, wide=None):
         if (dense or exact) and two_piece:
             raise ValueError("MultiGraphBatch: the dense and exact multi-graph batches are one-piece")
         if dense and exact:
@@ -555,6 +584,7 @@ class MultiGraphBatch:
         self.two_piece = bool(two_piece)
         self.dense = bool(dense)
         self.exact = bool(exact)
+        config, self.wide = _multi_wide_config("MultiGraphBatch", mi, config, self.dense, self.exact, wide)
         h = C.c_void_p()
         create = _lib.lib().poa_multi_create_2piece if self.two_piece else (_lib.lib().poa_multi_create_dense if self.dense else _lib.lib().poa_multi_create)
         if self.exact:
@@ -582,7 +612,9 @@ class MultiGraphBatch:
 
     def launches(self):
         """What the last run of a dense batch launched, one dict per chunk (poa_multi_last_launch), in the form of
-        ResidentBatch.launches: "kernel" is "packed", "quads" 1 or 2, "tb_lanes" 64, "tb_depth" 32, "queries" the chunk's."""
+        ResidentBatch.launches: "kernel" is "packed", "quads" 1 or 2, "tb_lanes" 64, "tb_depth" 32, "queries" the chunk's.
+        A chunk that ran the strip loop (POA_LAUNCH_STRIPS: a query of more than 1023 symbols) has "strips": True, no other
+        chunk has the key."""
         out = []
         while True:
             v = (C.c_uint32 * 8)()
@@ -592,8 +624,10 @@ class MultiGraphBatch:
             _lib.check(rc)
             out.append({"kernel": LAUNCH_KERNELS[v[0]], "quads": int(v[1]), "fuse": bool(v[2] & 1), "mw": bool(v[2] & 2),
                         "waves": int(v[3]), "code_fmt": int(v[4]), "tb_lanes": int(v[5]), "tb_depth": int(v[6]), "queries": int(v[7])})
-            if self.exact:   # the launch bits of an exact batch name the replay kernel instead
-                out[-1].update(fuse=False, mw=False, replay={1: "lds", 2: "generic"}[int(v[2])])
+            if self.exact:   # the low launch bits of an exact batch name the replay kernel instead
+                out[-1].update(fuse=False, mw=False, replay={1: "lds", 2: "generic"}[int(v[2]) & 3])
+            if v[2] & _lib.LAUNCH_STRIPS:
+                out[-1]["strips"] = True
 
     def search_counters(self):
         """[n, 4] num_queued, num_visited, num_pruned, steps of the last run of an exact batch (poa_multi_fetch_search_counters);
@@ -883,10 +917,11 @@ class PoastaAligner:
         query against its own graph.  Global.  A two-piece config (Affine2PieceDijkstra / Affine2PieceMinGapCost) runs
         poa_align_multi_2piece: the dense two-piece pass's results.
         mode="dense": the same results from the dense batch (poa_align_multi_dense): the packed forward pass over compact
-        planes — more workspace, queries of at most 1023 symbols, one-piece costs only (a two-piece config: ValueError).
+        planes — more workspace, one-piece costs only (a two-piece config: ValueError).  Reads of more than 1023 symbols set
+        POA_CFG_WIDE_QUERIES by themselves: their chunks run the forward pass strip by strip.
         mode="exact" | "hybrid": the replay of the reference's search behind the dense batch (poa_align_multi_exact): per query
         what align_batch returns on a PoastaAligner of that mode for the query's graph alone; heuristic and pruning come from
-        the aligner's config as there, queue_entries_per_cell from the aligner.  One-piece, Global, at most 1023 symbols."""
+        the aligner's config as there, queue_entries_per_cell from the aligner.  One-piece, Global; long reads as under "dense"."""
         if self.aln_type != AlignmentType.Global:
             raise ValueError("align_multi: AlignmentType.Global only")
         if mode not in ("checkpoint", "dense", "exact", "hybrid"):
@@ -903,6 +938,7 @@ class PoastaAligner:
             st = _lib.PoaStats()
             c = self.config.costs._c()
             cfg = make_config(mode, self.config.heuristic, pruning, self.queue_entries_per_cell)
+            cfg, _ = _multi_wide_config("align_multi", mi, cfg, False, True, None)
             _lib.check(_lib.lib().poa_align_multi_exact(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq),
                                                         _p(mi.qoff), _p(score), _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags),
                                                         C.byref(st), self.device))
@@ -917,6 +953,7 @@ class PoastaAligner:
         st = _lib.PoaStats()
         c = self.config.costs._c()
         cfg = make_config("dense" if mode == "dense" else ("checkpoint2" if two_piece else "checkpoint"), self.config.heuristic)
+        cfg, _ = _multi_wide_config("align_multi", mi, cfg, mode == "dense", False, None)
         fn = _lib.lib().poa_align_multi_2piece if two_piece else (_lib.lib().poa_align_multi_dense if mode == "dense" else _lib.lib().poa_align_multi)
         _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq), _p(mi.qoff), _p(score),
                       _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags), C.byref(st), self.device))

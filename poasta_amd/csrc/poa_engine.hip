@@ -2568,6 +2568,7 @@ int multi_plan_of(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_g
     }
     std::string err;
     int rc;
+    const bool wide = cfg && (cfg->flags & POA_CFG_WIDE_QUERIES);   // read by the dense and exact kinds alone
     if (kind == MultiKind::Exact) {
         // the bubble index of every listed graph, under the handle's lock as prepare_exact builds it
         for (uint32_t g = 0; g < n_graphs; ++g) {
@@ -2577,9 +2578,9 @@ int multi_plan_of(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_g
         }
         MultiExactCosts xc;   // the default costs' ring (64 priorities): a run with other costs recomputes the slot
         xc.queue_entries_per_cell = cfg ? cfg->queue_entries_per_cell : 0.f;
-        rc = build_multi_exact_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, xc, plan, err);
+        rc = build_multi_exact_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, xc, plan, err, wide);
     } else if (kind == MultiKind::dense) {
-        rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
+        rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err, wide);
     } else {
         uint32_t seg_rows = 0;
         { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
@@ -2768,10 +2769,12 @@ int multi_create_dense_impl(const poa_graph_t* const* graphs, uint32_t n_graphs,
 
     HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, b->d_rows, m->d_slot));
     HIP_TRY(CreateFrame::alloc_each(pl.n_edges_total, b->d_pred_rows, m->d_pred_slot));
-    HIP_TRY(CreateFrame::alloc_each(n, m->d_graph_of));
+    HIP_TRY(CreateFrame::alloc_each(n, m->d_graph_of, m->d_carry_off));
     HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_dense));
     if (const int rc = frame.alloc_results(b, qoff[n], n, n, true, pl.scratch_off[n])) return rc;
-    HIP_TRY(CreateFrame::alloc_each(1, b->d_carry));   // FwdParams::strip_carry: a valid address that one-strip queries never touch
+    // the largest chunk's strip carries (POA_CFG_WIDE_QUERIES: 2 x rows words per query wider than one strip); at least one word,
+    // FwdParams::strip_carry is a valid address that one-strip queries never touch
+    HIP_TRY(CreateFrame::alloc_each(std::max<uint64_t>(1, pl.max_carry_words), b->d_carry));
     if (const int rc = frame.acquire_planes(b, pl.workspace_bytes, true, "dense multi-graph workspace")) return rc;
 
     // one block per listed graph: what poa_batch_run_ex puts into FwdParams / TbParams for that graph alone, absolute encoding
@@ -2808,6 +2811,7 @@ int multi_create_dense_impl(const poa_graph_t* const* graphs, uint32_t n_graphs,
     HIP_TRY(CreateFrame::upload(m->d_pred_slot, h_pred_dslot));
     HIP_TRY(CreateFrame::upload(m->d_dense, h_blocks));
     HIP_TRY(CreateFrame::upload(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    HIP_TRY(CreateFrame::upload(m->d_carry_off.p, pl.carry_off.data(), (size_t)n * 4));
     if (const int rc = frame.upload_queries(b, qseq, qoff, n, pl.scratch_off.data(), pl.pitch.data(), pl.region_off.data(), n)) return rc;
     if (exact) { if (const int rc = multi_create_exact_tables(m.get(), graphs, n_graphs)) return rc; }
     if (const int rc = frame.end_upload(b)) return rc;
@@ -3068,6 +3072,21 @@ int poa_align_multi_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 // The core is a dense poa_batch (ckpt not set), so poa_multi_fetch / _stats / _device_results / _workspace_bytes / _destroy
 // serve it unchanged and poa_stats_t.plane_bytes is the planes' own size.  Its mode check, plan and constructor stand with the
 // other two kinds' above (MultiKind::dense, multi_create_dense_impl).
+namespace {
+// The forward launch of one chunk of a dense or exact batch.  A chunk whose widest query is one strip launches the one-strip
+// kernel by its quads, in a batch created with POA_CFG_WIDE_QUERIES too; a chunk with a wider query (only such a batch has one)
+// launches the strip loop once for all its queries.  Returns the launch bits of the chunk's record.
+uint32_t multi_dense_forward(const MultiDenseLaunch& ml, uint32_t max_pitch, dim3 grid, dim3 block, hipStream_t stream) {
+    if (max_pitch > MULTI_STRIP_COLUMNS) {
+        hipLaunchKernelGGL(poa_forward_packed_multi_wide_kernel, grid, block, 0, stream, ml);
+        return POA_LAUNCH_STRIPS;
+    }
+    if (max_pitch <= 512) hipLaunchKernelGGL((poa_forward_packed_multi_kernel<1>), grid, block, 0, stream, ml);
+    else hipLaunchKernelGGL((poa_forward_packed_multi_kernel<2>), grid, block, 0, stream, ml);
+    return 0u;
+}
+}  // namespace
+
 extern "C" {
 
 int poa_graph_compact_elems(const poa_graph_t* g, uint32_t len, uint64_t* elems) {
@@ -3123,17 +3142,17 @@ int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
         ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
         ml.spec_depth = 32;   // what plan_dense_chunk pairs with 64 lanes per walk on the compact layout
         ml.code_fmt = 0;
-        const uint32_t quads = ch.max_pitch <= 512 ? 1u : 2u;   // 512 columns per quad; the plan holds every pitch to 1024
+        ml.carry = b->d_carry.p; ml.carry_off = m->d_carry_off.p;
+        const uint32_t quads = ch.max_pitch <= 512 ? 1u : 2u;   // 512 columns per quad
         const dim3 grid((ch.count + 3) / 4), block(256);
-        if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_multi_kernel<1>), grid, block, 0, stream, ml);
-        else hipLaunchKernelGGL((poa_forward_packed_multi_kernel<2>), grid, block, 0, stream, ml);
+        const uint32_t strips = multi_dense_forward(ml, ch.max_pitch, grid, block, stream);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
         hipLaunchKernelGGL(poa_traceback_multi_kernel, grid, block, 0, stream, ml);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark(2)) return rc;
         // the record of poa_batch_last_launch: kernel, quads, launch bits, waves per workgroup, code_fmt, lanes per walk, depth, queries
-        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, 0u, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
+        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, strips, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
     }
     return run.end_pairs();
 }
@@ -3263,11 +3282,11 @@ int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
         ml.first_query = ch.first; ml.n_queries = ch.count;
         ml.cost_x = costs->mismatch; ml.cost_o = costs->gap_open; ml.cost_e = costs->gap_extend;
         ml.spec_depth = 32; ml.code_fmt = 0;
+        ml.carry = b->d_carry.p; ml.carry_off = m->d_carry_off.p;
         const uint32_t quads = ch.max_pitch <= 512 ? 1u : 2u;
         const dim3 grid((ch.count + 3) / 4), block(256);
         // 1. the dense kind's forward and walk launches
-        if (quads == 1) hipLaunchKernelGGL((poa_forward_packed_multi_kernel<1>), grid, block, 0, stream, ml);
-        else hipLaunchKernelGGL((poa_forward_packed_multi_kernel<2>), grid, block, 0, stream, ml);
+        const uint32_t strips = multi_dense_forward(ml, ch.max_pitch, grid, block, stream);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
         hipLaunchKernelGGL(poa_traceback_multi_kernel, grid, block, 0, stream, ml);
@@ -3302,8 +3321,9 @@ int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
         hipLaunchKernelGGL(poa_traceback_multi_exact_kernel, grid, block, 0, stream, xl);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
-        // the record of poa_multi_last_launch: the dense kind's, with the replay kernel in the launch bits (1: all in LDS, 2: generic pointers)
-        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, lds_all ? 1u : 2u, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
+        // the record of poa_multi_last_launch: the dense kind's, with the replay kernel in the low two launch bits (1: all in LDS,
+        // 2: generic pointers) and POA_LAUNCH_STRIPS on top
+        b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, (lds_all ? 1u : 2u) | strips, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
     }
     return run.end_pairs();
 }

@@ -104,8 +104,15 @@ int build_multi_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64
     return 0;
 }
 
-int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                           uint64_t workspace_bytes, MultiPlan& out, std::string& err) {
+namespace {
+// strip carries of a wide dense or exact query: two words per row (forward_packed_strips: the insertion-scan carry and I of the
+// strip's last column), for a query wider than one strip only.  The checkpointed kinds' rule with the packed kernel's words.
+inline uint64_t dense_carry_words(uint32_t pitch, uint32_t n_rows) { return pitch > MULTI_STRIP_COLUMNS ? 2ull * n_rows : 0ull; }
+const char* const DENSE_CARRY_OVERFLOW = "multi-graph batch: the strip carries of one chunk exceed 2^32 words; cap workspace_bytes";
+
+// build_multi_dense_plan; `carries` false: the chunks' carries are left to the caller (the exact plan cuts its own chunks)
+int dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+               uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide, bool carries) {
     out = MultiPlan();
     if (!graph_qoff || !qoff || (n_graphs && !graphs)) { err = "dense multi-graph batch: null argument"; return ERR_INVALID_ARG; }
     if (graph_qoff[0] != 0) { err = "dense multi-graph batch: graph_qoff[0] is not 0"; return ERR_INVALID_ARG; }
@@ -117,7 +124,8 @@ int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
     const uint32_t n = (uint32_t)graph_qoff[n_graphs];
     for (uint32_t i = 0; i < n; ++i) {
         if (qoff[i + 1] < qoff[i]) { err = "dense multi-graph batch: qoff not monotone"; return ERR_INVALID_ARG; }
-        if (qoff[i + 1] - qoff[i] > MULTI_DENSE_MAX_LEN) {
+        if (wide && qoff[i + 1] - qoff[i] > 0x7FFFFFF0ull) { err = "query longer than 2^31"; return ERR_UNSUPPORTED; }
+        if (!wide && qoff[i + 1] - qoff[i] > MULTI_DENSE_MAX_LEN) {
             err = "dense multi-graph batch: a query of more than 1023 symbols is wider than one strip of the packed forward pass; "
                   "the checkpointed batch (poa_multi_create) takes queries of any length";
             return ERR_UNSUPPORTED;
@@ -167,12 +175,13 @@ int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
     }
     out.scratch_off[n] = scratch;
 
-    // chunks: the greedy rule of build_multi_plan; the region offsets restart with every chunk
+    // chunks: the greedy rule of build_multi_plan; the region and carry offsets restart with every chunk
     const uint64_t budget = workspace_bytes == 0 ? out.bytes_total : std::max(workspace_bytes, out.largest_query_bytes);
     MultiPlan::Chunk cur{0, 0, 0, 0, 0};
     auto close = [&]() {
         out.chunks.push_back(cur);
         out.workspace_bytes = std::max(out.workspace_bytes, cur.cells * 2);
+        out.max_carry_words = std::max(out.max_carry_words, cur.carry_words);
     };
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t elems = elems_of(i);
@@ -182,11 +191,21 @@ int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
         }
         out.region_off[i] = cur.cells;
         cur.cells += elems;
+        const uint64_t cw = carries ? dense_carry_words(out.pitch[i], out.graphs[out.graph_of[i]].n_rows) : 0ull;   // (0 without `wide`: every pitch <= 1024)
+        if (cur.carry_words + cw > 0xFFFFFFFFull) { err = std::string("dense ") + DENSE_CARRY_OVERFLOW; return ERR_UNSUPPORTED; }
+        out.carry_off[i] = (uint32_t)cur.carry_words;
+        cur.carry_words += cw;
         cur.max_pitch = std::max(cur.max_pitch, out.pitch[i]);
         cur.count++;
     }
     if (cur.count) close();
     return 0;
+}
+}  // namespace
+
+int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                           uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide) {
+    return dense_plan(graphs, n_graphs, graph_qoff, qoff, workspace_bytes, out, err, wide, true);
 }
 
 int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiExactSlot& out, std::string& err) {
@@ -223,10 +242,11 @@ int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiE
 }
 
 int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err) {
+                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err, bool wide) {
     // the dense plan as one chunk: the argument checks, the graphs' row and edge bases, pitches, pair scratch, the totals
-    if (const int rc = build_multi_dense_plan(graphs, n_graphs, graph_qoff, qoff, 0, out, err)) {
-        if (rc == ERR_UNSUPPORTED) err = "exact multi-graph batch: a query of more than 1023 symbols is wider than one strip of the packed forward pass; "
+    // (the carries belong to the chunks cut below)
+    if (const int rc = dense_plan(graphs, n_graphs, graph_qoff, qoff, 0, out, err, wide, false)) {
+        if (rc == ERR_UNSUPPORTED && !wide) err = "exact multi-graph batch: a query of more than 1023 symbols is wider than one strip of the packed forward pass; "
                                          "poa_align_batch_ex takes queries of any length, one graph at a time";
         return rc;
     }
@@ -250,7 +270,7 @@ int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
 
     auto dense_elems = [&](uint32_t i) { return multi_dense_query_elems(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_DENSE_PAD_ELEMS; };
     auto table_cells = [&](uint32_t i) { return multi_exact_table_cells(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_EXACT_PAD_CELLS; };
-    out.bytes_total = 0; out.largest_query_bytes = 0; out.workspace_bytes = 0;
+    out.bytes_total = 0; out.largest_query_bytes = 0; out.workspace_bytes = 0; out.max_carry_words = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t bytes = dense_elems(i) * 2 + table_cells(i) * 4;
         out.bytes_total += bytes;
@@ -266,6 +286,7 @@ int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
         for (uint32_t i = cur.first; i < cur.first + cur.count; ++i) out.table_off[i] += cur.cells / 2;
         out.chunks.push_back(cur);
         out.workspace_bytes = std::max(out.workspace_bytes, cur.cells * 2 + cur.table_cells * 4);
+        out.max_carry_words = std::max(out.max_carry_words, cur.carry_words);
         out.exact_slots = std::max(out.exact_slots, cur.count);
     };
     for (uint32_t i = 0; i < n; ++i) {
@@ -278,6 +299,10 @@ int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
         out.table_off[i] = cur.table_cells;
         cur.cells += elems;
         cur.table_cells += cells;
+        const uint64_t cw = dense_carry_words(out.pitch[i], out.graphs[out.graph_of[i]].n_rows);
+        if (cur.carry_words + cw > 0xFFFFFFFFull) { err = std::string("exact ") + DENSE_CARRY_OVERFLOW; return ERR_UNSUPPORTED; }
+        out.carry_off[i] = (uint32_t)cur.carry_words;
+        cur.carry_words += cw;
         cur.max_pitch = std::max(cur.max_pitch, out.pitch[i]);
         cur.count++;
     }

@@ -36,8 +36,12 @@
 // elements (poa_graph.hpp: the M plane, a quarter plane of flag codes, the kept D rows; a graph without a d_slot table keeps
 // all n_rows of them) + 256 bytes of padding.  region_off and Chunk::cells are then in TWO-byte elements, relative to the
 // query's chunk; chunks are cut by the same greedy rule; Chunk::max_pitch chooses the kernel's quads (1 up to 512 columns,
-// 2 above).  Every query is one strip: a query of more than 1023 symbols (pitch above 1024) is refused, and there are no
-// carries.  The tables a dense graph needs are rows and d_slot by row (row_base), pred_rows and pred_dslot by edge
+// 2 above).  Without `wide` every query is one strip: a query of more than 1023 symbols (pitch above 1024) is refused, and there
+// are no carries.  With `wide` (POA_CFG_WIDE_QUERIES) any length passes and the carry rule above holds with the packed kernel's
+// words: a query of pitch > MULTI_STRIP_COLUMNS takes 2 x n_rows(graph) words at carry_off[q], relative to its chunk
+// (forward_packed_strips: carry[2r] the insertion-scan carry, carry[2r + 1] I of the strip's last column; one parity, the wave
+// reads a row's words before it overwrites them), every other query 0; Chunk::carry_words and max_carry_words as in
+// build_multi_plan.  The exact variant cuts its own chunks and lays the carries out by them.  The tables a dense graph needs are rows and d_slot by row (row_base), pred_rows and pred_dslot by edge
 // (edge_base); the checkpoint fields of MultiGraphPlan stay empty.
 //
 // The exact variant (poa_multi_*_exact, poa_multi_exact.hpp; build_multi_exact_plan below) is the dense plan plus what the
@@ -155,7 +159,7 @@ inline uint64_t multi_dense_query_elems(const FlatGraph& g, uint64_t len) {
 
 // The dense plan: reads MultiGraphIn::g alone (sweep and own may be null).  Same return values as build_multi_plan.
 int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                           uint64_t workspace_bytes, MultiPlan& out, std::string& err);
+                           uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide = false);
 
 constexpr uint64_t MULTI_EXACT_PAD_CELLS = 64;      // 256 bytes behind every query's visited table, in four-byte cells
 // four-byte cells of the visited table of a query of `len` symbols on that graph, padding NOT included
@@ -176,6 +180,6 @@ int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiE
 // The exact plan: build_multi_dense_plan plus the table regions, the chunks by both footprints, the ExactGraph table bases and
 // the slot workspace under `costs`.  Reads MultiGraphIn::g alone; every listed graph's bubble index must be built.
 int build_multi_exact_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err);
+                           uint64_t workspace_bytes, const MultiExactCosts& costs, MultiPlan& out, std::string& err, bool wide = false);
 
 }  // namespace poa_amd

@@ -17,6 +17,7 @@
 // the reads of all graphs) and then gets its add_alignment_with_weights.  Builds drop out as their reads run out.  Every output
 // is what `align` writes for that file alone.  A read that comes back with EXACT_OVERFLOW or REF_PANIC stops its own build with
 // the message `align` prints; the other builds go on and the exit status is 2.  One-piece costs, Global, --mode exact | hybrid.
+// Reads of any length: a round with a read of more than 1023 symbols runs on a batch created with POA_CFG_WIDE_QUERIES.
 #include <chrono>
 #include <cstdio>
 #include <cstring>
