@@ -47,7 +47,10 @@ extern "C" {
 #define POA_FLAG_SHORT_QUERY 0x08u  /* len <= 1: reference special cases (gap_affine.rs:808-824) */
 #define POA_FLAG_TRUNCATED 0x10u    /* backtrace ended before the start node (as the reference's would) */
 #define POA_FLAG_EMPTY_GRAPH 0x20u  /* no real nodes: PoastaAligner::align shortcut (mod.rs:124-142), score 4*len */
-#define POA_FLAG_EXACT_OVERFLOW 0x40u /* exact replay ran out of workspace: the dense result (and its flags) was kept */
+#define POA_FLAG_EXACT_OVERFLOW 0x40u /* exact replay ran out of workspace: the dense result (and its flags) was kept.  For a POA_SPAN_ENDS_FREE
+                                       * run that result is the GLOBAL alignment of the dense pass, not an answer to the span asked for: treat the
+                                       * query as not aligned and run it again with a larger queue_entries_per_cell.  The descriptor ring is sized
+                                       * to hold every priority that is live at once (a free graph begin included), so only the queue pool sets it. */
 #define POA_FLAG_CAPPED 0x80u       /* capped score-set run: the score is above the pair's cap and was not returned */
 
 /* modes (poa_config_t.mode) */
@@ -426,6 +429,26 @@ enum {
 #define POA_LAUNCH_MW 2u     /* one workgroup per query, its strips pipelined over the waves */
 #define POA_LAUNCH_STRIPS 4u /* poa_multi_last_launch only: the chunk ran the strip loop of a POA_CFG_WIDE_QUERIES batch */
 int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
+/* what the exact replay launched for chunk `chunk` of the last run (POA_MODE_EXACT, POA_MODE_HYBRID, every ends-free run):
+ *   out[0] replay kernel, POA_REPLAY_*        out[1] priorities in the descriptor ring (`win`; the lane kernel has no ring)
+ *   out[2] lanes per query                    out[3] waves per block
+ *   out[4] POA_REPLAY_BIT_* bits              out[5] resident blocks as the launcher computed them (0: it did not ask)
+ *   out[6] blocks launched                    out[7] dynamic LDS bytes of the launch
+ * POA_ERR_INVALID_ARG: no run yet, or no such chunk; POA_ERR_UNSUPPORTED: the last run replayed nothing.  Host side only. */
+enum {
+    POA_REPLAY_NONE = 0,
+    POA_REPLAY_LANE,          /* poa_exact_kernel: one sequential search per lane */
+    POA_REPLAY_WAVE_LDS,      /* poa_wsearch_kernel: a wave per query, graph and ring in LDS */
+    POA_REPLAY_WAVE_GROUPS,   /* poa_wsearch_groups_kernel: several queries per wave */
+    POA_REPLAY_WAVE_GENERIC,  /* poa_wsearch_global_kernel: a wave per query, graph or ring read through generic pointers */
+    POA_REPLAY_FLAT_GENERIC,  /* poa_fsearch_kernel: the parallel step over the generic code */
+    POA_REPLAY_FLAT_LEAN      /* poa_fsearch_lean_kernel: the parallel step's lean code (Global runs with row records) */
+};
+#define POA_REPLAY_BIT_GRAPH_LDS 1u    /* the graph arrays (flat lean: the row records it reads) were staged into LDS */
+#define POA_REPLAY_BIT_REC_LDS 2u      /* the per-row records were staged into LDS */
+#define POA_REPLAY_BIT_RING_GLOBAL 4u  /* the descriptor ring lay in global memory */
+#define POA_REPLAY_BIT_PERSISTENT 8u   /* persistent schedule: `resident` blocks took the queries from a work counter */
+int poa_batch_replay_info(poa_batch_t* b, uint32_t chunk, uint32_t out[8]);
 /* the paired banded pass of the last dense run (two queries of one length per wave, one per 16-bit half of every register):
  * out[0] = queries that ran paired, out[1] = queries of banded chunks that ran one per wave, out[2] = the default rule's
  * count (a chunk pairs from that many queries in pairs on; POA_TUNE_BAND_PAIR overrides), out[3] = 1 if the run paired.

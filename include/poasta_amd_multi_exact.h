@@ -63,6 +63,10 @@ int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
 /* out[4 * n_queries]: num_queued, num_visited, num_pruned, steps of every query of the last run, in the format of
  * poa_batch_fetch_search_counters; zeros for a query that was not replayed.  Waits for the run. */
 int poa_multi_fetch_search_counters(poa_multi_t* m, uint32_t* out);
+/* what the replay launched for chunk `chunk` of the last poa_multi_run_exact, in the record format of poa_batch_replay_info
+ * (poasta_amd.h): POA_REPLAY_WAVE_LDS or POA_REPLAY_WAVE_GENERIC, the slot's `win`, 64 lanes per query, one wave per block, the
+ * POA_REPLAY_BIT_* bits, 0, the chunk's queries as blocks, the dynamic LDS bytes.  Host side only. */
+int poa_multi_replay_info(poa_multi_t* m, uint32_t chunk, uint32_t out[8]);
 /* one-shot: create, run, fetch, destroy */
 int poa_align_multi_exact(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff,
                           const poa_costs_t* costs, const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff,

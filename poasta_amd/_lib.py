@@ -22,7 +22,7 @@ FLAG_CAPPED = 0x80
 EXPORTS = ["poa_version", "poa_last_error", "poa_device_count", "poa_graph_create", "poa_graph_destroy",
            "poa_graph_rows", "poa_graph_node_rows", "poa_graph_update", "poa_align_batch", "poa_align_batch_ex", "poa_align_batch_2piece", "poa_align_batch_2piece_ex", "poa_planes_2piece", "poa_release_cache", "poa_batch_create", "poa_batch_run",
            "poa_batch_run_ex",
-           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_band_pair_info", "poa_batch_band_narrow_info", "poa_batch_last_launch", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
+           "poa_batch_fetch", "poa_batch_stats", "poa_batch_device_results", "poa_batch_fetch_search_counters", "poa_batch_last_layout", "poa_batch_band_info", "poa_batch_band_pair_info", "poa_batch_band_narrow_info", "poa_batch_last_launch", "poa_batch_replay_info", "poa_batch_fetch_planes", "poa_batch_fetch_compact", "poa_batch_destroy",
            "poa_batch_run_2piece", "poa_batch_fetch_planes_2piece",
            "poa_graph_sweep_slots", "poa_batch_create_ex", "poa_batch_workspace_bytes", "poa_graph_checkpoint_plan", "poa_graph_checkpoint_plan2",
            "poa_multi_footprint", "poa_multi_create", "poa_multi_run", "poa_multi_fetch", "poa_multi_stats", "poa_multi_device_results",
@@ -46,7 +46,7 @@ EXPORTS_MULTI_DENSE = ["poa_multi_footprint_dense", "poa_multi_create_dense", "p
                        "poa_graph_compact_elems", "poa_multi_last_launch"]
 # every symbol include/poasta_amd_multi_exact.h declares (checked by tests/test_multi_exact_plan.py)
 EXPORTS_MULTI_EXACT = ["poa_multi_footprint_exact", "poa_multi_create_exact", "poa_multi_run_exact", "poa_multi_fetch_search_counters",
-                       "poa_align_multi_exact"]
+                       "poa_align_multi_exact", "poa_multi_replay_info"]
 
 
 class PoaBest(C.Structure):
@@ -249,6 +249,9 @@ def lib():
     if hasattr(L, "poa_batch_last_launch"):
         L.poa_batch_last_launch.restype = C.c_int
         L.poa_batch_last_launch.argtypes = [vp, C.c_uint32, vp]
+    if hasattr(L, "poa_batch_replay_info"):   # (POA_LIB_PATH may name the build of an older tree: A/B runs)
+        L.poa_batch_replay_info.restype = C.c_int
+        L.poa_batch_replay_info.argtypes = [vp, C.c_uint32, vp]
     L.poa_batch_device_results.restype = C.c_int
     L.poa_batch_device_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.poa_batch_fetch_planes.restype = C.c_int
@@ -316,6 +319,9 @@ def lib():
         L.poa_multi_run_exact.argtypes = L.poa_multi_run.argtypes
         L.poa_multi_fetch_search_counters.restype = C.c_int
         L.poa_multi_fetch_search_counters.argtypes = [vp, vp]
+        if hasattr(L, "poa_multi_replay_info"):
+            L.poa_multi_replay_info.restype = C.c_int
+            L.poa_multi_replay_info.argtypes = [vp, C.c_uint32, vp]
         L.poa_align_multi_exact.restype = C.c_int
         L.poa_align_multi_exact.argtypes = L.poa_align_multi.argtypes
     # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)

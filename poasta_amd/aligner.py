@@ -178,6 +178,21 @@ def make_config(mode="dense", heuristic=_lib.HEURISTIC_MINGAP, pruning=True, que
 
 
 LAUNCH_KERNELS = ("none", "forward", "packed", "px", "pxmw", "band")   # POA_KERNEL_* of include/poasta_amd.h
+REPLAY_KERNELS = ("none", "lane", "wave_lds", "wave_groups", "wave_generic", "flat_generic", "flat_lean")   # POA_REPLAY_*
+
+
+def _replay_records(call, handle, n_queries):
+    """The per-chunk records of poa_batch_replay_info / poa_multi_replay_info as dicts."""
+    out = []
+    while True:
+        v = (C.c_uint32 * 8)()
+        rc = call(handle, len(out), v)
+        if rc == -1 and (out or n_queries == 0):   # past the last chunk
+            return out
+        _lib.check(rc)
+        out.append({"kernel": REPLAY_KERNELS[v[0]], "win": int(v[1]), "lanes": int(v[2]), "waves": int(v[3]),
+                    "graph_lds": bool(v[4] & 1), "rec_lds": bool(v[4] & 2), "ring_global": bool(v[4] & 4), "persistent": bool(v[4] & 8),
+                    "resident": int(v[5]), "blocks": int(v[6]), "lds_bytes": int(v[7])})
 
 
 class AlignedPair:
@@ -445,6 +460,12 @@ class ResidentBatch:
             out.append({"kernel": LAUNCH_KERNELS[v[0]], "quads": int(v[1]), "fuse": bool(v[2] & 1), "mw": bool(v[2] & 2),
                         "waves": int(v[3]), "code_fmt": int(v[4]), "tb_lanes": int(v[5]), "tb_depth": int(v[6]), "queries": int(v[7])})
 
+    def replay_info(self):
+        """What the exact replay of the last run launched, one dict per chunk (poa_batch_replay_info): "kernel" in REPLAY_KERNELS,
+        "win" (priorities in the descriptor ring), "lanes" per query, "waves" per block, "graph_lds", "rec_lds", "ring_global",
+        "persistent", "resident" (blocks, 0: not computed), "blocks" launched, "lds_bytes"."""
+        return _replay_records(_lib.lib().poa_batch_replay_info, self.handle, self.n)
+
     def device_results(self):
         ptrs = [C.c_void_p() for _ in range(4)]
         _lib.check(_lib.lib().poa_batch_device_results(self.handle, *[C.byref(p) for p in ptrs]))
@@ -628,6 +649,11 @@ class MultiGraphBatch:
                 out[-1].update(fuse=False, mw=False, replay={1: "lds", 2: "generic"}[int(v[2]) & 3])
             if v[2] & _lib.LAUNCH_STRIPS:
                 out[-1]["strips"] = True
+
+    def replay_info(self):
+        """What the replay of the last run of an exact batch launched, one dict per chunk (poa_multi_replay_info), in the form
+        of ResidentBatch.replay_info."""
+        return _replay_records(_lib.lib().poa_multi_replay_info, self.handle, self.n)
 
     def search_counters(self):
         """[n, 4] num_queued, num_visited, num_pruned, steps of the last run of an exact batch (poa_multi_fetch_search_counters);

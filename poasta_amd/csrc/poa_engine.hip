@@ -287,6 +287,9 @@ struct poa_batch {
     uint32_t band_queries = 0, band_min_d = 0, band_chunks = 0;
     // what the dense one-piece path launched per chunk of the last run (poa_batch_last_launch); empty after any other run
     std::vector<DenseChunkPlan> launches;
+    // what the exact replay launched per chunk of the last run (poa_batch_replay_info / poa_multi_replay_info)
+    struct ReplayRecord { uint32_t v[8]; };   // kernel, win, lanes per query, waves per block, POA_REPLAY_BIT_*, resident, blocks, LDS bytes
+    std::vector<ReplayRecord> replays;
 
     // one event set per run since the last stats call, written by RunFrame and read by collect_stats
     std::vector<std::vector<hipEvent_t>> runs;
@@ -933,6 +936,10 @@ int replay_flat(poa_batch* b, const poa_batch::Chunk& ch, const ExactParams& ep,
     if (n_blocks > resident && !T.ptr(POA_TUNE_WS_STATIC)) {   // persistent waves, longest expected search first
         if (const int rc = persistent_schedule(b, ch, resident, stream, pp, n_blocks)) return rc;
     }
+    b->replays.push_back({{pp.lean ? (uint32_t)POA_REPLAY_FLAT_LEAN : (uint32_t)POA_REPLAY_FLAT_GENERIC, win, group, wpb,
+                           (pp.graph_lds || pp.rec_lds ? POA_REPLAY_BIT_GRAPH_LDS : 0u) | (pp.rec_lds ? POA_REPLAY_BIT_REC_LDS : 0u) |
+                               (pp.ring_global ? POA_REPLAY_BIT_RING_GLOBAL : 0u) | (pp.order ? POA_REPLAY_BIT_PERSISTENT : 0u),
+                           resident, n_blocks, lds_bytes}});
     HIP_TRY(b->d_ex_logs.alloc((size_t)n_blocks * wpb * ps_scratch_words()));
     pp.scratch = b->d_ex_logs.p;
     if (pp.lean) hipLaunchKernelGGL(poa_fsearch_lean_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, pp);
@@ -990,11 +997,16 @@ int replay_wave(poa_batch* b, const poa_batch::Chunk& ch, const ExactParams& ep,
     if (lds_bytes > 48u * 1024u)
         HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     const uint32_t per_block = wpb * (64 / group);
-    uint32_t n_blocks = (ch.count + per_block - 1) / per_block;
+    uint32_t n_blocks = (ch.count + per_block - 1) / per_block, resident = 0;
     if (group == 64 && !T.ptr(POA_TUNE_WS_STATIC)) {
-        const uint32_t resident = resident_blocks(b, kfn, wpb, lds_bytes);
+        resident = resident_blocks(b, kfn, wpb, lds_bytes);
         if (n_blocks > resident) { if (const int rc = persistent_schedule(b, ch, resident, stream, wp, n_blocks)) return rc; }
     }
+    b->replays.push_back({{group != 64 ? (uint32_t)POA_REPLAY_WAVE_GROUPS : (lds_all ? (uint32_t)POA_REPLAY_WAVE_LDS : (uint32_t)POA_REPLAY_WAVE_GENERIC),
+                           win, group, wpb,
+                           (wp.graph_lds ? POA_REPLAY_BIT_GRAPH_LDS : 0u) | (wp.rec_lds ? POA_REPLAY_BIT_REC_LDS : 0u) |
+                               (wp.ring_global ? POA_REPLAY_BIT_RING_GLOBAL : 0u) | (wp.order ? POA_REPLAY_BIT_PERSISTENT : 0u),
+                           resident, n_blocks, lds_bytes}});
     if (group != 64) hipLaunchKernelGGL(poa_wsearch_groups_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
     else if (lds_all) hipLaunchKernelGGL(poa_wsearch_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
     else hipLaunchKernelGGL(poa_wsearch_global_kernel, dim3(n_blocks), dim3(64 * wpb), lds_bytes, stream, wp);
@@ -1027,6 +1039,8 @@ int replay_lane(poa_batch* b, const poa_batch::Chunk& ch, ExactParams ep, const 
         ep.lanes_per_wave = lanes;
     }
     const uint32_t per_block = lanes * (EXACT_BLOCK / 64);
+    b->replays.push_back({{POA_REPLAY_LANE, b->ex_win, 1u, EXACT_BLOCK / 64, lds_graph ? POA_REPLAY_BIT_GRAPH_LDS : 0u, 0u,
+                           (ch.count + per_block - 1) / per_block, lds_graph ? lds_bytes : 0u}});
     hipLaunchKernelGGL(poa_exact_kernel, dim3((ch.count + per_block - 1) / per_block), dim3(EXACT_BLOCK), lds_graph ? lds_bytes : 0, stream, ep);
     return POA_OK;
 }
@@ -1395,8 +1409,14 @@ static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_confi
     // wave search: the descriptor ring covers `win` priorities (see the launch), and every live stack holds a chunk of its own
     uint32_t win = 64;
     {
-        const uint64_t win_need = (uint64_t)maxc + costs->gap_open + ((uint64_t)b->ex_skew + 3) * costs->gap_extend + 8;
-        while (win < win_need && win < (1u << 24)) win *= 2;
+        // exact_replay_win (poa_multi_plan.hpp) holds the rule; a free graph begin adds the spread of the initial priorities
+        ExactWinIn wi;
+        wi.x = costs->mismatch; wi.o = costs->gap_open; wi.e = costs->gap_extend; wi.skew = b->ex_skew;
+        wi.mingap = !cfg || cfg->heuristic == POA_HEURISTIC_MINGAP;
+        wi.free_begin = cfg && cfg->span == POA_SPAN_ENDS_FREE && cfg->graph_free_begin.kind == POA_BOUND_UNBOUNDED;
+        wi.max_len = b->max_len;
+        for (uint32_t r = 0; r < n; ++r) wi.dist_max = std::max<uint32_t>(wi.dist_max, fg.dist_max[r]);
+        win = exact_replay_win(wi);
     }
     const uint64_t pool_ws = pool64 + (uint64_t)BQ_CHUNK * (3ull * win + 8);
     if (pool_ws > 0xFFFFFFF0ull) return fail(POA_ERR_UNSUPPORTED, "exact replay: queue pool too large");
@@ -1603,6 +1623,7 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
     b->two_piece = false;
     set_layout(b, R.narrow, R.compact, R.relative);
     b->launches.clear();
+    b->replays.clear();
     b->band_used = false; b->band_queries = 0; b->band_min_d = 0; b->band_chunks = 0;
     b->pair_paired = 0; b->pair_single = 0;
     b->narrow_ran = 0; b->narrow_how = 0; b->narrow_chunks = 0;
@@ -1790,6 +1811,16 @@ int poa_batch_last_launch(poa_batch_t* b, uint32_t chunk, uint32_t out[8]) {
         return fail(POA_ERR_UNSUPPORTED, "poa_batch_last_launch: the last run was not a dense one-piece run");
     if (chunk >= b->launches.size()) return fail(POA_ERR_INVALID_ARG, "poa_batch_last_launch: the last run had no such chunk");
     for (int k = 0; k < 8; ++k) out[k] = b->launches[chunk].v[k];
+    return POA_OK;
+}
+
+int poa_batch_replay_info(poa_batch_t* b, uint32_t chunk, uint32_t out[8]) {
+    if (!b || !out) return fail(POA_ERR_INVALID_ARG, "poa_batch_replay_info: null argument");
+    if (!b->ran) return fail(POA_ERR_INVALID_ARG, "poa_batch_replay_info: poa_batch_run has not been called");
+    if (b->two_piece || b->sweep || b->ckpt || (b->last_mode != POA_MODE_EXACT && b->last_mode != POA_MODE_HYBRID))
+        return fail(POA_ERR_UNSUPPORTED, "poa_batch_replay_info: the last run replayed nothing (its mode was neither exact nor hybrid, and its span not ends-free)");
+    if (chunk >= b->replays.size()) return fail(POA_ERR_INVALID_ARG, "poa_batch_replay_info: the last run had no such chunk");
+    for (int k = 0; k < 8; ++k) out[k] = b->replays[chunk].v[k];
     return POA_OK;
 }
 
@@ -3249,6 +3280,7 @@ int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
     set_layout(b, true, true, false);
     b->active_plan = 0;
     b->launches.clear();
+    b->replays.clear();
     if (b->n_queries == 0) return run.end_empty(true);
 
     int lds_cap = 64 * 1024;
@@ -3324,8 +3356,18 @@ int poa_multi_run_exact(poa_multi_t* m, const poa_costs_t* costs, const poa_conf
         // the record of poa_multi_last_launch: the dense kind's, with the replay kernel in the low two launch bits (1: all in LDS,
         // 2: generic pointers) and POA_LAUNCH_STRIPS on top
         b->launches.push_back(DenseChunkPlan{{POA_KERNEL_PACKED, quads, (lds_all ? 1u : 2u) | strips, 4u, ml.code_fmt, 64u, ml.spec_depth, ch.count}, -1, false, true, false});
+        b->replays.push_back({{lds_all ? (uint32_t)POA_REPLAY_WAVE_LDS : (uint32_t)POA_REPLAY_WAVE_GENERIC, slot.win, 64u, 1u,
+                               (lds_all ? POA_REPLAY_BIT_GRAPH_LDS : 0u) | (xl.stage_rec ? POA_REPLAY_BIT_REC_LDS : 0u) | (lds_all ? 0u : POA_REPLAY_BIT_RING_GLOBAL),
+                               0u, ch.count, lds_bytes}});
     }
     return run.end_pairs();
+}
+
+int poa_multi_replay_info(poa_multi_t* m, uint32_t chunk, uint32_t out[8]) {
+    if (!m || !out) return fail(POA_ERR_INVALID_ARG, "poa_multi_replay_info: null argument");
+    if (!m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_replay_info: the batch was not created by poa_multi_create_exact");
+    if (!m->core.ran) return fail(POA_ERR_INVALID_ARG, "poa_multi_replay_info: poa_multi_run_exact has not been called");
+    return poa_batch_replay_info(&m->core, chunk, out);
 }
 
 int poa_multi_fetch_search_counters(poa_multi_t* m, uint32_t* out) {

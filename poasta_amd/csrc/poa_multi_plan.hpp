@@ -164,13 +164,49 @@ int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const 
 constexpr uint64_t MULTI_EXACT_PAD_CELLS = 64;      // 256 bytes behind every query's visited table, in four-byte cells
 // four-byte cells of the visited table of a query of `len` symbols on that graph, padding NOT included
 inline uint64_t multi_exact_table_cells(const FlatGraph& g, uint64_t len) { return 3ull * g.n * (((len + 1 + 63) / 64) * 64); }
-// the descriptor ring's width under those costs for a graph spread `skew` (prepare_exact's rule)
-inline uint32_t multi_exact_win(uint32_t x, uint32_t o, uint32_t e, uint32_t skew) {
-    const uint64_t maxc = x > o + e ? x : o + e;
-    const uint64_t need = maxc + o + ((uint64_t)skew + 3) * e + 8;
+// THE rule for the width of the replay's descriptor ring (`win` priorities, a power of two from 64): prepare_exact,
+// multi_exact_slot and the CPU harness (tests/exact_host) all call it.  bq_push (poa_exact.hpp) refuses a push that would make
+// the live priorities span `win` or more, so `win` must exceed highest live priority - lowest live priority at every push:
+//   jump     a pop at priority f pushes at most max(x, o + e) + o + (skew + 3) * e above f: one edit, one state change, and
+//            what the min-gap heuristic can grow along one edge and the greedy extension behind it, where skew = max over rows
+//            of dist_max - dist_min (heuristic.rs:70-102).  With ONE initial state this is the whole live range.
+//   spread   graph_free_begin = Unbounded queues EVERY real node at offset 0 with score 0 (push_initial_states,
+//            gap_affine.rs:150-163), at priority h(row, 0): 0 for a row whose [dist_min - 1, dist_max - 1] holds the query's
+//            length, else o + e * (distance of the length from that interval) <= o + e * max(max_len, dist_max).  Those
+//            entries stay queued while the search pops from the lowest of them upwards, so the live range is
+//            [f, max(highest initial priority, f + jump)] and the ring must cover the larger of the two.  Under Dijkstra
+//            order h = 0 and the spread is 0; a graph of two rows or fewer has no real node and takes the one-state branch,
+//            whose `win` the jump bounds as before.
+// Global runs and every other kind of graph_free_begin keep the jump term alone.
+struct ExactWinIn {
+    uint32_t x = 4, o = 6, e = 2;   // mismatch, gap open, gap extend
+    uint32_t skew = 0;              // max over rows of dist_max - dist_min
+    bool mingap = true;             // the min-gap heuristic (false: Dijkstra order)
+    bool free_begin = false;        // an ends-free run whose graph_free_begin is Unbounded
+    uint64_t max_len = 0;           // longest query of the batch           (read with free_begin only)
+    uint32_t dist_max = 0;          // largest dist_max over the graph's rows (read with free_begin only)
+};
+inline uint64_t exact_replay_win_need(const ExactWinIn& in) {
+    const uint64_t maxc = in.x > in.o + in.e ? in.x : in.o + in.e;
+    uint64_t span = maxc + in.o + ((uint64_t)in.skew + 3) * in.e;
+    if (in.free_begin && in.mingap) {
+        const uint64_t far = in.max_len > in.dist_max ? in.max_len : in.dist_max;
+        const uint64_t spread = in.o + far * in.e;
+        if (spread > span) span = spread;
+    }
+    return span + 8;
+}
+inline uint32_t exact_replay_win(const ExactWinIn& in) {
+    const uint64_t need = exact_replay_win_need(in);
     uint32_t win = 64;
     while (win < need && win < (1u << 24)) win *= 2;
     return win;
+}
+// the ring's width of a Global run under those costs for a graph spread `skew`
+inline uint32_t multi_exact_win(uint32_t x, uint32_t o, uint32_t e, uint32_t skew) {
+    ExactWinIn in;
+    in.x = x; in.o = o; in.e = e; in.skew = skew;
+    return exact_replay_win(in);
 }
 
 // One slot's sizes under `costs`, from what an exact plan holds of its graphs (rows, exits, spread, longest query).  The

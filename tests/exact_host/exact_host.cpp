@@ -11,16 +11,20 @@
 #include "../../include/poasta_amd.h"
 #include "../../poasta_amd/csrc/poa_exact.hpp"
 #include "../../poasta_amd/csrc/poa_graph.hpp"
+#include "../../poasta_amd/csrc/poa_multi_plan.hpp"   // exact_replay_win: the engine's rule for the descriptor ring
 
 using namespace poa_amd;
 
-static uint32_t g_batch = 0, g_win = 0, g_par_lanes = 0, g_par_rmax = 4, g_par_fast = 1, g_rec = 0;   // g_par_rmax == 0: the flat schedule (run_flat)
+static uint32_t g_batch = 0, g_win = 0, g_last_win = 0, g_par_lanes = 0, g_par_rmax = 4, g_par_fast = 1, g_rec = 0;   // g_par_rmax == 0: the flat schedule (run_flat)
 
 extern "C" {
 
 // 0: linked-list queue (ExactSearch::run); n > 0: bucket queue stepped in batches of n (ExactSearch::run_buckets)
 void exact_host_set_batch(uint32_t n) { g_batch = n; }
-void exact_host_set_window(uint32_t w) { g_win = w; }  // 0: a window that always suffices
+// 0: a window that always suffices; 0xFFFFFFFF: the engine's rule (exact_replay_win, as prepare_exact calls it for a batch of
+// this one query); any other value: that many priorities (a power of two)
+void exact_host_set_window(uint32_t w) { g_win = w; }
+uint32_t exact_host_last_window(void) { return g_last_win; }   // the ring of the last exact_host_run that had one
 // 1: the instantiation of the wave kernels whose one-round-trip path reads the per-row records (EX_AS_NO_SPEC | EX_AS_REC_LDS), run_buckets
 void exact_host_set_records(uint32_t on) { g_rec = on; }
 // lanes > 0: ExactSearch::run_parallel(lanes, rmax) — the step schedule of poa_psearch.hpp (entries of a stack expanded at once)
@@ -56,10 +60,28 @@ int exact_host_run(uint32_t n, uint32_t start, uint32_t end, const uint8_t* symb
     std::vector<uint32_t> bq_desc;
     std::vector<ExU4> bq_chunks;
     if (g_batch || g_par_lanes) {
-        uint32_t win = 64;
-        const uint32_t need = 2 * (std::max<uint32_t>(x, (uint32_t)o + e) + o + (uint32_t)(g.n + 2) * e) + 8;
-        while (win < need) win *= 2;
-        if (g_win) win = g_win;
+        // "always suffices": twice the engine's rule with the whole graph as spread and, for a free graph begin, the whole
+        // graph and query as the initial priorities' reach
+        ExactWinIn wi;
+        wi.x = x; wi.o = o; wi.e = e;
+        wi.mingap = heuristic != 0;
+        wi.free_begin = span && span[0] && span[3] == 0;
+        wi.max_len = len;
+        uint32_t win;
+        if (g_win == 0xFFFFFFFFu) {
+            for (uint32_t r = 0; r < g.n; ++r) {
+                wi.skew = std::max<uint32_t>(wi.skew, g.dist_max[r] - std::min(g.dist_min[r], g.dist_max[r]));
+                wi.dist_max = std::max<uint32_t>(wi.dist_max, g.dist_max[r]);
+            }
+            win = exact_replay_win(wi);
+        } else if (g_win) {
+            win = g_win;
+        } else {
+            wi.skew = g.n; wi.dist_max = g.n + len;
+            win = 64;
+            while (win < 2 * exact_replay_win_need(wi)) win *= 2;
+        }
+        g_last_win = win;
         bq_desc.assign((size_t)3 * win, BQ_EMPTY);
         bq_chunks.resize((size_t)BQ_CHUNK * (pool.size() / 32 + 3 * win + 64));
         W.bq_desc = bq_desc.data(); W.bq_win = win; W.bq_chunks = bq_chunks.data(); W.bq_chunk_cap = (uint32_t)(bq_chunks.size() / BQ_CHUNK);

@@ -166,6 +166,25 @@ void check_plan(const std::vector<MultiGraphIn>& in, const std::vector<uint64_t>
     uint32_t win = 64;
     while (win < std::max<uint64_t>(costs.x, costs.o + costs.e) + costs.o + ((uint64_t)skew + 3) * costs.e + 8) win *= 2;
     CHECK(s.win == win && s.win == multi_exact_win(costs.x, costs.o, costs.e, skew) && s.skew == skew);
+    {
+        // the one rule behind it (exact_replay_win): Global, a bounded graph begin and Dijkstra order are the jump term above,
+        // whatever the frontier fields say; a free graph begin under the min-gap heuristic covers o + e * max(len, dist_max)
+        ExactWinIn in;
+        in.x = costs.x; in.o = costs.o; in.e = costs.e; in.skew = skew; in.max_len = 100000; in.dist_max = 100000;
+        CHECK(exact_replay_win(in) == win);
+        in.free_begin = true; in.mingap = false;
+        CHECK(exact_replay_win(in) == win);
+        in.mingap = true;
+        CHECK(exact_replay_win_need(in) >= in.o + 100000ull * in.e + 8 && exact_replay_win(in) >= exact_replay_win_need(in) &&
+              exact_replay_win(in) >= win && (exact_replay_win(in) & (exact_replay_win(in) - 1)) == 0);
+        ExactWinIn c;   // costs 4 / 6 / 2, a chain: 32 nodes overflowed 64 priorities, 300 nodes put the ring in global memory
+        c.free_begin = true; c.max_len = 32; c.dist_max = 33;
+        CHECK(exact_replay_win(c) == 128);
+        c.max_len = 300; c.dist_max = 301;
+        CHECK(exact_replay_win(c) == 1024);
+        c.free_begin = false;
+        CHECK(exact_replay_win(c) == 64);
+    }
     const uint64_t wpn = (max_len + 1 + 63) / 64, swpn = (wpn + 63) / 64;
     CHECK(s.n_exit == n_exit && s.wpn == wpn && s.swpn == swpn && s.stack_cap == stack);
     CHECK(s.pool_cap == ((pool + 64 * (3ull * win + 8) + 63) & ~63ull) && s.pool_cap % BQ_CHUNK == 0);

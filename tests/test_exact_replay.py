@@ -24,7 +24,7 @@ def _p(a):
 def harness():
     src = os.path.join(ROOT, "tests", "exact_host", "exact_host.cpp")
     out = os.path.join(ROOT, "tests", "exact_host", "libexact_host.so")
-    deps = [src] + [os.path.join(ROOT, "poasta_amd", "csrc", f) for f in ("poa_exact.hpp", "poa_graph.cpp", "poa_graph.hpp")]
+    deps = [src] + [os.path.join(ROOT, "poasta_amd", "csrc", f) for f in ("poa_exact.hpp", "poa_graph.cpp", "poa_graph.hpp", "poa_multi_plan.hpp")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, src,
                                os.path.join(ROOT, "poasta_amd", "csrc", "poa_graph.cpp")])
@@ -32,6 +32,8 @@ def harness():
     X.exact_host_run.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [C.c_uint8] * 3 + [C.c_int, C.c_int, vp, C.c_uint32, vp, vp, vp, vp, vp]
     X.exact_host_bubbles.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [vp] * 5 + [C.c_uint32]
     X.exact_host_set_batch.argtypes = [C.c_uint32]
+    X.exact_host_set_window.argtypes = [C.c_uint32]
+    X.exact_host_last_window.restype = C.c_uint32
     X.exact_host_set_parallel.argtypes = [C.c_uint32] * 3
     X.exact_host_set_records.argtypes = [C.c_uint32]
     X.exact_host_run2.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [vp, C.c_int, C.c_int, vp, C.c_uint32, vp, vp, vp]
@@ -204,6 +206,185 @@ def test_replay_equals_oracle_search_cpu(oracle, harness, queue_variant):
     assert _compare(oracle, harness, poa.graph, poa.queries(6, length=0), (4, 6, 2), 1, 1) == 6
     pg = W.PangenomePOA(ref_len=300, n_hap=6, p_snp=0.02, p_indel=0.01, max_indel=6, seed=4)
     assert _compare(oracle, harness, pg.graph, pg.queries(6, length=120), (4, 6, 2), 1, 1) == 6
+
+
+# ---- the descriptor ring's width (exact_replay_win, poa_multi_plan.hpp) -------------------------------------------------------
+WIN_ENGINE = 0xFFFFFFFF        # exact_host_set_window: the engine's rule; 0: a window that always suffices
+WIN_COSTS = [(4, 6, 2), (40, 30, 4), (100, 60, 5), (200, 100, 2), (255, 250, 5), (1, 0, 40), (3, 1, 60), (1, 10, 255), (60, 0, 255)]
+
+
+def _win_jump(x, o, e, skew):
+    """The ring of a run with one initial state: what every Global run had before the free-begin term existed."""
+    need, win = max(x, o + e) + o + (skew + 3) * e + 8, 64
+    while win < need:
+        win *= 2
+    return win
+
+
+def _win_rule(x, o, e, skew, mingap=True, free_begin=False, max_len=0, dist_max=0):
+    """exact_replay_win restated: the jump of one pop, or the spread of the initial priorities of a free graph begin."""
+    need = max(x, o + e) + o + (skew + 3) * e
+    if free_begin and mingap:
+        need = max(need, o + e * max(max_len, dist_max))
+    need, win = need + 8, 64
+    while win < need:
+        win *= 2
+    return win
+
+
+def _n_prio(x, o, e, n, max_len):
+    """prepare_exact's priority range: the wave search runs while win <= n_prio, the lane kernel (no ring) otherwise."""
+    return (n + max_len + 2) * max(x, o + e) + o + (n + max_len) * e + 64
+
+
+def _graph_spread(X, g):
+    """(skew, largest dist_max) of the product's bubble index: what prepare_exact reads for the rule."""
+    n = g.n
+    dmin, dmax, ex = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+    off, nbm = np.zeros(n + 1, np.uint32), np.zeros((64 * n, 3), np.uint32)
+    assert X.exact_host_bubbles(g.n, g.start, g.end, _p(g.symbol), _p(g.succ_off), _p(g.succ), _p(g.pred_off), _p(g.pred),
+                                _p(dmin), _p(dmax), _p(ex), _p(off), _p(nbm), 64 * n) == 0
+    return int((dmax - np.minimum(dmin, dmax)).max()), int(dmax.max())
+
+
+def _chain(n, seed=0, bypass=None, alphabet=b"ACGT"):
+    """A chain of n nodes; bypass = (i, j): one more edge from its i-th to its j-th node.  Returns (graph, its symbols)."""
+    rng = np.random.Generator(np.random.PCG64(90 + seed))
+    sym = np.frombuffer(alphabet, np.uint8)[rng.integers(0, len(alphabet), n)]
+    b = GraphBuilder()
+    ids = b.add_path(sym)
+    if bypass:
+        b.add_edge(ids[bypass[0]], ids[bypass[1]])
+    return b.finish(), sym
+
+
+def _span_words(span):
+    """exact_host_run's span argument for dict(qry_free_end=, graph_free_begin=, graph_free_end=) of (kind, value); None: Global.
+    A bound that is not named is Unbounded (kind 0), as in oracle.ends_free."""
+    if span is None:
+        return None
+    qfe, gfb, gfe = span.get("qry_free_end", (0, 0)), span.get("graph_free_begin", (0, 0)), span.get("graph_free_end", (0, 0))
+    return np.array([1, qfe[0], qfe[1], gfb[0], gfe[0], gfe[1]], np.uint32)
+
+
+def _run_both_windows(X, g, q, costs, heur, prune, span, spread):
+    """One search under the window that always suffices and under the engine's rule: status, score, the three counters, the
+    end cell and all three planes must be equal, and the engine's window the restated rule's.  Returns (status, win)."""
+    q = np.ascontiguousarray(q, np.uint8)
+    sarr = _span_words(span)
+    got = []
+    for mode in (0, WIN_ENGINE):
+        X.exact_host_set_window(mode)
+        pl = [np.zeros((g.n, len(q) + 1), np.uint32) for _ in range(3)]
+        xo = np.zeros(6, np.uint32)
+        rc = X.exact_host_run(g.n, g.start, g.end, _p(g.symbol), _p(g.succ_off), _p(g.succ), _p(g.pred_off), _p(g.pred),
+                              *costs, heur, prune, _p(q), len(q), _p(xo), _p(pl[0]), _p(pl[1]), _p(pl[2]),
+                              _p(sarr) if sarr is not None else None)
+        got.append((rc, xo.tolist(), pl, X.exact_host_last_window()))
+    X.exact_host_set_window(0)
+    what = (g.n, len(q), costs, heur, prune, span)
+    free_begin = span is not None and span.get("graph_free_begin", (0, 0))[0] == 0
+    skew, dist_max = spread
+    win = got[1][3]
+    assert win == _win_rule(*costs, skew, heur != 0, free_begin, len(q), dist_max), what
+    if not free_begin:
+        assert win == _win_jump(*costs, skew), what          # Global, Included and Excluded begins: the ring they always had
+    # the lane-kernel fallback (replay_chunk: win > n_prio) is never reached BECAUSE of the free-begin term
+    assert win <= _n_prio(*costs, g.n, len(q)) or win == _win_jump(*costs, skew), what
+    assert got[0][0] == got[1][0], ("status", got[0][0], got[1][0], win, what)
+    assert got[0][1] == got[1][1], ("score / counters / end cell", got[0][1], got[1][1], what)
+    for a, b in zip(got[0][2], got[1][2]):
+        assert np.array_equal(a, b), ("visited table", what)
+    return got[0][0], win
+
+
+WINDOW_SCHEDULES = [("buckets", 7), ("flat", (8, 0, 1)), ("flat_lean", (8, 0, 2))]
+
+
+@pytest.mark.parametrize("schedule", [s[1] for s in WINDOW_SCHEDULES], ids=[s[0] for s in WINDOW_SCHEDULES])
+def test_engine_window_rule_replays_like_a_window_that_always_suffices_cpu(harness, schedule):
+    """exact_replay_win is the ONE rule for the replay's descriptor ring (prepare_exact, multi_exact_slot and this harness call
+    it).  Every case runs twice, under a ring that always suffices and under the rule's: status, score, counters, end cell and
+    the three planes of the visited table are equal, every status is EX_OK (so the two sides cannot agree by failing alike),
+    and the rule's ring equals its restatement above — for Global runs and Included / Excluded graph begins the ring of the
+    jump term alone, tier by tier from 64 to 16384.
+
+    Before the free-begin term a chain of 32 nodes under graph_free_begin = Unbounded ended with EX_POOL_FULL (status 2) at
+    costs 4/6/2 under the min-gap heuristic: the initial states spread over o + e * max(len, dist_max) priorities, the ring
+    held 64.
+
+    The lane-kernel fallback (replay_chunk takes it when win > n_prio): the free-begin term never causes it.  Where the spread
+    decides, need <= o + e * (n + len) + 8 with dist_max <= n, hence win < 2 * need <= 2 * o + 2 * e * (n + len) + 16, while
+    n_prio = (n + len + 2) * max(x, o + e) + o + (n + len) * e + 64 >= (n + len) * (o + 2 * e) + 3 * o + 2 * e + 64 exceeds that.
+    So win > n_prio only where the jump term alone gives it, as before; _run_both_windows asserts it per case."""
+    X = harness
+    if isinstance(schedule, tuple):
+        X.exact_host_set_parallel(*schedule)
+    else:
+        X.exact_host_set_batch(schedule)
+    INC, EXC = 1, 2
+    spans = [None,                                                                               # Global
+             dict(),                                                                             # all Unbounded
+             dict(qry_free_end=(INC, 0), graph_free_end=(INC, 0)),                               # free begin, Included(0) ends
+             dict(qry_free_end=(EXC, 1), graph_free_end=(EXC, 1)),                               # free begin only: Excluded(1) frees nothing
+             dict(graph_free_begin=(INC, 0)),                                                    # bounded begin, free ends
+             dict(qry_free_end=(INC, 2)), dict(qry_free_end=(EXC, 3), graph_free_end=(INC, 2)),  # the mixed spans of the ends-free test
+             dict(graph_free_begin=(INC, 0), qry_free_end=(INC, 0), graph_free_end=(EXC, 3)), dict(graph_free_end=(INC, 0))]
+    free_spans = spans[1:4]
+    hp = ((1, 1), (0, 1), (1, 0), (0, 0))
+    n_run, n_ok, tiers_global, tiers_free = 0, 0, set(), set()
+    try:
+        # random DAGs: 3 to 40 nodes, four edge densities, both alphabets; costs, heuristic / pruning and span rotate
+        k = 0
+        for pi, p_edge in enumerate((0.08, 0.15, 0.3, 0.5)):
+            for seed in range(36):
+                rng = np.random.Generator(np.random.PCG64(11000 + 100 * pi + seed))
+                alpha = b"AC" if seed % 2 else b"ACGT"
+                g = W.random_dag(4000 + 100 * pi + seed, n_nodes=int(rng.integers(3, 41)), p_edge=p_edge, alphabet=alpha)
+                spread = _graph_spread(X, g)
+                for qi in range(3):
+                    q = W.random_walk_query(rng, g, 0.3, alpha)
+                    k += 1
+                    span = spans[k % len(spans)]
+                    st, win = _run_both_windows(X, g, q, WIN_COSTS[(k // 2) % len(WIN_COSTS)], *hp[(k // 3) % 4], span, spread)
+                    n_run += 1; n_ok += st == 0
+        # chains under a free graph begin: 32 nodes and more overflowed the ring of the jump term alone
+        for n in (20, 28, 32, 40, 100, 300):
+            g, sym = _chain(n, seed=n)
+            spread = _graph_spread(X, g)
+            for li, ln in enumerate((1, 8, n // 2, n)):
+                a = (n - ln) // 3
+                q = sym[a:a + ln]
+                for si, span in enumerate(free_spans + [spans[4], None]):
+                    for costs in ((4, 6, 2), WIN_COSTS[1 + (li + si + n) % 8]):
+                        for heur, prune in (((1, 1), (0, 0)) if n <= 100 else ((1, 1),)):
+                            st, win = _run_both_windows(X, g, q, costs, heur, prune, span, spread)
+                            n_run += 1; n_ok += st == 0
+                            if span in free_spans and heur:
+                                tiers_free.add(win)
+        # skew: a chain of 12 with SNP-free body (skew 0) and chains with one bypass edge (skew about n): Global under every cost
+        # set puts the ring in every tier from 64 to 16384
+        for n, bypass in ((12, None), (31, (1, 28)), (34, (1, 32))):
+            g, sym = _chain(n, seed=7 * n, bypass=bypass)
+            spread = _graph_spread(X, g)
+            if bypass:
+                assert spread[0] == bypass[1] - bypass[0] - 1, spread
+            rng = np.random.Generator(np.random.PCG64(12000 + n))
+            qs = [sym, np.concatenate([sym[:bypass[0] + 1], sym[bypass[1]:]]) if bypass else sym[2:9], W.random_walk_query(rng, g, 0.3)]
+            for ci, costs in enumerate(WIN_COSTS):
+                for qi, q in enumerate(qs):
+                    for span in (None, spans[1 + (ci + qi) % 8]):
+                        st, win = _run_both_windows(X, g, q, costs, *hp[(ci + qi) % 4], span, spread)
+                        n_run += 1; n_ok += st == 0
+                        if span is None:
+                            tiers_global.add(win)
+    finally:
+        X.exact_host_set_window(0)
+        X.exact_host_set_batch(0)
+        X.exact_host_set_parallel(0, 4, 1)
+    assert n_ok == n_run and n_run > 1000, (n_ok, n_run)
+    assert tiers_global == {64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384}, sorted(tiers_global)
+    assert {128, 256, 1024} <= tiers_free, sorted(tiers_free)      # chains of 32 / 100 / 300 nodes at costs 4/6/2
 
 
 # ------------------------------------------------------------------------------------------------

@@ -150,6 +150,10 @@ def _fetch(mb):
     res = mb.fetch()
     res.counters = mb.search_counters()
     res.launches = mb.launches()
+    res.replay = mb.replay_info()      # poa_multi_replay_info: the replay's own record, `win` included
+    assert [r["kernel"] for r in res.replay] == [{"lds": "wave_lds", "generic": "wave_generic"}[l["replay"]] for l in res.launches]
+    assert all(r["lanes"] == 64 and r["waves"] == 1 and r["blocks"] == l["queries"] and r["ring_global"] == (l["replay"] == "generic")
+               for r, l in zip(res.replay, res.launches))
     return res
 
 
@@ -218,6 +222,7 @@ def test_multi_exact_mixed_graphs_one_run(engine, oracle, mode, heur, prune):
     replayed = _check(engine, oracle, res, "mixed", graphs, seqs, costs, mode, heur, prune, (mode, heur, prune))
     assert res.stats["n_chunks"] == 1 and res.stats["n_queries"] == n
     assert [l["replay"] for l in res.launches] == ["lds"] and res.launches[0]["queries"] == n
+    assert res.replay[0]["win"] in (64, 128) and res.replay[0]["graph_lds"] and res.replay[0]["lds_bytes"] >= 12 * res.replay[0]["win"]
     if mode == "exact":
         assert replayed == n - len(seqs[5])   # every query but those of the graph without real nodes
     else:
@@ -290,6 +295,9 @@ def test_multi_exact_wide_ring(engine, oracle):
     _check(engine, oracle, res, "mixed", graphs, seqs, costs, "exact", "mingap", True, "40/30/3")
     glob = _with_env(dict(POA_EXACT_LDS="0"), lambda: _run(engine, graphs, seqs, costs))
     assert [l["replay"] for l in glob.launches] == ["generic"] and [l["replay"] for l in res.launches] == ["lds"]
+    win = res.replay[0]["win"]
+    assert win >= 128 and win & (win - 1) == 0 and win >= need and glob.replay[0]["win"] == win
+    assert res.replay[0]["lds_bytes"] >= 12 * win and glob.replay[0]["lds_bytes"] == 0 and not glob.replay[0]["graph_lds"]
     _same(glob, res, "40/30/3, generic pointers")
 
 
