@@ -8,7 +8,8 @@ windowed model (tests/band_model.py) under the plan of poa_band_plan.cpp:
   * INF (or a value >= 0x3FFF) reads 0x3FFF in the score field; nothing finer is defined there (memory reads turn it into INF);
   * the same for the kept D rows against 0x3FFF.
 So that the second rule hides nothing, every case asserts from the oracle's planes alone that all finite M and D values are below
-0x3FFF.  Only columns 0..L are compared.  The banded kernel writes its windows only: outside them the planes hold what was there
+0x3FFF (the cases of tests/test_clamped_cells.py open their Batch with clamped=True and assert the opposite: that finite values at
+and above 0x3FFF are there, in M and in the kept D rows).  Only columns 0..L are compared.  The banded kernel writes its windows only: outside them the planes hold what was there
 before, which one case checks word for word.  All comparisons are bit-exact.
 
 Which queries the banded pass certifies follows from the plan's D and the oracle's score (tests/test_band_forward.py); those path
@@ -84,8 +85,8 @@ def _assert_words(fetched, planes, mask, what):
 
 class Batch:
     """a graph and its reads; the oracle's planes (by engine row), the plans and the model's planes, each computed once"""
-    def __init__(self, engine, oracle, g, qs):
-        self.engine, self.oracle, self.g = engine, oracle, g
+    def __init__(self, engine, oracle, g, qs, clamped=False):
+        self.engine, self.oracle, self.g, self.clamped = engine, oracle, g, clamped
         self.qs = [np.ascontiguousarray(q, np.uint8) for q in qs]
         assert len(qs) <= 16 and 512 <= max(len(q) for q in qs) <= 1023, [len(q) for q in qs]      # one chunk of the one-strip kernel
         self.qseq, self.qoff = pack_queries(self.qs)
@@ -100,11 +101,20 @@ class Batch:
         if (i, costs) not in self._true:
             od = self.og.dense_align(self.qs[i], self.oracle.Costs(*costs), planes=True)
             planes = [np.ascontiguousarray(od[name][self.orank])[self.node_of_row] for name in ("M", "I", "D")]
-            # from the oracle alone: every finite value fits the 14-bit score field, so only true INF cells fall under the ">=" rule
-            for p in (planes[0], planes[2]):
-                assert int(p[p != INF].max()) < 0x3FFF
+            self._fits(planes)
             self._true[(i, costs)] = planes
         return self._true[(i, costs)]
+
+    def _fits(self, planes):
+        """from the planes alone: every finite value fits the 14-bit score field, so only true INF cells fall under the ">=" rule;
+        clamped: finite M values and finite values of the kept D rows at and above 0x3FFF are there (a query of two columns or
+        more: an empty or one-symbol query rides along under the others' pitch)"""
+        m, d = planes[0], planes[2][self.kept]
+        if not self.clamped:
+            for p in (planes[0], planes[2]):
+                assert int(p[p != INF].max()) < 0x3FFF
+        elif m.shape[1] > 2:
+            assert ((m != INF) & (m >= 0x3FFF)).any() and ((d != INF) & (d >= 0x3FFF)).any()
 
     def dense(self, costs):
         if costs not in self._dense:
@@ -122,8 +132,7 @@ class Batch:
         if (i, costs) not in self._model:
             q = self.qs[i]
             planes = windowed_planes(self.g, self.rows, q, costs, SEG_ROWS, WINDOW, self.plan(X, len(q)).bases)
-            for p in (planes[0], planes[2]):
-                assert int(p[p != INF].max()) < 0x3FFF
+            self._fits(planes)
             self._model[(i, costs)] = planes
         return self._model[(i, costs)]
 

@@ -33,6 +33,7 @@ def harness():
                                os.path.join(ROOT, "poasta_amd", "csrc", "poa_graph.cpp")])
     X = C.CDLL(out)
     X.derive_host_check.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [C.c_uint8] * 2 + [vp, C.c_uint32, vp, vp, vp, vp]
+    X.derive_host_check_clamped.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [C.c_uint8] * 2 + [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp]
     X.derive_host_chain_nodes.argtypes = [C.c_uint32] * 3 + [vp] * 5 + [vp]
     return X
 
