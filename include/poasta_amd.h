@@ -297,7 +297,11 @@ int poa_align_batch_ex(const poa_graph_t* g, const poa_costs_t* costs, const poa
  * `poasta align -g 6,24 -e 2,1` (src/bin/poasta.rs:319-445).  Same buffers as poa_align_batch.  Scores are the optimum of the
  * reference's two-piece alignment graph (what its search returns in Dijkstra order without pruning); flags == 0 certifies
  * the alignment as the one the reference's backtrace rule forces (gap_affine_2piece.rs:639-794).  Returns
- * POA_ERR_INVALID_ARG where the reference's constructor panics (extend1 < extend2). */
+ * POA_ERR_INVALID_ARG where the reference's constructor panics (extend1 < extend2).
+ * Like poa_align_batch it is a resident batch created, run (poa_batch_run_2piece), fetched and destroyed inside the call.  The
+ * batch is asked to hold min(60 % of the device's free memory, 64 GiB) of planes at most, and no more than the run needs: 20
+ * bytes per cell of a query's pitch with u32 cells, 12 with u16 cells (the batch's three-plane 4-byte regions, of which five
+ * u16 planes use 10); a larger batch runs in chunks.  The workspace is parked for the next call (poa_release_cache). */
 int poa_align_batch_2piece(const poa_graph_t* g, const poa_costs2_t* costs, uint32_t n_queries,
                            const uint8_t* qseq, const uint64_t* qoff, uint32_t* score,
                            poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity,
@@ -312,7 +316,10 @@ int poa_align_batch_2piece(const poa_graph_t* g, const poa_costs2_t* costs, uint
  * poa_align_batch_ex.  score[n] is the score the reference's search returns (which may exceed the dense optimum), pairs
  * its backtrace (gap_affine_2piece.rs:639-794, :944-1043); flags: POA_FLAG_REF_PANIC, POA_FLAG_TRUNCATED,
  * POA_FLAG_EXACT_OVERFLOW (queue pool: raise cfg->queue_entries_per_cell).  search_counters (may be NULL): 4 words per query —
- * num_queued, num_visited, num_pruned (AstarResult, astar.rs:228) and the queue entries that were live at once. */
+ * num_queued, num_visited, num_pruned (AstarResult, astar.rs:228) and the queue entries that were live at once.
+ * The replay runs on the same kind of batch: five u32 planes per query at the query's own pitch and, per query of a chunk, the
+ * search's queue and reached sets; both together take 85 % of the device's free memory at most, a larger batch runs in chunks.
+ * poa_stats_t: ms_exact is the search, ms_forward 0, n_exact the number of queries. */
 /* Mode SCORE: the scores poa_align_batch_2piece returns, by the score-only sweep under the one-piece costs
  * open' = open1 + extend1 - extend2, extend' = extend2; no pairs, flags as under POA_MODE_SCORE.
  * Mode CHECKPOINT2: everything poa_align_batch_2piece returns, from a batch of the checkpointed footprint created, run,
@@ -326,8 +333,9 @@ int poa_align_batch_2piece_ex(const poa_graph_t* g, const poa_costs2_t* costs, c
 int poa_planes_2piece(const poa_graph_t* g, const poa_costs2_t* costs, const uint8_t* seq, uint32_t len,
                       uint32_t* m, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2, int device);
 
-/* poa_align_batch parks its plane workspace (tens of GB; hipMalloc/hipFree of it cost seconds) per device for the next
- * call; this returns that memory to the driver.  (src/bin/lasagna.rs has no counterpart: its tables live on the heap.) */
+/* poa_align_batch and poa_align_batch_2piece (with _ex, and poa_planes_2piece) park their plane workspace (tens of GB;
+ * hipMalloc/hipFree of it cost seconds) per device for the next call; this returns that memory to the driver.
+ * (src/bin/lasagna.rs has no counterpart: its tables live on the heap.) */
 void poa_release_cache(void);
 
 /* ---- resident batch (queries and results stay in HBM; used by the multi-GPU driver) ------ */
@@ -370,8 +378,8 @@ int poa_batch_run_ex(poa_batch_t* b, const poa_costs_t* costs, const poa_config_
  *                                first run of a width.
  *   POA_MODE_SCORE               the score-only sweep under open' = open1 + extend1 - extend2, extend' = extend2; a batch created
  *                                for POA_MODE_SCORE.
- *   POA_MODE_EXACT / HYBRID / CHECKPOINT, POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED (the replay keeps a workspace of its own:
- *                                poa_align_batch_2piece_ex; checkpointed mode is one-piece only).
+ *   POA_MODE_EXACT / HYBRID / CHECKPOINT, POA_SPAN_ENDS_FREE: POA_ERR_UNSUPPORTED (the replay runs through the one-shot call
+ *                                alone: poa_align_batch_2piece_ex; checkpointed mode is one-piece only).
  *   POA_MODE_CHECKPOINT2         poa_align_batch_2piece's results from a slot-sized workspace: per chunk a two-piece sweep that
  *                                keeps slots and snapshots of M, D1 and D2 (pass 1), then, last segment first, the recompute of a
  *                                segment's five planes into the window and the walk through it (pass 2); a batch created for

@@ -33,6 +33,18 @@ uint64_t choose_workspace(uint64_t requested, uint64_t free_bytes, uint64_t fixe
     return ws;
 }
 
+TwoPieceWorkspace two_piece_workspace(uint64_t free_bytes, uint64_t bytes_total, uint64_t largest, uint64_t replay_slot_bytes, bool replay) {
+    uint64_t budget = std::min<uint64_t>((uint64_t)(free_bytes * 0.6), 64ull << 30);
+    uint32_t max_slots = ~0u;
+    if (replay) {
+        // (the replay is bound by the latency of its dependent loads: as many searches in flight as the memory holds)
+        const uint64_t per_slot = std::max<uint64_t>(largest + replay_slot_bytes, 1);
+        max_slots = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)(free_bytes * 0.85) / per_slot, 1), ~0u);
+        budget = max_slots * largest;
+    }
+    return {std::max(std::min(budget, bytes_total), largest), max_slots};
+}
+
 // POA_PLANES=32 forces u32 cells (debug / A-B)
 bool planes32(const TuneView& T) { const int* pv = T.ptr(POA_TUNE_PLANES); return pv && *pv == 32; }
 

@@ -25,6 +25,13 @@ bool planes32(const TuneView& T);
 // choose_workspace: bytes of plane workspace, or WORKSPACE_NO_FIT when the largest item does not fit in device memory.
 constexpr uint64_t WORKSPACE_NO_FIT = ~0ull;
 uint64_t choose_workspace(uint64_t requested, uint64_t free_bytes, uint64_t fixed, uint64_t bytes_total, uint64_t largest, bool own_footprint);
+// The workspace a one-shot call of the two-piece model asks its batch to hold, from what the device has free and the queries'
+// plane bytes (all of them, the largest one's).  Dense pass: min(60 % of free, 64 GiB).  Replay: planes and search workspaces
+// (replay_slot_bytes per query of a chunk) share 85 % of free as max_slots queries of the largest size would; a chunk then
+// takes at most max_slots queries, so shorter queries never add search workspaces beyond that.  Never more than bytes_total,
+// never less than `largest`.
+struct TwoPieceWorkspace { uint64_t bytes; uint32_t max_slots; };
+TwoPieceWorkspace two_piece_workspace(uint64_t free_bytes, uint64_t bytes_total, uint64_t largest, uint64_t replay_slot_bytes, bool replay);
 // The concatenated table of a batch over many graphs: the table src_of(g) of every graph that owns its tables (a handle's first
 // listing, table_of == g) copied to that graph's base in `dst`, which the plan sized; a repeated handle is copied once.
 template <typename T, typename GraphPlan, typename SrcOf>

@@ -163,6 +163,12 @@ bool PlaneWorkspace::acquire(int dev, size_t need, std::string& err, bool exact)
     bytes = need;
     return true;
 }
+// what a batch on `dev` can take over besides the device's free memory
+static size_t parked_workspace_bytes(int dev) {
+    if (dev < 0 || dev >= 16) return 0;
+    std::lock_guard<std::mutex> lk(g_ws_cache.mu);
+    return g_ws_cache.bytes[dev];
+}
 void PlaneWorkspace::release() {
     if (!p) return;
     void* victim = p;
@@ -207,7 +213,7 @@ struct poa_batch {
     // the five u16 planes of a two-piece run fit a query's region of plan[0] (2.5 of its 3 x rows x pitch elements)
     Plan plan[4];
     uint64_t plan_ws = 0;            // bytes of workspace the plans were cut for
-    bool two_piece = false;          // the last run was a dense two-piece run (five planes in the workspace)
+    bool two_piece = false;          // the last run was a two-piece run over five full planes: the dense pass, or (last_mode EXACT / HYBRID) the replay
     bool plan16_same = true;         // plan[1], plan[2] not built: everything fits in one chunk anyway
     int active_plan = 0;             // plan of the last run
     const Plan& cur() const { return plan[active_plan]; }
@@ -243,7 +249,8 @@ struct poa_batch {
     DevBuf<uint32_t> d_ex_counters;    // wave search: num_queued, num_visited, num_pruned, steps per query
     DevBuf<uint32_t> d_ex_logs;        // parallel-step search (poa_fsearch.hpp): the lanes' push logs, per resident wave
     DevBuf<FlatGraph::RowRec> d_ex_rec; // per-row records of its lean step (FlatGraph::row_rec)
-    bool exact_ready = false;
+    bool ex_tables_ready = false;      // the replay's view of the graph and its per-query result buffers are there (prepare_exact_tables)
+    bool exact_ready = false;          // the search workspace is sized for the one-piece replay (prepare_exact); prepare_replay2 clears it
     bool prof_on = false;              // the last run asked for the replay kernel's cycle counts (POA_TUNE_WS_PROF)
     uint32_t last_mode = 0;
     // score-only batch (poa_batch_create_ex with POA_MODE_SCORE): the workspace holds n_sweep_slots rows of M and D per query,
@@ -350,6 +357,7 @@ static void collect_stats(poa_batch* b, poa_stats_t* stats) {
     stats->n_runs = (uint32_t)b->runs.size();
     stats->n_forward_launches = launches;
     if (b->sweep) tb = 0.f;   // nothing but the sweep runs
+    if (b->two_piece && b->last_mode != POA_MODE_DENSE) { ex = fwd; fwd = 0.f; }   // the two-piece replay: the search runs where the forward pass would
     stats->ms_forward = fwd; stats->ms_traceback = tb; stats->ms_exact = ex; stats->ms_total = total;
     for (auto& r : b->runs) b->free_sets.push_back(std::move(r));
     b->runs.clear();
@@ -681,9 +689,10 @@ static int prepare_band_pairs(poa_batch* b) {
 
 // Greedy chunking of the queries over `ws` bytes of workspace (elems_of(i) elements of elem_bytes each), with the chunks evened
 // out: the forward kernels that take a workgroup per query finish with their most loaded CU, so 2 000 queries that fit 527 at
-// a time run as 4 x 500, not 3 x 527 + 419 (measured on configs[4]: 434 -> 320 ms).
+// a time run as 4 x 500, not 3 x 527 + 419 (measured on configs[4]: 434 -> 320 ms).  max_count: queries per chunk at most (the
+// two-piece replay, which holds a search workspace per query of a chunk).
 template <typename ElemsOf>
-static void build_chunk_plan(poa_batch::Plan& pl, uint32_t n_queries, uint64_t ws, uint64_t elem_bytes, ElemsOf elems_of) {
+static void build_chunk_plan(poa_batch::Plan& pl, uint32_t n_queries, uint64_t ws, uint64_t elem_bytes, ElemsOf elems_of, uint32_t max_count = ~0u) {
     auto need_of = [&](uint32_t i) { return (uint64_t)elems_of(i) * elem_bytes; };
     auto greedy = [&](uint64_t budget, std::vector<poa_batch::Chunk>& chunks, std::vector<uint64_t>& off) {
         chunks.clear();
@@ -692,7 +701,7 @@ static void build_chunk_plan(poa_batch::Plan& pl, uint32_t n_queries, uint64_t w
         uint64_t used = 0;
         for (uint32_t i = 0; i < n_queries; ++i) {
             const uint64_t need = need_of(i);
-            if (used + need > budget && i > first) {
+            if ((used + need > budget || i - first >= max_count) && i > first) {
                 chunks.push_back({first, i - first});
                 first = i; used = 0;
             }
@@ -1379,6 +1388,44 @@ static int batch_create_impl(const poa_graph_t* g, int device, uint32_t n_querie
     });
 }
 
+// The replay's view of the graph (the bubble index is built by now) and the per-query result buffers of a search, uploaded once
+// per batch: what the one-piece replay (prepare_exact) and the two-piece one (prepare_replay2) share.
+static int prepare_exact_tables(poa_batch* b) {
+    if (b->ex_tables_ready) return POA_OK;
+    const FlatGraph& fg = b->graph->g;
+    const uint32_t n = fg.n;
+    HIP_TRY(b->d_succ_off.alloc(fg.succ_row_off.size()));
+    HIP_TRY(b->d_succ_rows.alloc(std::max<size_t>(fg.succ_rows.size(), 1)));
+    HIP_TRY(b->d_dist_min.alloc(n)); HIP_TRY(b->d_dist_max.alloc(n)); HIP_TRY(b->d_exit_idx.alloc(n));
+    HIP_TRY(b->d_node_row.alloc(n)); HIP_TRY(b->d_sp_to_end.alloc(n));
+    HIP_TRY(b->d_ex_end.alloc(2 * (size_t)std::max<uint32_t>(b->n_queries, 1)));
+    HIP_TRY(hipMemcpy(b->d_node_row.p, fg.node_row.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_sp_to_end.p, fg.sp_to_end.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(b->d_ex_sym.alloc((size_t)n + 4));
+    {
+        std::vector<uint8_t> row_sym((size_t)n + 4, 0);
+        for (uint32_t r = 0; r < n; ++r) row_sym[r] = fg.rows[r].sym;
+        HIP_TRY(hipMemcpy(b->d_ex_sym.p, row_sym.data(), row_sym.size(), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(b->d_nbm_off.alloc(n + 1)); HIP_TRY(b->d_nbm.alloc(std::max<size_t>(fg.nbm.size(), 1)));
+    if (!fg.row_rec.empty()) {
+        HIP_TRY(b->d_ex_rec.alloc(fg.row_rec.size()));
+        HIP_TRY(hipMemcpy(b->d_ex_rec.p, fg.row_rec.data(), fg.row_rec.size() * sizeof(FlatGraph::RowRec), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(b->d_ex_status.alloc(std::max<uint32_t>(b->n_queries, 1)));
+    HIP_TRY(b->d_ex_counters.alloc(4 * (size_t)std::max<uint32_t>(b->n_queries, 1)));
+    HIP_TRY(b->d_ex_prof.alloc(8 * (size_t)std::max<uint32_t>(b->n_queries, 1)));   // (diagnostics; once, not per chunk while a kernel may write it)
+    HIP_TRY(hipMemcpy(b->d_succ_off.p, fg.succ_row_off.data(), fg.succ_row_off.size() * 4, hipMemcpyHostToDevice));
+    if (!fg.succ_rows.empty()) HIP_TRY(hipMemcpy(b->d_succ_rows.p, fg.succ_rows.data(), fg.succ_rows.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_dist_min.p, fg.dist_min.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_dist_max.p, fg.dist_max.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_exit_idx.p, fg.exit_idx.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->d_nbm_off.p, fg.nbm_off.data(), (n + 1) * 4, hipMemcpyHostToDevice));
+    if (!fg.nbm.empty()) HIP_TRY(hipMemcpy(b->d_nbm.p, fg.nbm.data(), fg.nbm.size() * sizeof(FlatGraph::NodeBubble), hipMemcpyHostToDevice));
+    b->ex_tables_ready = true;
+    return POA_OK;
+}
+
 static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_config_t* cfg) {
     const FlatGraph& fg = b->graph->g;
     std::string err;
@@ -1433,36 +1480,7 @@ static int prepare_exact(poa_batch* b, const poa_costs_t* costs, const poa_confi
     const uint64_t need = slots * ((uint64_t)fg.n_exit * (wpn + swpn) * 8 + 3ull * n_prio * 4 + (uint64_t)stack_cap * 12 + (uint64_t)pool_cap * 16);
     if (need + (256ull << 20) > free_b + b->d_ex_pool.n * 16 + b->d_ex_head.n * 4 + b->d_ex_reached.n * 8)
         return fail(POA_ERR_OUT_OF_MEMORY, "exact replay workspace does not fit: create the batch with a smaller workspace_bytes (fewer queries per chunk) or lower queue_entries_per_cell");
-    if (!b->exact_ready) {
-        HIP_TRY(b->d_succ_off.alloc(fg.succ_row_off.size()));
-        HIP_TRY(b->d_succ_rows.alloc(std::max<size_t>(fg.succ_rows.size(), 1)));
-        HIP_TRY(b->d_dist_min.alloc(n)); HIP_TRY(b->d_dist_max.alloc(n)); HIP_TRY(b->d_exit_idx.alloc(n));
-        HIP_TRY(b->d_node_row.alloc(n)); HIP_TRY(b->d_sp_to_end.alloc(n));
-        HIP_TRY(b->d_ex_end.alloc(2 * (size_t)std::max<uint32_t>(b->n_queries, 1)));
-        HIP_TRY(hipMemcpy(b->d_node_row.p, fg.node_row.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_sp_to_end.p, fg.sp_to_end.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(b->d_ex_sym.alloc((size_t)n + 4));
-        {
-            std::vector<uint8_t> row_sym((size_t)n + 4, 0);
-            for (uint32_t r = 0; r < n; ++r) row_sym[r] = fg.rows[r].sym;
-            HIP_TRY(hipMemcpy(b->d_ex_sym.p, row_sym.data(), row_sym.size(), hipMemcpyHostToDevice));
-        }
-        HIP_TRY(b->d_nbm_off.alloc(n + 1)); HIP_TRY(b->d_nbm.alloc(std::max<size_t>(fg.nbm.size(), 1)));
-        if (!fg.row_rec.empty()) {
-            HIP_TRY(b->d_ex_rec.alloc(fg.row_rec.size()));
-            HIP_TRY(hipMemcpy(b->d_ex_rec.p, fg.row_rec.data(), fg.row_rec.size() * sizeof(FlatGraph::RowRec), hipMemcpyHostToDevice));
-        }
-        HIP_TRY(b->d_ex_status.alloc(std::max<uint32_t>(b->n_queries, 1)));
-        HIP_TRY(b->d_ex_counters.alloc(4 * (size_t)std::max<uint32_t>(b->n_queries, 1)));
-        HIP_TRY(b->d_ex_prof.alloc(8 * (size_t)std::max<uint32_t>(b->n_queries, 1)));   // (diagnostics; once, not per chunk while a kernel may write it)
-        HIP_TRY(hipMemcpy(b->d_succ_off.p, fg.succ_row_off.data(), fg.succ_row_off.size() * 4, hipMemcpyHostToDevice));
-        if (!fg.succ_rows.empty()) HIP_TRY(hipMemcpy(b->d_succ_rows.p, fg.succ_rows.data(), fg.succ_rows.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_dist_min.p, fg.dist_min.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_dist_max.p, fg.dist_max.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_exit_idx.p, fg.exit_idx.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->d_nbm_off.p, fg.nbm_off.data(), (n + 1) * 4, hipMemcpyHostToDevice));
-        if (!fg.nbm.empty()) HIP_TRY(hipMemcpy(b->d_nbm.p, fg.nbm.data(), fg.nbm.size() * sizeof(FlatGraph::NodeBubble), hipMemcpyHostToDevice));
-    }
+    if (const int trc = prepare_exact_tables(b)) return trc;
     HIP_TRY(b->d_ex_reached.alloc(std::max<uint64_t>(slots * fg.n_exit * wpn, 1)));
     HIP_TRY(b->d_ex_rsum.alloc(std::max<uint64_t>(slots * fg.n_exit * swpn, 1)));
     HIP_TRY(b->d_ex_head.alloc(slots * 3 * n_prio));
@@ -1727,7 +1745,8 @@ int poa_batch_fetch(poa_batch_t* b, uint32_t* score, poa_aln_pair_t* pairs, uint
             for (uint32_t i = 0; i < n; ++i) nf += fl[i] != 0;
             stats->n_flagged = nf;
         }
-        if (stats && (b->last_mode == POA_MODE_EXACT || b->last_mode == POA_MODE_HYBRID)) {
+        if (stats && b->two_piece && b->last_mode != POA_MODE_DENSE) n_exact = n;   // (the two-piece replay searches for every query)
+        else if (stats && (b->last_mode == POA_MODE_EXACT || b->last_mode == POA_MODE_HYBRID)) {
             std::vector<uint32_t> stt(n);
             HIP_TRY(hipMemcpy(stt.data(), b->d_ex_status.p, (size_t)n * 4, hipMemcpyDeviceToHost));
             uint32_t ne = 0;
@@ -1937,10 +1956,11 @@ int poa_batch_fetch_compact(poa_batch_t* b, uint32_t query, uint16_t* m_raw, uin
     return POA_OK;
 }
 
-// ---- two-piece model on a resident batch (kernels: poa_twopiece.hpp with TwoPieceBatchParams) ------------------------------------
+// ---- two-piece model on a resident batch (kernels: poa_twopiece.hpp) ---------------------------------------------------------------
 // The u32 plan of the two-piece pass, cut on the first u32 run: five planes of 4-byte cells per query.  The batch's workspace
 // was sized for three; it is replaced by a larger one only if the longest query's five planes do not fit it.
-static int prepare_two_piece_u32(poa_batch* b) {
+// max_count: queries per chunk at most; the two-piece replay alone passes one (build_chunk_plan).
+static int prepare_two_piece_u32(poa_batch* b, uint32_t max_count = ~0u) {
     const uint32_t rows = b->graph->g.n, n = b->n_queries;
     uint64_t biggest = 0;
     for (uint32_t i = 0; i < n; ++i) biggest = std::max<uint64_t>(biggest, 5ull * rows * b->h_pitch[i] * 4);
@@ -1957,7 +1977,7 @@ static int prepare_two_piece_u32(poa_batch* b) {
     }
     poa_batch::Plan& pl = b->plan[3];
     try {
-        build_chunk_plan(pl, n, ws, 4, [&](uint32_t i) { return 5ull * rows * b->h_pitch[i]; });
+        build_chunk_plan(pl, n, ws, 4, [&](uint32_t i) { return 5ull * rows * b->h_pitch[i]; }, max_count);
     } catch (const std::bad_alloc&) { pl.chunks.clear(); return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed"); }
     if (pl.d_off.alloc(n) != hipSuccess) { pl.chunks.clear(); return fail(POA_ERR_OUT_OF_MEMORY, "two-piece u32 plan: device allocation failed"); }
     if (hipMemcpy(pl.d_off.p, pl.off.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) { pl.chunks.clear(); return fail(POA_ERR_HIP, "two-piece u32 plan: upload failed"); }
@@ -2015,6 +2035,138 @@ static int run_ckpt2(poa_batch* b, const poa_costs2_t* costs, hipStream_t stream
     return run.end_pairs();
 }
 
+// the parameter block of the two-piece kernels over the batch's active plan: u32 planes, no replay; a run sets what differs
+static TwoPieceParams two_piece_params(poa_batch* b, const poa_costs2_t* costs) {
+    const FlatGraph& fg = b->graph->g;
+    TwoPieceParams P;
+    P.rows = b->d_rows.p; P.pred_rows = b->d_pred_rows.p; P.n_rows = fg.n; P.start_row = fg.start_row; P.end_row = fg.end_row;
+    P.qseq = b->d_qseq.p; P.qoff = b->d_qoff.p; P.first_query = 0; P.n_queries = 0;
+    P.planes = b->d_planes.p; P.q_pitch = b->d_pitch.p; P.plane_off = b->cur().d_off.p; P.off_scale = 1u;
+    P.x = costs->mismatch; P.o1 = costs->gap_open1; P.e1 = costs->gap_extend1; P.e2 = costs->gap_extend2;
+    P.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
+    P.score = b->d_score.p; P.flags = b->d_flags.p; P.n_pairs = b->d_npairs.p;
+    P.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p); P.scratch_off = b->d_scratch_off.p;
+    P.exact_pass = 0; P.ex_status = nullptr; P.ex_end = nullptr;
+    return P;
+}
+
+// ---- the replay of the reference's two-piece search (mode EXACT / HYBRID of poa_align_batch_2piece_ex) ---------------------------
+// What one search holds besides its five u32 planes: prepare_exact's sizes with five stacks per priority; the pool holds the
+// entries live at once - popped slots are reused - at cfg->queue_entries_per_cell entries per cell, default 0.5.  The refusals
+// need no device.
+struct Replay2Sizes {
+    uint32_t n_prio, pool_cap, stack_cap, wpn, swpn;
+    uint64_t slot_bytes;
+};
+static int replay2_sizes(const poa_graph_t* g, uint64_t max_len, const poa_costs2_t* costs, const poa_config_t* cfg, Replay2Sizes& z) {
+    const FlatGraph& fg = g->g;
+    if (5ull * fg.n * ((max_len + 64) & ~63ull) >= (1ull << 32))
+        return fail(POA_ERR_UNSUPPORTED, "two-piece replay: the visited table of one query exceeds 2^32 cells");
+    std::string err;
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(const_cast<poa_graph*>(g)->bubble_mu);
+        rc = build_bubble_index(const_cast<FlatGraph&>(fg), err);
+    }
+    if (rc != POA_OK) return fail(rc, err);
+    const uint32_t om = std::max<uint32_t>(costs->gap_open1, costs->gap_open2);
+    const uint32_t maxc = std::max<uint32_t>(costs->mismatch, om + costs->gap_extend1);
+    const uint64_t n_prio64 = ((uint64_t)fg.n + max_len + 2) * maxc + 2ull * (om + ((uint64_t)fg.n + max_len) * costs->gap_extend1) + 64;
+    if (n_prio64 > (1ull << 26)) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: priority range too large for this graph / query size");
+    const float f = (cfg->queue_entries_per_cell > 0.f) ? cfg->queue_entries_per_cell : 0.5f;
+    const uint64_t pool64 = std::max<uint64_t>(1024, (uint64_t)(f * (double)fg.n * (double)(max_len + 1)));
+    if (pool64 > 0xFFFFFFF0ull) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: queue pool too large");
+    z.n_prio = (uint32_t)n_prio64; z.pool_cap = (uint32_t)pool64; z.stack_cap = (uint32_t)(fg.n + max_len + 8);
+    z.wpn = (uint32_t)((max_len + 1 + 63) / 64); z.swpn = (z.wpn + 63) / 64;
+    z.slot_bytes = (uint64_t)fg.n_exit * (z.wpn + z.swpn) * 8 + 5ull * z.n_prio * 4 + (uint64_t)z.stack_cap * 12 + (uint64_t)z.pool_cap * 16;
+    return POA_OK;
+}
+
+// The graph tables, the u32 plan of five planes with at most max_slots queries per chunk, and the search workspace of the
+// largest chunk in the batch's replay buffers.
+static int prepare_replay2(poa_batch* b, const Replay2Sizes& z, uint32_t max_slots) {
+    const FlatGraph& fg = b->graph->g;
+    if (const int rc = prepare_exact_tables(b)) return rc;
+    if (const int rc = prepare_two_piece_u32(b, max_slots)) return rc;
+    const uint64_t slots = b->plan[3].max_chunk;
+    HIP_TRY(b->d_ex_reached.alloc(std::max<uint64_t>(slots * fg.n_exit * z.wpn, 1)));
+    HIP_TRY(b->d_ex_rsum.alloc(std::max<uint64_t>(slots * fg.n_exit * z.swpn, 1)));
+    HIP_TRY(b->d_ex_head.alloc(slots * 5 * z.n_prio));
+    HIP_TRY(b->d_ex_stack.alloc(slots * z.stack_cap));
+    if (b->d_ex_pool.alloc(slots * z.pool_cap) != hipSuccess) return fail(POA_ERR_OUT_OF_MEMORY, "two-piece replay: queue pool");
+    b->ex_n_prio = z.n_prio; b->ex_pool_cap = z.pool_cap; b->ex_stack_cap = z.stack_cap; b->ex_wpn = z.wpn; b->ex_swpn = z.swpn;
+    b->exact_ready = false;   // (the shared buffers now have the two-piece sizes)
+    return POA_OK;
+}
+
+// The replay for EVERY query of a batch created for the dense pass: per chunk the search (poa2_exact_kernel) into tables that
+// start unvisited, then the walk from the cell each search stopped at; scan and compaction of the pairs as in dense mode.
+// Reached by the one-shot call alone (poa_batch_run_2piece refuses the mode): a fresh batch with queries, which runs once.
+static int run_replay2(poa_batch* b, const poa_costs2_t* costs, const poa_config_t* cfg, const TuneView& T, const Replay2Sizes& z,
+                       uint32_t max_slots, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(b->device));
+    const FlatGraph& fg = b->graph->g;
+    RunFrame run;
+    if (const int rc = run.open(b, "poa_batch_run: call poa_batch_stats/fetch at least every 256 runs")) return rc;
+    if (const int rc = prepare_replay2(b, z, max_slots)) return rc;
+    if (const int rc = run.begin(stream, b->plan[3].chunks.size())) return rc;
+    b->last_mode = cfg->mode;
+    b->two_piece = true;
+    set_layout(b, false);
+    b->active_plan = 3;
+    const poa_batch::Plan& PL = b->cur();
+    TwoPieceParams P = two_piece_params(b, costs);
+    P.exact_pass = 1; P.ex_status = b->d_ex_status.p; P.ex_end = b->d_ex_end.p;
+    TwoPieceExact X;
+    X.G = ExactGraph{fg.n, fg.start_row, fg.end_row, b->d_ex_sym.p, b->d_succ_off.p, b->d_succ_rows.p, b->d_dist_min.p, b->d_dist_max.p,
+                     b->d_exit_idx.p, fg.n_exit, b->d_nbm_off.p, b->d_nbm.p, b->d_node_row.p, b->d_sp_to_end.p, nullptr};
+    X.C = ExactCosts{costs->mismatch, costs->gap_open1, costs->gap_extend1, cfg->heuristic, cfg->pruning, 0, 0, 0, 0, 0, 0,
+                     costs->gap_open2, costs->gap_extend2};
+    if (cfg->span == POA_SPAN_ENDS_FREE) {
+        X.C.ends_free = 1;
+        X.C.qfe_kind = cfg->qry_free_end.kind; X.C.qfe_val = cfg->qry_free_end.value;
+        X.C.gfb_kind = cfg->graph_free_begin.kind;
+        X.C.gfe_kind = cfg->graph_free_end.kind; X.C.gfe_val = cfg->graph_free_end.value;
+    }
+    X.reached = b->d_ex_reached.p; X.rsum = b->d_ex_rsum.p; X.wpn = b->ex_wpn; X.swpn = b->ex_swpn;
+    X.head = b->d_ex_head.p; X.n_prio = b->ex_n_prio; X.pool = b->d_ex_pool.p; X.pool_cap = b->ex_pool_cap;
+    X.stack = b->d_ex_stack.p; X.stack_cap = b->ex_stack_cap;
+    X.status = b->d_ex_status.p; X.end_cell = b->d_ex_end.p; X.counters = b->d_ex_counters.p;
+    X.n_succ = (uint32_t)fg.succ_rows.size(); X.n_nbm = (uint32_t)fg.nbm.size();
+    for (const auto& ch : PL.chunks) {
+        P.first_query = ch.first; P.n_queries = ch.count;
+        // the search fills its table from nothing: unvisited planes (a chunk's regions lie back to back from the start of the
+        // workspace, build_chunk_plan), empty stacks, empty reached sets
+        const uint32_t last = ch.first + ch.count - 1;
+        HIP_TRY(hipMemsetAsync(b->d_planes.p, 0xFF, (PL.off[last] + 5ull * fg.n * b->h_pitch[last]) * 4, stream));
+        HIP_TRY(hipMemsetAsync(b->d_ex_head.p, 0xFF, (size_t)ch.count * 5 * b->ex_n_prio * 4, stream));
+        if (fg.n_exit) {
+            HIP_TRY(hipMemsetAsync(b->d_ex_reached.p, 0, (size_t)ch.count * fg.n_exit * b->ex_wpn * 8, stream));
+            HIP_TRY(hipMemsetAsync(b->d_ex_rsum.p, 0, (size_t)ch.count * fg.n_exit * b->ex_swpn * 8, stream));
+        }
+        // active lanes per wave: enough waves to fill the chip first (one divergent search per lane), then more lanes
+        uint32_t lanes = (ch.count + 8191) / 8192;
+        if (lanes > 64) lanes = 64;
+        if (const int* lv = T.ptr(POA_TUNE_EXACT_LANES)) { const int v = (*lv); if (v >= 1 && v <= 64) lanes = (uint32_t)v; }
+        X.lanes_per_wave = lanes;
+        // graph arrays in LDS when they fit (one copy per block of 16 waves)
+        const uint32_t lds_bytes = exact_lds_bytes(fg.n, X.n_succ, X.n_nbm);
+        bool lds_graph = lds_bytes <= 150u * 1024u;
+        if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) lds_graph = lds_graph && (*gv) != 0;
+        if (lds_graph && lds_bytes > 48u * 1024u)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(poa2_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        X.lds_graph = lds_graph ? 1u : 0u;
+        const uint32_t per_block = lanes * (EXACT2_BLOCK / 64);
+        hipLaunchKernelGGL(poa2_exact_kernel, dim3((ch.count + per_block - 1) / per_block), dim3(EXACT2_BLOCK), lds_graph ? lds_bytes : 0, stream, P, X);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        hipLaunchKernelGGL(poa2_traceback_kernel<uint32_t>, dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark(2)) return rc;
+    }
+    return run.end_pairs();
+}
+
 int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!b || !costs) return fail(POA_ERR_INVALID_ARG, "poa_batch_run_2piece: null argument");
     const uint32_t mode = cfg ? cfg->mode : POA_MODE_DENSE;
@@ -2060,24 +2212,17 @@ int poa_batch_run_2piece(poa_batch_t* b, const poa_costs2_t* costs, const poa_co
     b->active_plan = plan;
     const poa_batch::Plan& PL = b->cur();
     if (b->n_queries == 0) return run.end_empty(true);
-    TwoPieceBatchParams P;
-    P.rows = b->d_rows.p; P.pred_rows = b->d_pred_rows.p; P.n_rows = fg.n; P.start_row = fg.start_row; P.end_row = fg.end_row;
-    P.qseq = b->d_qseq.p; P.qoff = b->d_qoff.p; P.pitch = 0; P.planes = b->d_planes.p;
-    P.x = costs->mismatch; P.o1 = costs->gap_open1; P.e1 = costs->gap_extend1; P.e2 = costs->gap_extend2;
-    P.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
-    P.score = b->d_score.p; P.flags = b->d_flags.p; P.n_pairs = b->d_npairs.p;
-    P.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p); P.scratch_stride = 0;
-    P.exact_pass = 0; P.ex_status = nullptr; P.ex_end = nullptr;
-    P.q_pitch = b->d_pitch.p; P.plane_off = PL.d_off.p; P.off_scale = narrow ? 2u : 1u; P.scratch_off = b->d_scratch_off.p;
+    TwoPieceParams P = two_piece_params(b, costs);
+    P.off_scale = narrow ? 2u : 1u;
     for (const auto& ch : PL.chunks) {
         P.first_query = ch.first; P.n_queries = ch.count;
-        // one wave per query, previous row in registers for up to 1024 columns: the launch shapes of run_two_piece
-        if (narrow) hipLaunchKernelGGL((poa2_forward_kernel<uint16_t, 2, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
-        else hipLaunchKernelGGL((poa2_forward_kernel<uint32_t, 4, TwoPieceBatchParams>), dim3(ch.count), dim3(64), 0, stream, P);
+        // one wave per query, previous row in registers for up to 1024 columns (u16: two passes of 512, u32: four of 256)
+        if (narrow) hipLaunchKernelGGL((poa2_forward_kernel<uint16_t, 2>), dim3(ch.count), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL((poa2_forward_kernel<uint32_t, 4>), dim3(ch.count), dim3(64), 0, stream, P);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark()) return rc;
-        if (narrow) hipLaunchKernelGGL((poa2_traceback_kernel<uint16_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
-        else hipLaunchKernelGGL((poa2_traceback_kernel<uint32_t, TwoPieceBatchParams>), dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
+        if (narrow) hipLaunchKernelGGL(poa2_traceback_kernel<uint16_t>, dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
+        else hipLaunchKernelGGL(poa2_traceback_kernel<uint32_t>, dim3((ch.count + 63) / 64), dim3(64), 0, stream, P);
         HIP_TRY(hipGetLastError());
         if (const int rc = run.mark(2)) return rc;
     }
@@ -2088,7 +2233,7 @@ int poa_batch_fetch_planes_2piece(poa_batch_t* b, uint32_t query, uint32_t* m, u
     if (!b || !m || !i1 || !d1 || !i2 || !d2) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: null argument");
     if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: bad query / not run");
     if (b->ckpt2) return fail(POA_ERR_UNSUPPORTED, "poa_batch_fetch_planes_2piece: a checkpointed batch keeps snapshots and one segment window, no score planes");
-    if (!b->two_piece) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the last run was not a dense two-piece run");
+    if (!b->two_piece || b->last_mode != POA_MODE_DENSE) return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the last run was not a dense two-piece run");
     const auto& last = b->cur().chunks.back();
     if (query < last.first || query >= last.first + last.count)
         return fail(POA_ERR_INVALID_ARG, "poa_batch_fetch_planes_2piece: the query's planes were overwritten by a later chunk");
@@ -2244,16 +2389,17 @@ void poa_release_cache(void) {
 }  // extern "C"
 
 
-// ---- two-piece affine model (poa_twopiece.hpp) ---------------------------------------------------------------------------
+// ---- two-piece affine model (poa_twopiece.hpp): the one-shot calls ------------------------------------------------------------
+// Like every one-shot call: the checks, then a batch, one run through its frame, fetch, destroy.  mode: DENSE = the dense
+// Global pass; EXACT / HYBRID = the replay of the reference's search for EVERY query (under this model a dense flag of 0
+// certifies the alignment only where the reference's search is optimal, and it need not be: DESIGN.md §6a - so there is no
+// cheaper hybrid).  fetch_extra(batch) reads what else the caller wants from a run that went well, before the results' fetch.
 namespace {
-// planes_out: null, or five host pointers (M, I1, D1, I2, D2) receiving the planes of query 0, rows x (len + 1)
-int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t n_queries, const uint8_t* qseq,
-                  const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags,
-                  poa_stats_t* stats, int device, uint32_t* const* planes_out, uint32_t* counters_out) {
+template <typename FetchExtra>
+int two_piece_one_shot(const poa_graph_t* g, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t n_queries, const uint8_t* qseq,
+                       const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags,
+                       poa_stats_t* stats, int device, FetchExtra&& fetch_extra) {
     if (!g || !costs || (n_queries && (!qseq || !qoff))) return fail(POA_ERR_INVALID_ARG, "poa_align_batch_2piece: null argument");
-    // mode: DENSE = the dense Global pass; EXACT / HYBRID = the replay of the reference's search for EVERY query (under this
-    // model a dense flag of 0 certifies the alignment only where the reference's search is optimal, and it need not be:
-    // DESIGN.md §6a — so there is no cheaper hybrid)
     const bool score_only = cfg && cfg->mode == POA_MODE_SCORE;
     const bool exact = cfg && cfg->mode != POA_MODE_DENSE && !score_only && cfg->mode != POA_MODE_CHECKPOINT2;
     if (cfg && cfg->mode == POA_MODE_CHECKPOINT) return fail(POA_ERR_UNSUPPORTED, "checkpointed mode: one-piece gap-affine model only");
@@ -2270,16 +2416,14 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
     if (costs->gap_extend1 < costs->gap_extend2)
         return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
     if (poa_device_count() <= 0) return fail(POA_ERR_NO_DEVICE, "no HIP device: the engine has no CPU alignment path");
-    HIP_TRY(hipSetDevice(device));
     const FlatGraph& fg = g->g;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (pair_off) pair_off[0] = 0;
     if (n_queries == 0) return POA_OK;
-    uint64_t max_len = 0, cells = 0;
+    uint64_t max_len = 0;
     for (uint32_t i = 0; i < n_queries; ++i) {
         if (qoff[i + 1] < qoff[i]) return fail(POA_ERR_INVALID_ARG, "qoff must be non-decreasing");
         max_len = std::max<uint64_t>(max_len, qoff[i + 1] - qoff[i]);
-        cells += (uint64_t)fg.n * (qoff[i + 1] - qoff[i] + 1);
     }
     if (fg.n_real == 0) {  // empty graph: mod.rs:124-142
         for (uint32_t i = 0; i < n_queries; ++i) {
@@ -2297,207 +2441,37 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
         return sweep_one_shot(g, costs->mismatch, (uint32_t)costs->gap_open1 + costs->gap_extend1 - costs->gap_extend2, costs->gap_extend2, cfg,
                               n_queries, qseq, qoff, score, pair_off, flags, stats, device);
     }
-    if (ckpt2) {
-        // one-shot checkpointed call: a batch sized from the plan's footprint, one run, everything the dense pass returns
-        poa_batch_t* cb = nullptr;
-        int crc = poa_batch_create_ex(g, device, n_queries, qseq, qoff, cfg, 0, &cb);
-        if (crc != POA_OK) return crc;
-        crc = poa_batch_run_2piece(cb, costs, cfg, nullptr);
-        if (crc == POA_OK) crc = poa_batch_fetch(cb, score, pairs, pair_off, pair_capacity, flags, stats);
-        poa_batch_destroy(cb);
-        return crc;
-    }
-    const uint32_t pitch = (uint32_t)((max_len + 64) & ~63ull);
-    const uint64_t per_query = 5ull * fg.n * pitch;   // plane elements
-    if (per_query >= (1ull << 34)) return fail(POA_ERR_UNSUPPORTED, "two-piece pass: planes of one query too large");
-    if (exact && per_query >= (1ull << 32)) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: the visited table of one query exceeds 2^32 cells");
-    // u16 planes under the bound of the one-piece pass taken with the first piece's costs (the replayed table is u32)
-    const bool narrow = u16_cells_suffice(costs->gap_open1, costs->gap_extend1, max_len, fg) && !costs->wide_planes && !exact;
-    const uint64_t elem = narrow ? 2 : 4;
-    // replay workspace per query slot (prepare_exact's sizes with five stacks per priority; the pool holds the entries live
-    // at once — popped slots are reused — at cfg->queue_entries_per_cell entries per cell, default 0.5)
-    uint32_t x_n_prio = 0, x_pool_cap = 0, x_stack_cap = 0, x_wpn = 0, x_swpn = 0;
-    uint64_t x_bytes = 0;
-    if (exact) {
-        std::string err;
-        int brc;
-        {
-            std::lock_guard<std::mutex> lk(const_cast<poa_graph*>(g)->bubble_mu);
-            brc = build_bubble_index(const_cast<FlatGraph&>(fg), err);
+    if (!ckpt2 && 5ull * fg.n * ((max_len + 64) & ~63ull) >= (1ull << 34)) return fail(POA_ERR_UNSUPPORTED, "two-piece pass: planes of one query too large");
+    Replay2Sizes z{};
+    if (exact)
+        if (const int rc = replay2_sizes(g, max_len, costs, cfg, z)) return rc;
+    // The workspace the batch is asked to hold (two_piece_workspace, poa_dense_plan.cpp), in the bytes per cell of pitch the run
+    // addresses: 20 for five u32 planes; a u16 run lives in the batch's 4-byte three-plane regions, 12, of which it uses 10.
+    // A checkpointed batch holds its own footprint.  (A device that cannot be asked is refused by the constructor.)
+    uint64_t ws_request = 0;
+    uint32_t max_slots = ~0u;
+    if (!ckpt2) {
+        const bool narrow = u16_cells_suffice(costs->gap_open1, costs->gap_extend1, max_len, fg) && !costs->wide_planes && !exact;
+        uint64_t total = 0, largest = 0;
+        for (uint32_t i = 0; i < n_queries; ++i) {
+            const uint64_t bytes = (narrow ? 12ull : 20ull) * fg.n * ((qoff[i + 1] - qoff[i] + 64) & ~63ull);
+            total += bytes; largest = std::max(largest, bytes);
         }
-        if (brc != POA_OK) return fail(brc, err);
-        const uint32_t om = std::max<uint32_t>(costs->gap_open1, costs->gap_open2);
-        const uint32_t maxc = std::max<uint32_t>(costs->mismatch, om + costs->gap_extend1);
-        const uint64_t n_prio64 = ((uint64_t)fg.n + max_len + 2) * maxc + 2ull * (om + ((uint64_t)fg.n + max_len) * costs->gap_extend1) + 64;
-        if (n_prio64 > (1ull << 26)) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: priority range too large for this graph / query size");
-        const float f = (cfg->queue_entries_per_cell > 0.f) ? cfg->queue_entries_per_cell : 0.5f;
-        const uint64_t pool64 = std::max<uint64_t>(1024, (uint64_t)(f * (double)fg.n * (double)(max_len + 1)));
-        if (pool64 > 0xFFFFFFF0ull) return fail(POA_ERR_UNSUPPORTED, "two-piece replay: queue pool too large");
-        x_n_prio = (uint32_t)n_prio64; x_pool_cap = (uint32_t)pool64; x_stack_cap = (uint32_t)(fg.n + max_len + 8);
-        x_wpn = (uint32_t)((max_len + 1 + 63) / 64); x_swpn = (x_wpn + 63) / 64;
-        x_bytes = (uint64_t)fg.n_exit * (x_wpn + x_swpn) * 8 + 5ull * x_n_prio * 4 + (uint64_t)x_stack_cap * 12 + (uint64_t)x_pool_cap * 16;
-    }
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // (the replay is bound by the latency of its dependent loads: as many searches in flight as the memory holds)
-    const uint64_t budget = exact ? (uint64_t)(free_b * 0.85) : std::min<uint64_t>((uint64_t)(free_b * 0.6), 64ull << 30);
-    uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_queries, budget / (per_query * elem + x_bytes + 1)));
-    const uint32_t stride = (uint32_t)std::min<uint64_t>(fg.n + max_len + 1, 0xFFFFFFFFull);
-    DevBuf<RowMeta> d_rows; DevBuf<uint32_t> d_pred, d_planes, d_score, d_flags, d_np; DevBuf<uint8_t> d_q; DevBuf<uint64_t> d_qoff;
-    DevBuf<poa_aln_pair_t> d_scratch;
-    HIP_TRY(d_rows.alloc(fg.rows.size())); HIP_TRY(d_pred.alloc(std::max<size_t>(fg.pred_rows.size(), 1)));
-    HIP_TRY(d_q.alloc(std::max<uint64_t>(qoff[n_queries], 1))); HIP_TRY(d_qoff.alloc(n_queries + 1));
-    HIP_TRY(d_score.alloc(n_queries)); HIP_TRY(d_flags.alloc(n_queries)); HIP_TRY(d_np.alloc(n_queries));
-    if (d_planes.alloc((size_t)((chunk * per_query * elem + 3) / 4)) != hipSuccess) return fail(POA_ERR_OUT_OF_MEMORY, "two-piece pass: plane workspace");
-    HIP_TRY(d_scratch.alloc((size_t)chunk * stride));
-    // the replay's view of the graph and its workspace
-    DevBuf<uint32_t> x_succ_off, x_succ, x_dmin, x_dmax, x_exit, x_nbm_off, x_node_row, x_sp, x_head, x_status, x_end, x_counters;
-    DevBuf<uint8_t> x_sym; DevBuf<FlatGraph::NodeBubble> x_nbm; DevBuf<uint64_t> x_reached, x_rsum;
-    DevBuf<ExQEntry> x_pool; DevBuf<ExStackEntry> x_stack;
-    TwoPieceExact X;
-    if (exact) {
-        const uint32_t n = fg.n;
-        HIP_TRY(x_succ_off.alloc(fg.succ_row_off.size())); HIP_TRY(x_succ.alloc(std::max<size_t>(fg.succ_rows.size(), 1)));
-        HIP_TRY(x_dmin.alloc(n)); HIP_TRY(x_dmax.alloc(n)); HIP_TRY(x_exit.alloc(n)); HIP_TRY(x_nbm_off.alloc(n + 1));
-        HIP_TRY(x_nbm.alloc(std::max<size_t>(fg.nbm.size(), 1))); HIP_TRY(x_node_row.alloc(n)); HIP_TRY(x_sp.alloc(n)); HIP_TRY(x_sym.alloc((size_t)n + 4));
-        std::vector<uint8_t> row_sym((size_t)n + 4, 0);
-        for (uint32_t r = 0; r < n; ++r) row_sym[r] = fg.rows[r].sym;
-        HIP_TRY(hipMemcpy(x_sym.p, row_sym.data(), row_sym.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_succ_off.p, fg.succ_row_off.data(), fg.succ_row_off.size() * 4, hipMemcpyHostToDevice));
-        if (!fg.succ_rows.empty()) HIP_TRY(hipMemcpy(x_succ.p, fg.succ_rows.data(), fg.succ_rows.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_dmin.p, fg.dist_min.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_dmax.p, fg.dist_max.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_exit.p, fg.exit_idx.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_nbm_off.p, fg.nbm_off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
-        if (!fg.nbm.empty()) HIP_TRY(hipMemcpy(x_nbm.p, fg.nbm.data(), fg.nbm.size() * sizeof(FlatGraph::NodeBubble), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_node_row.p, fg.node_row.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(x_sp.p, fg.sp_to_end.data(), n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(x_reached.alloc(std::max<uint64_t>((uint64_t)chunk * fg.n_exit * x_wpn, 1)));
-        HIP_TRY(x_rsum.alloc(std::max<uint64_t>((uint64_t)chunk * fg.n_exit * x_swpn, 1)));
-        HIP_TRY(x_head.alloc((size_t)chunk * 5 * x_n_prio)); HIP_TRY(x_stack.alloc((size_t)chunk * x_stack_cap));
-        if (x_pool.alloc((size_t)chunk * x_pool_cap) != hipSuccess) return fail(POA_ERR_OUT_OF_MEMORY, "two-piece replay: queue pool");
-        HIP_TRY(x_status.alloc(n_queries)); HIP_TRY(x_end.alloc(2 * (size_t)n_queries)); HIP_TRY(x_counters.alloc(4 * (size_t)n_queries));
-        X.G = ExactGraph{n, fg.start_row, fg.end_row, x_sym.p, x_succ_off.p, x_succ.p, x_dmin.p, x_dmax.p, x_exit.p, fg.n_exit,
-                         x_nbm_off.p, x_nbm.p, x_node_row.p, x_sp.p, nullptr};
-        X.C = ExactCosts{costs->mismatch, costs->gap_open1, costs->gap_extend1, cfg->heuristic, cfg->pruning, 0, 0, 0, 0, 0, 0,
-                         costs->gap_open2, costs->gap_extend2};
-        if (ends_free) {
-            X.C.ends_free = 1;
-            X.C.qfe_kind = cfg->qry_free_end.kind; X.C.qfe_val = cfg->qry_free_end.value;
-            X.C.gfb_kind = cfg->graph_free_begin.kind;
-            X.C.gfe_kind = cfg->graph_free_end.kind; X.C.gfe_val = cfg->graph_free_end.value;
-        }
-        X.reached = x_reached.p; X.rsum = x_rsum.p; X.wpn = x_wpn; X.swpn = x_swpn;
-        X.head = x_head.p; X.n_prio = x_n_prio; X.pool = x_pool.p; X.pool_cap = x_pool_cap;
-        X.stack = x_stack.p; X.stack_cap = x_stack_cap;
-        X.status = x_status.p; X.end_cell = x_end.p; X.counters = x_counters.p;
-    }
-    HIP_TRY(hipMemcpy(d_rows.p, fg.rows.data(), fg.rows.size() * sizeof(RowMeta), hipMemcpyHostToDevice));
-    if (!fg.pred_rows.empty()) HIP_TRY(hipMemcpy(d_pred.p, fg.pred_rows.data(), fg.pred_rows.size() * 4, hipMemcpyHostToDevice));
-    if (qoff[n_queries]) HIP_TRY(hipMemcpy(d_q.p, qseq, qoff[n_queries], hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_qoff.p, qoff, ((size_t)n_queries + 1) * 8, hipMemcpyHostToDevice));
-    TwoPieceParams P;
-    P.rows = d_rows.p; P.pred_rows = d_pred.p; P.n_rows = fg.n; P.start_row = fg.start_row; P.end_row = fg.end_row;
-    P.qseq = d_q.p; P.qoff = d_qoff.p; P.pitch = pitch; P.planes = d_planes.p;
-    P.x = costs->mismatch; P.o1 = costs->gap_open1; P.e1 = costs->gap_extend1; P.e2 = costs->gap_extend2; P.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
-    P.score = d_score.p; P.flags = d_flags.p; P.n_pairs = d_np.p; P.scratch = d_scratch.p; P.scratch_stride = stride;
-    P.exact_pass = exact ? 1u : 0u; P.ex_status = x_status.p; P.ex_end = x_end.p;
-    struct Events {   // destroyed on every way out
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() { for (auto ev : e) if (ev) (void)hipEventDestroy(ev); }
-    } evs;
-    for (auto& ev : evs.e) HIP_TRY(hipEventCreate(&ev));
-    hipEvent_t &e0 = evs.e[0], &e1 = evs.e[1], &e2 = evs.e[2];
-    float ms_f = 0.f, ms_t = 0.f;
-    std::vector<uint32_t> h_np(n_queries), h_flags(n_queries);
-    std::vector<poa_aln_pair_t> h_scratch((size_t)chunk * stride);
-    uint64_t at = 0;
-    uint32_t n_chunks = 0;
-    int rc = POA_OK;
-    for (uint32_t first = 0; first < n_queries; first += chunk) {
-        const uint32_t cnt = std::min(chunk, n_queries - first);
-        P.first_query = first; P.n_queries = cnt;
-        HIP_TRY(hipEventRecord(e0, nullptr));
-        if (exact) {
-            // the search fills its table from nothing: unvisited planes, empty stacks, empty reached sets
-            HIP_TRY(hipMemsetAsync(d_planes.p, 0xFF, (size_t)cnt * per_query * 4, nullptr));
-            HIP_TRY(hipMemsetAsync(x_head.p, 0xFF, (size_t)cnt * 5 * x_n_prio * 4, nullptr));
-            if (fg.n_exit) {
-                HIP_TRY(hipMemsetAsync(x_reached.p, 0, (size_t)cnt * fg.n_exit * x_wpn * 8, nullptr));
-                HIP_TRY(hipMemsetAsync(x_rsum.p, 0, (size_t)cnt * fg.n_exit * x_swpn * 8, nullptr));
-            }
-            // active lanes per wave: enough waves to fill the chip first (one divergent search per lane), then more lanes
-            uint32_t lanes = (cnt + 8191) / 8192;
-            if (lanes > 64) lanes = 64;
-            if (const int* lv = T.ptr(POA_TUNE_EXACT_LANES)) { const int v = (*lv); if (v >= 1 && v <= 64) lanes = (uint32_t)v; }
-            X.lanes_per_wave = lanes;
-            // graph arrays in LDS when they fit (one copy per block of 16 waves)
-            X.n_succ = (uint32_t)fg.succ_rows.size(); X.n_nbm = (uint32_t)fg.nbm.size();
-            const uint32_t lds_bytes = exact_lds_bytes(fg.n, X.n_succ, X.n_nbm);
-            bool lds_graph = lds_bytes <= 150u * 1024u;
-            if (const int* gv = T.ptr(POA_TUNE_EXACT_LDS)) lds_graph = lds_graph && (*gv) != 0;
-            if (lds_graph && lds_bytes > 48u * 1024u)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(poa2_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            X.lds_graph = lds_graph ? 1u : 0u;
-            const uint32_t per_block = lanes * (EXACT2_BLOCK / 64);
-            hipLaunchKernelGGL(poa2_exact_kernel, dim3((cnt + per_block - 1) / per_block), dim3(EXACT2_BLOCK), lds_graph ? lds_bytes : 0, nullptr, P, X);
-        }
-        // previous row in registers for up to 1024 (u16: two passes of 512) / 1024 (u32: four passes of 256) columns
-        else if (narrow) hipLaunchKernelGGL((poa2_forward_kernel<uint16_t, 2>), dim3(cnt), dim3(64), 0, nullptr, P);
-        else hipLaunchKernelGGL((poa2_forward_kernel<uint32_t, 4>), dim3(cnt), dim3(64), 0, nullptr, P);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, nullptr));
-        if (narrow) hipLaunchKernelGGL(poa2_traceback_kernel<uint16_t>, dim3((cnt + 63) / 64), dim3(64), 0, nullptr, P);
-        else hipLaunchKernelGGL(poa2_traceback_kernel<uint32_t>, dim3((cnt + 63) / 64), dim3(64), 0, nullptr, P);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e2, nullptr));
-        HIP_TRY(hipEventSynchronize(e2));
-        float a = 0, b2 = 0;
-        (void)hipEventElapsedTime(&a, e0, e1); (void)hipEventElapsedTime(&b2, e1, e2);
-        ms_f += a; ms_t += b2; n_chunks++;
-        HIP_TRY(hipMemcpy(h_np.data() + first, d_np.p + first, (size_t)cnt * 4, hipMemcpyDeviceToHost));
-        if (pairs || pair_off) {
-            HIP_TRY(hipMemcpy(h_scratch.data(), d_scratch.p, (size_t)cnt * stride * sizeof(poa_aln_pair_t), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < cnt; ++i) {
-                const uint32_t np = h_np[first + i];
-                if (np > stride) return fail(POA_ERR_HIP, "two-piece traceback: walk longer than rows + length");
-                if (pairs) {
-                    if (at + np > pair_capacity) rc = fail(POA_ERR_CAPACITY, "pair_capacity too small");
-                    else std::memcpy(pairs + at, h_scratch.data() + (size_t)i * stride + (stride - np), (size_t)np * sizeof(poa_aln_pair_t));
-                }
-                at += np;
-                if (pair_off) pair_off[first + i + 1] = at;
-            }
-        }
-        if (planes_out && first == 0) {
-            const uint32_t L0 = (uint32_t)(qoff[1] - qoff[0]);
-            std::vector<uint32_t> row(pitch);
-            std::vector<uint16_t> row16(pitch);
-            for (int pl = 0; pl < 5; ++pl)
-                for (uint32_t r = 0; r < fg.n; ++r) {
-                    const uint64_t at_el = ((uint64_t)pl * fg.n + r) * pitch;
-                    if (narrow) {
-                        HIP_TRY(hipMemcpy(row16.data(), reinterpret_cast<const uint16_t*>(d_planes.p) + at_el, (size_t)pitch * 2, hipMemcpyDeviceToHost));
-                        for (uint32_t c = 0; c < pitch; ++c) row[c] = row16[c] == 0xFFFFu ? 0xFFFFFFFFu : row16[c];
-                    } else {
-                        HIP_TRY(hipMemcpy(row.data(), d_planes.p + at_el, (size_t)pitch * 4, hipMemcpyDeviceToHost));
-                    }
-                    std::memcpy(planes_out[pl] + (size_t)r * (L0 + 1), row.data(), ((size_t)L0 + 1) * 4);
-                }
+        size_t free_b = 0, total_b = 0;
+        if (hipSetDevice(device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // a parked workspace counts as free for the dense pass, whose batch takes it over or frees it; the replay's search
+            // workspaces come out of what is free now, so its budget counts that alone
+            const TwoPieceWorkspace w = two_piece_workspace(free_b + (exact ? 0 : parked_workspace_bytes(device)), total, largest, z.slot_bytes, exact);
+            ws_request = w.bytes; max_slots = w.max_slots;
         }
     }
-    if (score) HIP_TRY(hipMemcpy(score, d_score.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-    if (exact && counters_out) HIP_TRY(hipMemcpy(counters_out, x_counters.p, (size_t)n_queries * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_flags.data(), d_flags.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost));
-    if (flags) std::memcpy(flags, h_flags.data(), (size_t)n_queries * 4);
-    if (stats) {
-        stats->cells = cells; stats->bases = qoff[n_queries]; stats->plane_bytes = cells * 5 * elem; stats->n_queries = n_queries;
-        stats->n_chunks = n_chunks; stats->n_forward_launches = n_chunks; stats->ms_forward = ms_f; stats->ms_traceback = ms_t;
-        uint32_t nf = 0;
-        for (uint32_t i = 0; i < n_queries; ++i) nf += h_flags[i] != 0;
-        stats->n_flagged = nf;
-        if (exact) { stats->n_exact = n_queries; stats->ms_exact = ms_f; stats->ms_forward = 0; }
-    }
+    poa_batch_t* b = nullptr;
+    int rc = ckpt2 ? poa_batch_create_ex(g, device, n_queries, qseq, qoff, cfg, 0, &b) : poa_batch_create(g, device, n_queries, qseq, qoff, ws_request, &b);
+    if (rc != POA_OK) return rc;
+    rc = exact ? run_replay2(b, costs, cfg, T, z, max_slots, nullptr) : poa_batch_run_2piece(b, costs, cfg, nullptr);
+    if (rc == POA_OK) rc = fetch_extra(b);   // (before the fetch: a pair_capacity that is too small keeps nothing else back)
+    if (rc == POA_OK) rc = poa_batch_fetch(b, score, pairs, pair_off, pair_capacity, flags, stats);
+    poa_batch_destroy(b);
     return rc;
 }
 }  // namespace
@@ -2505,24 +2479,27 @@ int run_two_piece(const poa_graph_t* g, const poa_costs2_t* costs, const poa_con
 int poa_align_batch_2piece(const poa_graph_t* g, const poa_costs2_t* costs, uint32_t n_queries, const uint8_t* qseq,
                            const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off,
                            uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
-    return run_two_piece(g, costs, nullptr, n_queries, qseq, qoff, score, pairs, pair_off, pair_capacity, flags, stats, device, nullptr, nullptr);
+    return two_piece_one_shot(g, costs, nullptr, n_queries, qseq, qoff, score, pairs, pair_off, pair_capacity, flags, stats, device,
+                              [](poa_batch_t*) { return POA_OK; });
 }
 
 int poa_align_batch_2piece_ex(const poa_graph_t* g, const poa_costs2_t* costs, const poa_config_t* cfg, uint32_t n_queries,
                               const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs, uint64_t* pair_off,
                               uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, uint32_t* search_counters, int device) {
-    return run_two_piece(g, costs, cfg, n_queries, qseq, qoff, score, pairs, pair_off, pair_capacity, flags, stats, device, nullptr, search_counters);
+    return two_piece_one_shot(g, costs, cfg, n_queries, qseq, qoff, score, pairs, pair_off, pair_capacity, flags, stats, device, [&](poa_batch_t* b) {
+        const bool replayed = b->two_piece && b->last_mode != POA_MODE_DENSE;
+        return replayed && search_counters ? poa_batch_fetch_search_counters(b, search_counters) : POA_OK;
+    });
 }
 
+// the five planes of one query: a batch of one, one dense run, the planes of its last (only) chunk
 int poa_planes_2piece(const poa_graph_t* g, const poa_costs2_t* costs, const uint8_t* seq, uint32_t len, uint32_t* m,
                       uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2, int device) {
     if (!m || !i1 || !d1 || !i2 || !d2) return fail(POA_ERR_INVALID_ARG, "poa_planes_2piece: null plane");
     const uint64_t qoff[2] = {0, len};
-    uint32_t* out[5] = {m, i1, d1, i2, d2};
-    uint32_t sc = 0, fl = 0;
-    return run_two_piece(g, costs, nullptr, 1, seq, qoff, &sc, nullptr, nullptr, 0, &fl, nullptr, device, out, nullptr);
+    return two_piece_one_shot(g, costs, nullptr, 1, seq, qoff, nullptr, nullptr, nullptr, 0, nullptr, nullptr, device,
+                              [&](poa_batch_t* b) { return poa_batch_fetch_planes_2piece(b, 0, m, i1, d1, i2, d2); });
 }
-
 
 // ---- multi-graph checkpointed batch (poa_multi.hpp, poa_multi_plan.hpp) -----------------------------------------------------
 // The batch's buffers, events, fetch and statistics are those of a poa_batch (`core`, no graph of its own): poa_batch_fetch,

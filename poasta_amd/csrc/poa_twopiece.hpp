@@ -23,6 +23,8 @@
 
 namespace poa_amd {
 
+// Every query has its own pitch, its planes at plane_off[qi] of the batch's workspace and its pairs at scratch_off[qi] of the
+// batch's scratch, as the one-piece kernels take them (FwdParams / TbParams).
 struct TwoPieceParams {
     const RowMeta* rows;
     const uint32_t* pred_rows;
@@ -30,53 +32,34 @@ struct TwoPieceParams {
     const uint8_t* qseq;
     const uint64_t* qoff;
     uint32_t first_query, n_queries;   // chunk
-    uint32_t pitch;                    // columns per row (multiple of 64), same for the whole chunk
-    uint32_t* planes;                  // per slot: [5][n_rows][pitch] of the kernel's plane type (u32, or u16 when every score that matters fits): M, I1, D1, I2, D2
+    uint32_t* planes;                  // per query: [5][n_rows][pitch] of the kernel's plane type (u32, or u16 when every score that matters fits): M, I1, D1, I2, D2
+    const uint32_t* q_pitch;           // [total] columns per plane row (multiple of 64)
+    const uint64_t* plane_off;         // [total] offset of the query's five planes, in units of off_scale plane elements
+    uint32_t off_scale;                // plane elements per unit of plane_off (2: u16 planes under the batch's 4-byte plan)
     uint32_t x, oe, e1, e2, o1;
     uint32_t* score;                   // [total]
     uint32_t* flags;                   // [total]
     uint32_t* n_pairs;                 // [total]
-    poa_aln_pair_t* scratch;           // per slot: n_rows + pitch pairs, written back to front
-    uint32_t scratch_stride;
+    poa_aln_pair_t* scratch;
+    const uint64_t* scratch_off;       // [total + 1] per-query region in `scratch` (capacity len + n_rows), written back to front
     // replayed search (poa2_exact_kernel ran on u32 planes): where each walk starts and what became of the search
     uint32_t exact_pass;
     const uint32_t* ex_status;         // [total] EX_*
     const uint32_t* ex_end;            // [2 * total] (row, offset) the search stopped at
 };
 
-// Resident batch (poa_batch_run_2piece): every query has its own pitch, its planes at plane_off[qi] of the batch's workspace and
-// its pairs at scratch_off[qi] of the batch's scratch, as the one-piece kernels take them (FwdParams / TbParams); `pitch` and
-// `scratch_stride` of the base are not read.
-struct TwoPieceBatchParams : TwoPieceParams {
-    const uint32_t* q_pitch;       // [total] columns per plane row (multiple of 64)
-    const uint64_t* plane_off;     // [total] offset of the query's five planes, in units of off_scale plane elements
-    uint32_t off_scale;            // plane elements per unit of plane_off (2: u16 planes under the batch's 4-byte plan)
-    const uint64_t* scratch_off;   // [total + 1] per-query region in `scratch` (capacity len + n_rows), written back to front
-};
-
-// where a query's planes and pairs live: fixed stride per slot of the chunk (one-shot call) / per query (resident batch)
-__device__ __forceinline__ uint32_t tp_pitch(const TwoPieceParams& P, uint32_t) { return P.pitch; }
-__device__ __forceinline__ uint32_t tp_pitch(const TwoPieceBatchParams& P, uint32_t qi) { return P.q_pitch[qi]; }
+// where a query's planes and pairs live
+__device__ __forceinline__ uint32_t tp_pitch(const TwoPieceParams& P, uint32_t qi) { return P.q_pitch[qi]; }
 template <typename T>
-__device__ __forceinline__ T* tp_planes(const TwoPieceParams& P, uint32_t slot, uint32_t, uint64_t plane) {
-    return reinterpret_cast<T*>(P.planes) + (uint64_t)slot * 5 * plane;
-}
-template <typename T>
-__device__ __forceinline__ T* tp_planes(const TwoPieceBatchParams& P, uint32_t, uint32_t qi, uint64_t) {
+__device__ __forceinline__ T* tp_planes(const TwoPieceParams& P, uint32_t qi) {
     return reinterpret_cast<T*>(P.planes) + P.plane_off[qi] * P.off_scale;
 }
-__device__ __forceinline__ poa_aln_pair_t* tp_out(const TwoPieceParams& P, uint32_t slot, uint32_t, uint32_t& cap) {
-    cap = P.scratch_stride;
-    return P.scratch + (uint64_t)slot * P.scratch_stride;
-}
-__device__ __forceinline__ poa_aln_pair_t* tp_out(const TwoPieceBatchParams& P, uint32_t, uint32_t qi, uint32_t& cap) {
+__device__ __forceinline__ poa_aln_pair_t* tp_out(const TwoPieceParams& P, uint32_t qi, uint32_t& cap) {
     cap = (uint32_t)(P.scratch_off[qi + 1] - P.scratch_off[qi]);
     return P.scratch + P.scratch_off[qi];
 }
-// pairs reported: the one-shot call keeps the walk's own count (its host side refuses one beyond the stride), a resident
-// batch clamps to the region as poa_traceback_kernel does (scan and compaction read n_pairs unchecked)
-__device__ __forceinline__ uint32_t tp_n_pairs(const TwoPieceParams&, uint32_t n_out, uint32_t) { return n_out; }
-__device__ __forceinline__ uint32_t tp_n_pairs(const TwoPieceBatchParams&, uint32_t n_out, uint32_t cap) { return n_out < cap ? n_out : cap; }
+// pairs reported: clamped to the region as poa_traceback_kernel does (scan and compaction read n_pairs unchecked)
+__device__ __forceinline__ uint32_t tp_n_pairs(uint32_t n_out, uint32_t cap) { return n_out < cap ? n_out : cap; }
 
 // Replay of the reference's two-piece search (Affine2PieceMinGapCost / Affine2PieceDijkstra with or without pruning,
 // config.rs:160-272; astar.rs:124-226 over gap_affine_2piece.rs): the search object of poa_exact.hpp instantiated with
@@ -109,8 +92,8 @@ __global__ __launch_bounds__(EXACT2_BLOCK) void poa2_exact_kernel(TwoPieceParams
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     ExactWork W;
-    W.T = P.planes + (uint64_t)slot * 5 * P.n_rows * P.pitch;
-    W.n_rows = P.n_rows; W.pitch = P.pitch;
+    W.T = tp_planes<uint32_t>(P, qi);
+    W.n_rows = P.n_rows; W.pitch = tp_pitch(P, qi);
     W.reached = X.reached + (uint64_t)slot * X.G.n_exit * X.wpn;
     W.rsum = X.rsum + (uint64_t)slot * X.G.n_exit * X.swpn;
     W.wpn = X.wpn; W.swpn = X.swpn;
@@ -222,8 +205,8 @@ __device__ __forceinline__ void tp_row_pass(const TpPassCosts& C, const RowMeta&
 // the bytes of a kernel that lives on its stores; arithmetic is u32 in registers either way (PlaneIO widens 0xFFFF to INF).
 // NP: passes whose previous row stays in registers (rows of up to NP * 64 * K columns): a chain row — one predecessor, the
 // previous row — then reads nothing back from the planes (6 of the 16 bytes of traffic per cell with u16 planes).
-template <typename T, int NP, typename PP = TwoPieceParams>
-__global__ __launch_bounds__(64) void poa2_forward_kernel(PP P) {
+template <typename T, int NP>
+__global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
     using IO = PlaneIO<T>;
     constexpr int K = IO::K;
     constexpr uint32_t PW = 64 * K;   // columns per pass
@@ -233,9 +216,9 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(PP P) {
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* q = P.qseq + qbeg;
-    const uint32_t pitch = tp_pitch(P, qi);   // (resident batch: the query's own — a pass may end inside its padding, never past it)
+    const uint32_t pitch = tp_pitch(P, qi);   // (the query's own: a pass may end inside its padding, never past it)
     const uint64_t plane = (uint64_t)P.n_rows * pitch;
-    T* M = tp_planes<T>(P, slot, qi, plane);
+    T* M = tp_planes<T>(P, qi);
     T* I1 = M + plane; T* D1 = I1 + plane; T* I2 = D1 + plane; T* D2 = I2 + plane;
     const uint32_t n_pass = (L + 1 + PW - 1) / PW;   // pitch is a multiple of 64: a pass may end inside the row's padding
     constexpr int NPA = NP > 0 ? NP : 1;
@@ -460,8 +443,8 @@ struct TpPlaneCells {
 };
 
 // One lane per query: the walk on the five planes.
-template <typename T, typename PP = TwoPieceParams>
-__global__ __launch_bounds__(64) void poa2_traceback_kernel(PP P) {
+template <typename T>
+__global__ __launch_bounds__(64) void poa2_traceback_kernel(TwoPieceParams P) {
     const uint32_t slot = blockIdx.x * 64 + threadIdx.x;
     if (slot >= P.n_queries) return;
     const uint32_t qi = P.first_query + slot;
@@ -469,11 +452,11 @@ __global__ __launch_bounds__(64) void poa2_traceback_kernel(PP P) {
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint32_t pitch = tp_pitch(P, qi);
     const uint64_t plane = (uint64_t)P.n_rows * pitch;
-    const TpPlaneCells<T> C{tp_planes<T>(P, slot, qi, plane), plane, pitch, P.exact_pass};
+    const TpPlaneCells<T> C{tp_planes<T>(P, qi), plane, pitch, P.exact_pass};
     TpWalkCtx W;
     W.rows = P.rows; W.pred_rows = P.pred_rows; W.q = P.qseq + qbeg; W.L = L; W.start_row = P.start_row; W.end_row = P.end_row;
     W.x = P.x; W.o1 = P.o1; W.e1 = P.e1; W.e2 = P.e2;
-    W.out = tp_out(P, slot, qi, W.cap);
+    W.out = tp_out(P, qi, W.cap);
     // the cell the walk starts from: (end row, L) in the dense Global pass; where the replayed search stopped otherwise
     uint32_t tb_row = P.end_row, tb_off = L;
     if (P.exact_pass) {
@@ -492,7 +475,7 @@ __global__ __launch_bounds__(64) void poa2_traceback_kernel(PP P) {
     const uint32_t fl = tp_walk_flags(S);
     // (a replayed table IS the reference's: its backtrace takes the first candidate, nothing to certify)
     P.flags[qi] = P.exact_pass ? (fl & (POA_FLAG_REF_PANIC | POA_FLAG_TRUNCATED)) : fl;
-    P.n_pairs[qi] = tp_n_pairs(P, S.n_out, W.cap);
+    P.n_pairs[qi] = tp_n_pairs(S.n_out, W.cap);
 }
 
 }  // namespace poa_amd

@@ -1,5 +1,5 @@
 // Stand-alone check of the two pure rules the batch constructors of poa_engine.hip share (poasta_amd/csrc/poa_dense_plan.hpp):
-// choose_workspace and concat_tables.  Built by tests/test_create_frame.py together with poa_dense_plan.cpp under
+// choose_workspace and concat_tables, and of two_piece_workspace, the workspace a one-shot two-piece call asks for.  Built by tests/test_create_frame.py together with poa_dense_plan.cpp under
 // -fsanitize=address,undefined, and run on the CPU.
 //
 // The workspace table below was written out by hand from the four constructors as they stood before they shared the rule:
@@ -79,6 +79,73 @@ void check_workspace() {
     CHECK(choose_workspace(0, 256 * GiB, GiB, 100 * GiB, 2 * GiB, true) == 100 * GiB);
 }
 
+// The chunks of `sizes` over `ws` bytes with at most max_count items each: the greedy rule of build_chunk_plan (poa_engine.hip)
+// restated; its evening-out keeps the number of chunks.  Returns the chunk count, the largest chunk in *max_chunk.
+uint64_t greedy_chunks(const std::vector<uint64_t>& sizes, uint64_t ws, uint64_t max_count, uint64_t* max_chunk) {
+    uint64_t chunks = 0, used = 0, count = 0;
+    *max_chunk = 0;
+    for (uint64_t need : sizes) {
+        if ((used + need > ws || count >= max_count) && count > 0) { ++chunks; used = 0; count = 0; }
+        used += need; ++count;
+        *max_chunk = std::max(*max_chunk, count);
+    }
+    return chunks + (count ? 1 : 0);
+}
+
+// two_piece_workspace against the rule the one-shot two-piece call had when it kept a workspace of its own:
+//     dense:   budget = min(0.6 x free, 64 GiB), floor(budget / per_query) queries per chunk, one at least
+//     replay:  budget = 0.85 x free, floor(budget / (per_query + replay bytes + 1)) queries per chunk, one at least
+// with per_query the planes of the longest query, which every query was given.
+void check_two_piece_workspace() {
+    const uint64_t GiB = 1ull << 30;
+    // dense: the budget, never above the total, never below the largest query
+    CHECK(two_piece_workspace(1000, 5000, 100, 0, false).bytes == 600);
+    CHECK(two_piece_workspace(1000, 500, 100, 0, false).bytes == 500);
+    CHECK(two_piece_workspace(100, 5000, 100, 0, false).bytes == 100);
+    CHECK(two_piece_workspace(288 * GiB, 100 * GiB, GiB, 0, false).bytes == 64 * GiB);
+    CHECK(two_piece_workspace(288 * GiB, 60 * GiB, GiB, 0, false).bytes == 60 * GiB);
+    CHECK(two_piece_workspace(100 * GiB, 100 * GiB, GiB, 0, false).bytes == (uint64_t)(100 * GiB * 0.6));
+    CHECK(two_piece_workspace(1000, 5000, 100, 0, false).max_slots == ~0u);
+    // equal queries: ceil(n / floor(budget / per_query)) chunks at a budget just below, at and just above a multiple of the query
+    const uint64_t q = 1000, n = 37;
+    const std::vector<uint64_t> equal(n, q);
+    for (uint64_t m : {1ull, 2ull, 5ull, 36ull, 37ull, 38ull})
+        for (uint64_t budget : {m * q - 1, m * q, m * q + 1}) {
+            uint64_t free_bytes = budget * 5 / 3 - 3;
+            while ((uint64_t)(free_bytes * 0.6) < budget) ++free_bytes;
+            CHECK((uint64_t)(free_bytes * 0.6) == budget);
+            const TwoPieceWorkspace w = two_piece_workspace(free_bytes, n * q, q, 0, false);
+            CHECK(w.bytes <= n * q && w.bytes >= q);
+            const uint64_t per_chunk = std::max<uint64_t>(budget / q, 1);
+            uint64_t max_chunk = 0;
+            CHECK(greedy_chunks(equal, w.bytes, w.max_slots, &max_chunk) == (n + per_chunk - 1) / per_chunk);
+        }
+    // replay: planes and the search workspaces of the largest chunk stay within 85 % of free, a chunk holds a query at least,
+    // and queries of mixed sizes never take more chunks than the uniform stride of the longest gave them
+    const std::vector<std::vector<uint64_t>> batches = {
+        std::vector<uint64_t>(50, 400),
+        {400, 100, 100, 400, 100, 100, 100, 100, 400, 100, 100, 100, 100, 100, 100, 100, 100, 400, 100, 100},
+        {400, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100},
+        {100, 400},
+        {400},
+    };
+    for (const auto& sizes : batches)
+        for (uint64_t slot_bytes : {0ull, 1ull, 150ull, 400ull, 5000ull})
+            for (uint64_t free_bytes = 100; free_bytes <= 40000; free_bytes += 37) {
+                uint64_t total = 0, largest = 0;
+                for (uint64_t s : sizes) { total += s; largest = std::max(largest, s); }
+                const TwoPieceWorkspace w = two_piece_workspace(free_bytes, total, largest, slot_bytes, true);
+                CHECK(w.bytes >= largest && w.bytes <= total && w.max_slots >= 1);
+                uint64_t max_chunk = 0;
+                const uint64_t chunks = greedy_chunks(sizes, w.bytes, w.max_slots, &max_chunk);
+                const uint64_t budget = (uint64_t)(free_bytes * 0.85);
+                if (largest + slot_bytes <= budget) CHECK(w.bytes + max_chunk * slot_bytes <= budget);
+                else CHECK(max_chunk == 1);   // (not even one fits the budget: one query at a time, as before)
+                const uint64_t before = std::max<uint64_t>(std::min<uint64_t>(sizes.size(), budget / (largest + slot_bytes + 1)), 1);
+                CHECK(chunks <= (sizes.size() + before - 1) / before);
+            }
+}
+
 // Three graphs of which the third repeats the first's handle, the second without rows in this table (a graph that has no
 // d_slot table: its part of the concatenated table is what the caller filled it with).  The bases are the planner's: a distinct
 // handle starts where the tables so far end, a repeated one shares the bases of its first listing.
@@ -132,6 +199,7 @@ void check_concat() {
 
 int main() {
     check_workspace();
+    check_two_piece_workspace();
     check_concat();
     std::printf("create_host ok\n");
     return 0;

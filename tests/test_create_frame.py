@@ -1,6 +1,7 @@
 """The host-side frame of a create, pinned over the engine's batch constructors: the device refusals and their texts, a null
 `out`, the workspace and chunks a cap gives, the upload time a batch reports, and creation after destruction.  With it the
-stand-alone check of the two pure rules the constructors share (tests/create_host), on the CPU under the sanitizers.
+stand-alone check of the pure rules the constructors and the one-shot two-piece calls share (tests/create_host), on the CPU
+under the sanitizers.
 
 Every constructor gets the inputs of test_run_frame.py: the two graphs of thirteen nodes with one bubble, the four queries of
 at most ten bases (one pitch of 64 columns), costs 4/6/2 and -g 6,24 -e 2,1.  All items of a batch (queries; pairs of a score
@@ -159,7 +160,8 @@ def _two_chunk_cap(engine, name):
 
 # ---- 0. the pure rules, on the CPU ---------------------------------------------------------------------------------------------
 def test_create_host_rules_under_sanitizers(tmp_path):
-    """tests/create_host: choose_workspace against a table written out from the constructors' former code, concat_tables with a
+    """tests/create_host: choose_workspace against a table written out from the constructors' former code, two_piece_workspace
+    against the budgets and chunk counts of the one-shot two-piece call's former workspace of its own, concat_tables with a
     repeated handle and an empty table — a program of its own, address and undefined-behaviour sanitizers on."""
     csrc = os.path.join(ROOT, "poasta_amd", "csrc")
     exe = os.path.join(str(tmp_path), "create_host")

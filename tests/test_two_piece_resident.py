@@ -1,8 +1,8 @@
 """Two-piece model on resident batches: poa_batch_run_2piece / poa_batch_fetch_planes_2piece (poa_engine.hip; kernels of
-poa_twopiece.hpp instantiated with TwoPieceBatchParams: per-query pitch, plane offset and scratch region).
+poa_twopiece.hpp: per-query pitch, plane offset and scratch region).
 
-Yardsticks, bit for bit on score, flags, pair_off and pairs: the one-shot poa_align_batch_2piece on the same queries (the code
-path the resident run must reproduce) and oracle/dense.hpp through pyoracle.  Graphs and queries are the seeded builders of
+Yardsticks, bit for bit on score, flags, pair_off and pairs: oracle/dense.hpp through pyoracle, and the one-shot
+poa_align_batch_2piece on the same queries (itself a batch run through poa_batch_run_2piece: the same path on a batch of its own).  Graphs and queries are the seeded builders of
 tests/test_two_piece_shapes.py: the chain graph, the four-predecessor graph and the MSA graph.
 
 CPU: both symbols exported, declared and refusing a null batch; the chunk count restated in plain Python (`predict_chunks`).

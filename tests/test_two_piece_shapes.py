@@ -1,8 +1,9 @@
-"""Two-piece dense pass (poasta_amd/csrc/poa_twopiece.hpp, run_two_piece in poa_engine.hip) at the shapes that decide which
+"""Two-piece dense pass (poasta_amd/csrc/poa_twopiece.hpp; the one-shot call is a resident batch's poa_batch_run_2piece in
+poa_engine.hip) at the shapes that decide which
 of its code paths run: both cell widths (u16: 8 columns per lane, 512 per pass, previous row in registers for up to 2
 passes; u32: 4 per lane, 256 per pass, up to 4 passes), rows of exactly one pass / one pass and a column, rows exactly at
 and just past the 1024-column register limit, rows of several passes read back from the planes, empty and one-base
-queries under a long query's pitch, chain rows, rows with several predecessors and chain rows behind such rows.
+queries beside a long query (each at its own pitch), chain rows, rows with several predecessors and chain rows behind such rows.
 
 CPU: the host's selection rule restated in plain Python (`predict`) and a case table (`CASES`); a test proves that the table
 reaches every path above for each width, so a trimmed table fails here rather than passing silently.
@@ -14,9 +15,10 @@ loop with first_query > 0); POA_ERR_CAPACITY and the extend1 < extend2 refusal t
 Expected plane cell under u16: the oracle's value if it is at most 65534, INF otherwise (what PlaneIO<uint16_t> stores and
 reads back); nothing here requires that a finite value above 65534 occurs.
 
-Gap left open: `poa_planes_2piece` takes one query, whose pitch is its own, so the PLANES of a short query under a long
-query's pitch cannot be fetched; that shape (first query empty, pitch set by a later 2 133-base query) is covered by the
-batch-level comparison of scores, flags and alignments only."""
+`poa_planes_2piece` takes one query; in a batch every query has its own pitch as well, so the planes it returns are laid out
+as the batch's are.  The planes of a short query INSIDE a batch of long ones (first query empty beside a 2 133-base query) are
+fetched in tests/test_two_piece_resident.py (poa_batch_fetch_planes_2piece); here that shape is covered by the batch-level
+comparison of scores, flags and alignments."""
 import ctypes as C
 import functools
 import os
@@ -34,7 +36,7 @@ INF = 0xFFFFFFFF
 NP_OF = {2: 2, 4: 4}   # passes whose previous row stays in registers: poa2_forward_kernel<uint16_t, 2> / <uint32_t, 4>
 
 
-# ---- the host's selection rule (run_two_piece), in plain Python -------------------------------------------------------------
+# ---- the host's selection rule (poa_batch_run_2piece), in plain Python ------------------------------------------------------
 def min_path_nodes(g):
     """Real nodes on the shortest start -> end path (FlatGraph::min_path_nodes)."""
     dist = {g.start: 0}
@@ -52,8 +54,8 @@ def min_path_nodes(g):
 
 
 def predict(g, lengths, costs, wide):
-    """What run_two_piece picks for a batch: ub, elem (2: u16 cells, 4: u32), K columns per lane, PW columns per pass, the
-    batch's pitch, and per query (n_pass, keep: previous row in registers)."""
+    """What poa_batch_run_2piece picks for a batch: ub, elem (2: u16 cells, 4: u32), K columns per lane, PW columns per pass, the
+    longest query's pitch (every query has its own: (L + 64) & ~63), and per query (n_pass, keep: previous row in registers)."""
     m, e1, o1, e2, o2 = costs
     max_len, mpn = max(lengths), min_path_nodes(g)
     ub = (o1 + e1 * max_len if max_len else 0) + (o1 + e1 * mpn if mpn else 0)
@@ -99,7 +101,7 @@ def graph_profile(g, node_rows):
 
 
 # ---- the case table ---------------------------------------------------------------------------------------------------------
-# query lengths of every batch: the empty and the one-base query first (their pitch, 2 176, is the longest query's), then
+# query lengths of every batch: the empty and the one-base query first (64 columns each beside the longest query's 2 176), then
 # L + 1 in {63, 64, 65}, around the u32 pass (256), the u16 pass (512), the register limit (1024), 2 134 columns (u16: five
 # passes, u32: nine, the last one partial, no registers), and fillers between them (2 048: whole passes only)
 LENS = (0, 1, 62, 63, 64, 254, 255, 256, 510, 511, 512, 1022, 1023, 1024, 2133, 300, 777, 1087, 1500, 2047, 2048)
@@ -175,7 +177,7 @@ def test_case_table_reaches_every_path():
         g = _poa(c.kind).graph
         p = predict(g, c.lengths, c.costs, c.wide)
         assert [len(q) for q in _queries(c.kind, c.lengths)] == list(c.lengths)
-        assert c.lengths[0] == 0 and p["pitch"] >= 1088                  # the first slot's query is empty under a long pitch
+        assert c.lengths[0] == 0 and p["pitch"] >= 1088                  # the first query is empty, in a batch whose longest pitch is long
         reached.setdefault((p["elem"], c.kind), set()).update(features(p, c.lengths))
         costs_seen[p["elem"]].add(c.costs)
         if c.kind == "mixed":
