@@ -648,4 +648,5 @@ int poa_score_pairs_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 #include "poasta_amd_tb.h"
 #include "poasta_amd_multi_dense.h"
 #include "poasta_amd_multi_exact.h"
+#include "poasta_amd_multi_dense2.h"
 #endif /* POASTA_AMD_H */

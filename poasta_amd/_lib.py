@@ -47,6 +47,9 @@ EXPORTS_MULTI_DENSE = ["poa_multi_footprint_dense", "poa_multi_create_dense", "p
 # every symbol include/poasta_amd_multi_exact.h declares (checked by tests/test_multi_exact_plan.py)
 EXPORTS_MULTI_EXACT = ["poa_multi_footprint_exact", "poa_multi_create_exact", "poa_multi_run_exact", "poa_multi_fetch_search_counters",
                        "poa_align_multi_exact", "poa_multi_replay_info"]
+# every symbol include/poasta_amd_multi_dense2.h declares (checked by tests/test_multi_dense2_plan.py)
+EXPORTS_MULTI_DENSE2 = ["poa_multi_footprint_dense_2piece", "poa_multi_create_dense_2piece", "poa_multi_run_dense_2piece",
+                        "poa_align_multi_dense_2piece", "poa_multi_fetch_planes_2piece"]
 
 
 class PoaBest(C.Structure):
@@ -142,7 +145,7 @@ class PoaError(RuntimeError):
 
 def build(force=False):
     """Compile the HIP engine for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h", "poasta_amd_multi_dense.h", "poasta_amd_multi_exact.h")]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(_HERE, "..", "include", h) for h in ("poasta_amd.h", "poasta_amd_scoreset_cap.h", "poasta_amd_scoreset_best.h", "poasta_amd_tb.h", "poasta_amd_multi_dense.h", "poasta_amd_multi_exact.h", "poasta_amd_multi_dense2.h")]
     stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC] + (["-B"] if force else []))
@@ -324,6 +327,18 @@ def lib():
             L.poa_multi_replay_info.argtypes = [vp, C.c_uint32, vp]
         L.poa_align_multi_exact.restype = C.c_int
         L.poa_align_multi_exact.argtypes = L.poa_align_multi.argtypes
+    if hasattr(L, "poa_multi_create_dense_2piece"):   # (as above)
+        # the dense two-piece batch kind on the same object: the argument lists of the _2piece namesakes
+        L.poa_multi_footprint_dense_2piece.restype = C.c_int
+        L.poa_multi_footprint_dense_2piece.argtypes = L.poa_multi_footprint.argtypes
+        L.poa_multi_create_dense_2piece.restype = C.c_int
+        L.poa_multi_create_dense_2piece.argtypes = L.poa_multi_create.argtypes
+        L.poa_multi_run_dense_2piece.restype = C.c_int
+        L.poa_multi_run_dense_2piece.argtypes = L.poa_multi_run_2piece.argtypes
+        L.poa_align_multi_dense_2piece.restype = C.c_int
+        L.poa_align_multi_dense_2piece.argtypes = L.poa_align_multi_2piece.argtypes
+        L.poa_multi_fetch_planes_2piece.restype = C.c_int
+        L.poa_multi_fetch_planes_2piece.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]
     # score set: graphs is an array of n_graphs handles; pair_query / pair_graph are u32 arrays, or both NULL (the full matrix)
     L.poa_scoreset_footprint.restype = C.c_int
     L.poa_scoreset_footprint.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, C.POINTER(PoaConfig), C.POINTER(C.c_uint64),

@@ -555,8 +555,20 @@ def _multi_wide_config(who, mi, config, dense, exact, wide):
     return config, bool(wide)
 
 
+def _multi_kind_check(who, two_piece, dense, exact, dense2, wide):
+    """The kinds of a multi-graph batch exclude each other; dense2 is the dense batch of the two-piece model, a kind of its own."""
+    if (dense or exact) and two_piece:
+        raise ValueError(who + ": the dense and exact multi-graph batches are one-piece (the dense two-piece batch: dense2=True)")
+    if dense and exact:
+        raise ValueError(who + ": dense and exact are two kinds of batch")
+    if dense2 and (dense or exact or two_piece):
+        raise ValueError(who + ": dense2 is a kind of its own: not together with dense, exact or two_piece")
+    if dense2 and wide:
+        raise ValueError(who + ": wide=True is for the dense and exact kinds; the dense two-piece batch takes queries of any length")
+
+
 def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, config=None, two_piece=False, dense=False, exact=False,
-                    wide=None):
+                    wide=None, dense2=False):
     """(bytes, largest_query_bytes) of a multi-graph batch: the plane workspace of the whole batch as one chunk and of its
     largest query (poa_multi_footprint; host only).  config: make_config("checkpoint", ckpt_rows=k) to size another plan.
     two_piece: the batch of the two-piece model (poa_multi_footprint_2piece; config: None or mode "checkpoint2").
@@ -564,17 +576,18 @@ def multi_footprint(graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qof
     exact: the exact batch (poa_multi_footprint_exact; config: None or mode "exact" / "hybrid"): the dense region and the u32
     visited table per query, plus the replay workspace of every slot (queue_entries_per_cell from config).
     wide: POA_CFG_WIDE_QUERIES for the dense and exact kinds (None: set iff a query is longer than 1023 symbols; True / False
-    force it; True with a checkpointed kind is a ValueError: that kind takes any length already)."""
-    if (dense or exact) and two_piece:
-        raise ValueError("multi_footprint: the dense and exact multi-graph batches are one-piece")
-    if dense and exact:
-        raise ValueError("multi_footprint: dense and exact are two kinds of batch")
+    force it; True with a checkpointed kind is a ValueError: that kind takes any length already).
+    dense2: the dense two-piece batch (poa_multi_footprint_dense_2piece; config: None or mode "dense"): five u16 planes per
+    query, any length; not together with dense, exact, two_piece or wide=True."""
+    _multi_kind_check("multi_footprint", two_piece, dense, exact, dense2, wide)
     mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
     config, _ = _multi_wide_config("multi_footprint", mi, config, dense, exact, wide)
     total, largest = C.c_uint64(0), C.c_uint64(0)
     fn = _lib.lib().poa_multi_footprint_2piece if two_piece else (_lib.lib().poa_multi_footprint_dense if dense else _lib.lib().poa_multi_footprint)
     if exact:
         fn = _lib.lib().poa_multi_footprint_exact
+    if dense2:
+        fn = _lib.lib().poa_multi_footprint_dense_2piece
     _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), _p(mi.qoff), C.byref(config) if config is not None else None,
                   C.byref(total), C.byref(largest)))
     return int(total.value), int(largest.value)
@@ -591,25 +604,28 @@ class MultiGraphBatch:
     says what the batch was created with): a chunk with such a query runs the strip loop, every other chunk what it always ran.
     exact=True: the exact batch (`poa_multi_create_exact`): the dense batch with the replay of the reference's search behind it;
     run with make_config("exact" | "hybrid", heuristic, pruning, ...): per query what align_batch returns in that mode for the
-    query's graph alone, and search_counters() the replay's counters."""
+    query's graph alone, and search_counters() the replay's counters.
+    dense2=True: the dense two-piece batch (`poa_multi_create_dense_2piece`): five u16 planes per query, one forward and one
+    walk launch per chunk instead of the two checkpointed passes; run with GapAffine2Piece costs that allow u16 cells (config:
+    None or make_config("dense", ...)), queries of any length; planes_2piece(query) reads a query's planes back."""
 
     def __init__(self, graphs, seqs_per_graph=None, graph_qoff=None, qseq=None, qoff=None, device=0, workspace_bytes=0, config=None,
-                 two_piece=False, dense=False, exact=False, wide=None):
-        if (dense or exact) and two_piece:
-            raise ValueError("MultiGraphBatch: the dense and exact multi-graph batches are one-piece")
-        if dense and exact:
-            raise ValueError("MultiGraphBatch: dense and exact are two kinds of batch")
+                 two_piece=False, dense=False, exact=False, wide=None, dense2=False):
+        _multi_kind_check("MultiGraphBatch", two_piece, dense, exact, dense2, wide)
         mi = _MultiInput(graphs, seqs_per_graph, graph_qoff, qseq, qoff)
         self.input, self.n, self.pair_capacity = mi, mi.n, mi.pair_capacity
         self.graph_qoff, self.qseq, self.qoff = mi.graph_qoff, mi.qseq, mi.qoff
         self.two_piece = bool(two_piece)
         self.dense = bool(dense)
         self.exact = bool(exact)
+        self.dense2 = bool(dense2)
         config, self.wide = _multi_wide_config("MultiGraphBatch", mi, config, self.dense, self.exact, wide)
         h = C.c_void_p()
         create = _lib.lib().poa_multi_create_2piece if self.two_piece else (_lib.lib().poa_multi_create_dense if self.dense else _lib.lib().poa_multi_create)
         if self.exact:
             create = _lib.lib().poa_multi_create_exact
+        if self.dense2:
+            create = _lib.lib().poa_multi_create_dense_2piece
         _lib.check(create(mi.handles, mi.n_graphs, _p(mi.graph_qoff), device, _p(mi.qseq), _p(mi.qoff),
                           C.byref(config) if config is not None else None, int(workspace_bytes), C.byref(h)))
         self.handle = h
@@ -619,11 +635,16 @@ class MultiGraphBatch:
         make_config("checkpoint2", ...)).  GapAffine2Piece costs run through poa_multi_run_2piece, all others through
         poa_multi_run: costs of the other model than the batch's are refused by the library (POA_ERR_INVALID_ARG).  A dense
         batch runs one-piece costs through poa_multi_run_dense (config: None or make_config("dense", ...)), an exact batch
-        through poa_multi_run_exact (config: None = make_config("exact"), or make_config("hybrid", ...))."""
+        through poa_multi_run_exact (config: None = make_config("exact"), or make_config("hybrid", ...)).  A dense2 batch runs
+        GapAffine2Piece costs through poa_multi_run_dense_2piece (config: None or make_config("dense", ...))."""
         c = costs._c()
         if config is None:
-            config = make_config("exact" if self.exact else ("dense" if self.dense else ("checkpoint2" if self.two_piece else "checkpoint")))   # (carries the POA_<NAME> overrides, if any are set)
-        if isinstance(costs, GapAffine2Piece):
+            config = make_config("exact" if self.exact else ("dense" if (self.dense or self.dense2) else ("checkpoint2" if self.two_piece else "checkpoint")))   # (carries the POA_<NAME> overrides, if any are set)
+        if self.dense2:
+            if not isinstance(costs, GapAffine2Piece):
+                raise ValueError("MultiGraphBatch.run: a dense2 batch runs GapAffine2Piece costs")
+            run = _lib.lib().poa_multi_run_dense_2piece
+        elif isinstance(costs, GapAffine2Piece):
             run = _lib.lib().poa_multi_run_2piece
         elif self.exact:
             run = _lib.lib().poa_multi_run_exact
@@ -649,6 +670,16 @@ class MultiGraphBatch:
                 out[-1].update(fuse=False, mw=False, replay={1: "lds", 2: "generic"}[int(v[2]) & 3])
             if v[2] & _lib.LAUNCH_STRIPS:
                 out[-1]["strips"] = True
+
+    def planes_2piece(self, query):
+        """M, I1, D1, I2, D2 of one query after a run of a dense2 batch (poa_multi_fetch_planes_2piece), rows = topological rank
+        in the query's own graph (its chunk must be the last one run)."""
+        g = int(np.searchsorted(self.graph_qoff, query, side="right")) - 1
+        rows = self.input.dgs[g].graph.n
+        cols = int(self.qoff[query + 1] - self.qoff[query]) + 1
+        out = [np.zeros((rows, cols), np.uint32) for _ in range(5)]
+        _lib.check(_lib.lib().poa_multi_fetch_planes_2piece(self.handle, query, *[_p(a) for a in out]))
+        return out
 
     def replay_info(self):
         """What the replay of the last run of an exact batch launched, one dict per chunk (poa_multi_replay_info), in the form
@@ -947,14 +978,19 @@ class PoastaAligner:
         POA_CFG_WIDE_QUERIES by themselves: their chunks run the forward pass strip by strip.
         mode="exact" | "hybrid": the replay of the reference's search behind the dense batch (poa_align_multi_exact): per query
         what align_batch returns on a PoastaAligner of that mode for the query's graph alone; heuristic and pruning come from
-        the aligner's config as there, queue_entries_per_cell from the aligner.  One-piece, Global; long reads as under "dense"."""
+        the aligner's config as there, queue_entries_per_cell from the aligner.  One-piece, Global; long reads as under "dense".
+        mode="dense2": the two-piece results from the dense two-piece batch (poa_align_multi_dense_2piece): five u16 planes per
+        query, reads of any length — more workspace, a two-piece config only (a one-piece config: ValueError), costs that allow
+        u16 cells."""
         if self.aln_type != AlignmentType.Global:
             raise ValueError("align_multi: AlignmentType.Global only")
-        if mode not in ("checkpoint", "dense", "exact", "hybrid"):
-            raise ValueError("align_multi: mode is \"checkpoint\", \"dense\", \"exact\" or \"hybrid\"")
+        if mode not in ("checkpoint", "dense", "exact", "hybrid", "dense2"):
+            raise ValueError("align_multi: mode is \"checkpoint\", \"dense\", \"exact\", \"hybrid\" or \"dense2\"")
         two_piece = getattr(self.config, "two_piece", False)
-        if mode != "checkpoint" and two_piece:
-            raise ValueError("align_multi: mode=\"%s\" is one-piece; a two-piece config runs the checkpointed batch" % mode)
+        if mode == "dense2" and not two_piece:
+            raise ValueError("align_multi: mode=\"dense2\" is the dense batch of the two-piece model; a one-piece config runs mode=\"dense\"")
+        if mode not in ("checkpoint", "dense2") and two_piece:
+            raise ValueError("align_multi: mode=\"%s\" is one-piece; a two-piece config runs the checkpointed batch or mode=\"dense2\"" % mode)
         if mode in ("exact", "hybrid"):
             mi = _MultiInput(graphs, seqs_per_graph)
             n = mi.n
@@ -978,9 +1014,11 @@ class PoastaAligner:
         pairs = np.zeros((max(mi.pair_capacity, 1), 2), np.uint32) if want_pairs else None
         st = _lib.PoaStats()
         c = self.config.costs._c()
-        cfg = make_config("dense" if mode == "dense" else ("checkpoint2" if two_piece else "checkpoint"), self.config.heuristic)
+        cfg = make_config("dense" if mode in ("dense", "dense2") else ("checkpoint2" if two_piece else "checkpoint"), self.config.heuristic)
         cfg, _ = _multi_wide_config("align_multi", mi, cfg, mode == "dense", False, None)
         fn = _lib.lib().poa_align_multi_2piece if two_piece else (_lib.lib().poa_align_multi_dense if mode == "dense" else _lib.lib().poa_align_multi)
+        if mode == "dense2":
+            fn = _lib.lib().poa_align_multi_dense_2piece
         _lib.check(fn(mi.handles, mi.n_graphs, _p(mi.graph_qoff), C.byref(c), C.byref(cfg), _p(mi.qseq), _p(mi.qoff), _p(score),
                       _p(pairs), _p(pair_off), mi.pair_capacity, _p(flags), C.byref(st), self.device))
         if want_pairs:
@@ -1045,7 +1083,9 @@ class PoastaAligner:
         two-piece form for a two-piece config; mode: align_multi's).  Returns (assignment, BatchResult), the BatchResult in
         the order of seqs; a query without a graph has no pairs, score POA_NONE and flags 0."""
         if mode == "dense" and getattr(self.config, "two_piece", False):   # (before the assignment runs for nothing)
-            raise ValueError("assign_and_align: mode=\"dense\" is one-piece; a two-piece config runs the checkpointed batch")
+            raise ValueError("assign_and_align: mode=\"dense\" is one-piece; a two-piece config runs the checkpointed batch or mode=\"dense2\"")
+        if mode == "dense2" and not getattr(self.config, "two_piece", False):
+            raise ValueError("assign_and_align: mode=\"dense2\" is the dense batch of the two-piece model; a one-piece config runs mode=\"dense\"")
         a = self.assign(graphs, seqs, pairs=pairs, max_score=max_score)
         n = len(seqs)
         order = [np.flatnonzero(a["graph"] == g) for g in range(len(graphs))]

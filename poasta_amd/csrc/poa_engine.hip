@@ -38,6 +38,7 @@
 #include "poa_multi_plan.hpp"
 #include "poa_multi.hpp"
 #include "poa_multi_dense.hpp"
+#include "poa_multi_dense2.hpp"
 #include "poa_multi_exact.hpp"
 #include "poa_scoreset_plan.hpp"
 #include "poa_scoreset.hpp"
@@ -2521,6 +2522,10 @@ struct poa_multi {
     // other's run calls), behind every chunk's dense regions the u32 visited tables, the ExactGraph arrays of all graphs
     // concatenated, one MultiExactBlock per listed graph, and the slots' replay workspace in one buffer (MultiExactSlot)
     bool exact = false;
+    // a batch of poa_multi_create_dense_2piece (poa_multi_dense2.hpp): five full u16 planes per query in the workspace, one
+    // MultiDense2Block per listed graph; neither core.ckpt nor `dense` is set
+    bool dense2 = false;
+    DevBuf<MultiDense2Block> d_dense2;
     DevBuf<MultiExactBlock> d_exact;
     DevBuf<uint64_t> d_table_off;
     DevBuf<uint8_t> d_x_sym, d_x_ws;
@@ -2532,7 +2537,7 @@ struct poa_multi {
 };
 
 namespace {
-enum class MultiKind { checkpoint, checkpoint2, dense, Exact };   // what a poa_multi holds: its plan, its footprint, its run
+enum class MultiKind { checkpoint, checkpoint2, dense, Exact, dense2 };   // what a poa_multi holds: its plan, its footprint, its run
 
 int multi_mode_check(const poa_config_t* cfg, const char* who, bool two_piece = false) {
     if (cfg && cfg->mode != (two_piece ? POA_MODE_CHECKPOINT2 : POA_MODE_CHECKPOINT))
@@ -2561,7 +2566,8 @@ int multi_exact_mode_check(const poa_config_t* cfg, const char* who) {
 }
 int multi_mode_check(MultiKind kind, const poa_config_t* cfg, const char* who) {
     if (kind == MultiKind::Exact) return multi_exact_mode_check(cfg, who);
-    return kind == MultiKind::dense ? multi_dense_mode_check(cfg, who) : multi_mode_check(cfg, who, kind == MultiKind::checkpoint2);
+    if (kind == MultiKind::dense || kind == MultiKind::dense2) return multi_dense_mode_check(cfg, who);
+    return multi_mode_check(cfg, who, kind == MultiKind::checkpoint2);
 }
 
 // the plan of the kind (build_multi_plan with the model's weights, build_multi_dense_plan) behind the checks of the handles
@@ -2589,6 +2595,8 @@ int multi_plan_of(MultiKind kind, const poa_graph_t* const* graphs, uint32_t n_g
         rc = build_multi_exact_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, xc, plan, err, wide);
     } else if (kind == MultiKind::dense) {
         rc = build_multi_dense_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err, wide);
+    } else if (kind == MultiKind::dense2) {
+        rc = build_multi_dense2_plan(in.data(), n_graphs, graph_qoff, qoff, workspace_bytes, plan, err);
     } else {
         uint32_t seg_rows = 0;
         { const TuneView T(cfg); if (const int* v = T.ptr(POA_TUNE_CKPT_ROWS)) seg_rows = (*v) > 0 ? (uint32_t)(*v) : 0u; }
@@ -2624,6 +2632,7 @@ int multi_create_open(CreateFrame& frame, MultiKind kind, std::unique_ptr<poa_mu
     if (!m) return fail(POA_ERR_OUT_OF_MEMORY, "host allocation failed");
     m->dense = kind == MultiKind::dense;
     m->exact = kind == MultiKind::Exact;
+    m->dense2 = kind == MultiKind::dense2;
     MultiPlan& pl = m->plan;
     auto plan_of = [&](uint64_t ws, MultiPlan& plan) { return multi_plan_of(kind, graphs, n_graphs, graph_qoff, qoff, cfg, ws, plan, who_c); };
     // a first plan without a cap: the argument checks (no device needed) and the footprint the cap is chosen from
@@ -2636,7 +2645,7 @@ int multi_create_open(CreateFrame& frame, MultiKind kind, std::unique_ptr<poa_mu
                            (kind == MultiKind::Exact ? pl.exact_bytes + pl.n_rows_total * 64 + (pl.n_succ_total + pl.n_nbm_total) * 16 : 0);
     if (const int rc = frame.plan_capped(pl, workspace_bytes, fixed, pl.largest_query_bytes, refusal, plan_of)) return rc;
     // the core batch: queries, results, pair buffers, events
-    frame.fill_core(&m->core, pl, (m->dense || m->exact) ? pl.plane_bytes : pl.bytes_total, qoff);
+    frame.fill_core(&m->core, pl, (m->dense || m->exact || m->dense2) ? pl.plane_bytes : pl.bytes_total, qoff);
     return POA_OK;
 }
 
@@ -2931,6 +2940,7 @@ int poa_multi_run(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* 
     if (m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_2piece (it runs through poa_multi_run_2piece only)");
     if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
     if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
+    if (m->dense2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run: the batch was created by poa_multi_create_dense_2piece (it runs through poa_multi_run_dense_2piece only)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run");
     if (mrc != POA_OK) return mrc;
     const TuneView T(cfg);
@@ -2976,6 +2986,7 @@ int poa_multi_run_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_co
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: null argument");
     if (m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_dense (it runs through poa_multi_run_dense only)");
     if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
+    if (m->dense2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create_dense_2piece (it runs through poa_multi_run_dense_2piece only)");
     if (!m->core.ckpt2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_2piece: the batch was created by poa_multi_create (a two-piece run needs poa_multi_create_2piece: its footprint differs)");
     const int mrc = multi_mode_check(cfg, "poa_multi_run_2piece", true);
     if (mrc != POA_OK) return mrc;
@@ -3120,6 +3131,7 @@ int poa_multi_create_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, 
 int poa_multi_run_dense(poa_multi_t* m, const poa_costs_t* costs, const poa_config_t* cfg, void* stream_v) {
     if (!m || !costs) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: null argument");
     if (m->exact) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was created by poa_multi_create_exact (it runs through poa_multi_run_exact only)");
+    if (m->dense2) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was created by poa_multi_create_dense_2piece (it runs through poa_multi_run_dense_2piece only)");
     if (!m->dense) return fail(POA_ERR_INVALID_ARG, "poa_multi_run_dense: the batch was not created by poa_multi_create_dense (a checkpointed batch runs through poa_multi_run / poa_multi_run_2piece)");
     const int mrc = multi_dense_mode_check(cfg, "poa_multi_run_dense");
     if (mrc != POA_OK) return mrc;
@@ -3181,6 +3193,174 @@ int poa_align_multi_dense(const poa_graph_t* const* graphs, uint32_t n_graphs, c
     if (stats) std::memset(stats, 0, sizeof(*stats));
     return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_dense(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
                           [&](poa_multi_t* m) { return poa_multi_run_dense(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
+}
+
+}  // extern "C"
+
+
+// ---- dense two-piece multi-graph batch (poa_multi_dense2.hpp, build_multi_dense2_plan) --------------------------------------
+// A fifth kind of the same object (poa_multi::dense2): the workspace holds every query's five u16 planes, a run is per chunk the
+// dense two-piece forward launch and the walk launch over the queries of all graphs, then the scan and compaction of pairs.  The
+// core is a dense poa_batch (ckpt not set, two_piece not set: the stored bytes are the plan's, pitch included), so
+// poa_multi_fetch / _stats / _device_results / _workspace_bytes / _destroy serve it unchanged.
+namespace {
+int multi_create_dense2_impl(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                             const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    CreateFrame frame{"poa_multi_create_dense_2piece"};
+    std::unique_ptr<poa_multi> m;
+    if (const int rc = multi_create_open(frame, MultiKind::dense2, m, graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes,
+                                         "the five score planes of the largest query do not fit in device memory"))
+        return rc;
+    const MultiPlan& pl = m->plan;
+    const uint32_t n = pl.n_queries;
+    poa_batch* b = &m->core;
+    b->last_mode = POA_MODE_DENSE;
+
+    // concatenated tables, one copy per distinct handle: rows by row, pred_rows by edge
+    std::vector<RowMeta> h_rows(pl.n_rows_total);
+    std::vector<uint32_t> h_pred_rows(pl.n_edges_total);
+    using GP = MultiGraphPlan;
+    concat_tables(h_rows, pl.graphs, &GP::row_base, [&](uint32_t g) -> auto& { return graphs[g]->g.rows; });
+    concat_tables(h_pred_rows, pl.graphs, &GP::edge_base, [&](uint32_t g) -> auto& { return graphs[g]->g.pred_rows; });
+    for (uint32_t g = 0; g < n_graphs; ++g)
+        if (pl.graphs[g].n_queries) note_graph_bound(m->ub_open, m->ub_extend, pl.graphs[g].max_len, graphs[g]->g);
+
+    HIP_TRY(CreateFrame::alloc_each(pl.n_rows_total, b->d_rows));
+    HIP_TRY(CreateFrame::alloc_each(pl.n_edges_total, b->d_pred_rows));
+    HIP_TRY(CreateFrame::alloc_each(n, m->d_graph_of));
+    HIP_TRY(CreateFrame::alloc_each(n_graphs, m->d_dense2));
+    if (const int rc = frame.alloc_results(b, qoff[n], n, n, true, pl.scratch_off[n])) return rc;
+    if (const int rc = frame.acquire_planes(b, pl.workspace_bytes, true, "dense two-piece multi-graph workspace")) return rc;
+
+    // one block per listed graph: what poa_batch_run_2piece puts into TwoPieceParams for that graph alone; the chunk, the costs
+    // and the planes base belong to the launch
+    std::vector<MultiDense2Block> h_blocks(n_graphs);
+    for (uint32_t g = 0; g < n_graphs; ++g) {
+        const MultiGraphPlan& gp = pl.graphs[g];
+        const FlatGraph& fg = graphs[g]->g;
+        MultiDense2Block& mb = h_blocks[g];
+        std::memset(&mb, 0, sizeof(mb));
+        TwoPieceParams& tp = mb.P;
+        tp.rows = b->d_rows.p + gp.row_base; tp.pred_rows = b->d_pred_rows.p + gp.edge_base;
+        tp.n_rows = fg.n; tp.start_row = fg.start_row; tp.end_row = fg.end_row;
+        tp.qseq = b->d_qseq.p; tp.qoff = b->d_qoff.p;
+        tp.q_pitch = b->d_pitch.p; tp.plane_off = b->plan[0].d_off.p; tp.off_scale = 1u;
+        tp.score = b->d_score.p; tp.flags = b->d_flags.p; tp.n_pairs = b->d_npairs.p;
+        tp.scratch = reinterpret_cast<poa_aln_pair_t*>(b->d_scratch.p); tp.scratch_off = b->d_scratch_off.p;
+        mb.empty = fg.n_real == 0 ? 1u : 0u;
+    }
+
+    if (const int rc = frame.begin_upload()) return rc;
+    HIP_TRY(CreateFrame::upload(b->d_rows, h_rows));
+    HIP_TRY(CreateFrame::upload(b->d_pred_rows, h_pred_rows));
+    HIP_TRY(CreateFrame::upload(m->d_dense2, h_blocks));
+    HIP_TRY(CreateFrame::upload(m->d_graph_of.p, pl.graph_of.data(), (size_t)n * 4));
+    if (const int rc = frame.upload_queries(b, qseq, qoff, n, pl.scratch_off.data(), pl.pitch.data(), pl.region_off.data(), n)) return rc;
+    if (const int rc = frame.end_upload(b)) return rc;
+
+    *out = m.release();
+    return POA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int poa_multi_footprint_dense_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                                     const poa_config_t* cfg, uint64_t* bytes, uint64_t* largest_query_bytes) {
+    return multi_footprint_impl(MultiKind::dense2, graphs, n_graphs, graph_qoff, qoff, cfg, bytes, largest_query_bytes, "poa_multi_footprint_dense_2piece");
+}
+
+int poa_multi_create_dense_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, int device, const uint8_t* qseq,
+                                  const uint64_t* qoff, const poa_config_t* cfg, uint64_t workspace_bytes, poa_multi_t** out) {
+    return CreateFrame::enter("poa_multi_create_dense_2piece", out, "poa_multi_create_dense_2piece: host allocation failed",
+                              [&] { return multi_create_dense2_impl(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, workspace_bytes, out); });
+}
+
+// per chunk the dense two-piece forward launch over the queries of all graphs (a wave per query), then the walk launch (a lane
+// per query); scan and compaction of the pairs over all queries.  Nothing is written into the batch before every refusal has passed.
+int poa_multi_run_dense_2piece(poa_multi_t* m, const poa_costs2_t* costs, const poa_config_t* cfg, void* stream_v) {
+    const char* who = "poa_multi_run_dense_2piece";
+    if (!m || !costs) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (!m->dense2)
+        return fail(POA_ERR_INVALID_ARG, std::string(who) + ": the batch was not created by poa_multi_create_dense_2piece (a checkpointed batch runs through "
+                                         "poa_multi_run / poa_multi_run_2piece, a dense one through poa_multi_run_dense, an exact one through poa_multi_run_exact)");
+    if (const int mrc = multi_dense_mode_check(cfg, who)) return mrc;
+    if (costs->gap_extend1 < costs->gap_extend2)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    const TuneView T(cfg);
+    // the batch is sized for u16 cells: every graph's own bound (the first piece's costs, its longest query and shortest path) must
+    // allow them, and neither wide_planes nor the planes tunable may ask for u32
+    const bool narrow = !costs->wide_planes && !planes32(T) && all_graphs_u16(m->ub_open, m->ub_extend, costs->gap_open1, costs->gap_extend1);
+    if (!narrow)
+        return fail(POA_ERR_UNSUPPORTED, std::string(who) + ": the run needs u32 cells (the first piece's score bound exceeds 65534 for some graph, "
+                                         "costs->wide_planes, or tune[POA_TUNE_PLANES] = 32) and a dense two-piece multi-graph batch holds u16 cells "
+                                         "only; the checkpointed batch (poa_multi_create_2piece, poa_multi_run_2piece) runs either width");
+    poa_batch* b = &m->core;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(b->device));
+    RunFrame run;
+    if (const int rc = run.open(b, std::string(who) + ": call poa_multi_stats/fetch at least every 256 runs")) return rc;
+    const MultiPlan& pl = m->plan;
+    if (const int rc = run.begin(stream, pl.chunks.size())) return rc;
+    b->last_mode = POA_MODE_DENSE;
+    b->two_piece = false;   // (poa_stats_t.plane_bytes is the plan's: whole pitches)
+    set_layout(b, true);
+    b->active_plan = 0;
+    b->launches.clear();
+    if (b->n_queries == 0) return run.end_empty(true);
+    for (const auto& ch : pl.chunks) {
+        MultiDense2Launch ml;
+        ml.graphs = m->d_dense2.p; ml.graph_of = m->d_graph_of.p; ml.planes = b->d_planes.p;
+        ml.first_query = ch.first; ml.n_queries = ch.count;
+        ml.x = costs->mismatch; ml.o1 = costs->gap_open1; ml.e1 = costs->gap_extend1; ml.e2 = costs->gap_extend2;
+        ml.oe = (uint32_t)costs->gap_open1 + costs->gap_extend1;
+        // one wave per query, previous row in registers for up to 1024 columns (two passes of 512): poa_batch_run_2piece's variant
+        hipLaunchKernelGGL((poa2_forward_multi_kernel<uint16_t, 2>), dim3((ch.count + 3) / 4), dim3(256), 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark()) return rc;
+        hipLaunchKernelGGL(poa2_traceback_multi_kernel<uint16_t>, dim3((ch.count + 63) / 64), dim3(64), 0, stream, ml);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = run.mark(2)) return rc;
+    }
+    return run.end_pairs();
+}
+
+int poa_multi_fetch_planes_2piece(poa_multi_t* m, uint32_t query, uint32_t* mp, uint32_t* i1, uint32_t* d1, uint32_t* i2, uint32_t* d2) {
+    const char* who = "poa_multi_fetch_planes_2piece";
+    if (!m || !mp || !i1 || !d1 || !i2 || !d2) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    if (!m->dense2) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": the batch was not created by poa_multi_create_dense_2piece (no other kind keeps five planes)");
+    poa_batch* b = &m->core;
+    if (!b->ran || query >= b->n_queries) return fail(POA_ERR_INVALID_ARG, std::string(who) + ": bad query / not run");
+    const MultiPlan& pl = m->plan;
+    const auto& last = pl.chunks.back();
+    if (query < last.first || query >= last.first + last.count)
+        return fail(POA_ERR_INVALID_ARG, std::string(who) + ": the query's planes were overwritten by a later chunk");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    const uint32_t rows = pl.graphs[pl.graph_of[query]].n_rows, pitch = pl.pitch[query];
+    const uint32_t cols = (uint32_t)(b->h_qoff[query + 1] - b->h_qoff[query]) + 1;
+    const uint64_t RP = (uint64_t)rows * pitch;
+    uint32_t* dst[5] = {mp, i1, d1, i2, d2};
+    return CreateFrame::guarded(std::string(who) + ": host allocation failed", [&]() -> int {
+        std::vector<uint16_t> tmp((size_t)rows * cols);
+        const uint16_t* base = reinterpret_cast<const uint16_t*>(b->d_planes.p) + pl.region_off[query];
+        for (int k = 0; k < 5; ++k) {
+            HIP_TRY(hipMemcpy2D(tmp.data(), (size_t)cols * 2, base + k * RP, (size_t)pitch * 2, (size_t)cols * 2, rows, hipMemcpyDeviceToHost));
+            for (size_t t = 0; t < tmp.size(); ++t) dst[k][t] = tmp[t] == 0xFFFFu ? 0xFFFFFFFFu : tmp[t];
+        }
+        return POA_OK;
+    });
+}
+
+int poa_align_multi_dense_2piece(const poa_graph_t* const* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const poa_costs2_t* costs,
+                                 const poa_config_t* cfg, const uint8_t* qseq, const uint64_t* qoff, uint32_t* score, poa_aln_pair_t* pairs,
+                                 uint64_t* pair_off, uint64_t pair_capacity, uint32_t* flags, poa_stats_t* stats, int device) {
+    if (!costs) return fail(POA_ERR_INVALID_ARG, "poa_align_multi_dense_2piece: null argument");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (costs->gap_extend1 < costs->gap_extend2)   // (before a batch is made for it)
+        return fail(POA_ERR_INVALID_ARG, "gap_extend1 must be greater than or equal to gap_extend2 for two-piece model");
+    return multi_one_shot([&](poa_multi_t** m) { return poa_multi_create_dense_2piece(graphs, n_graphs, graph_qoff, device, qseq, qoff, cfg, 0, m); },
+                          [&](poa_multi_t* m) { return poa_multi_run_dense_2piece(m, costs, cfg, nullptr); }, score, pairs, pair_off, pair_capacity, flags, stats);
 }
 
 }  // extern "C"

@@ -110,9 +110,11 @@ namespace {
 inline uint64_t dense_carry_words(uint32_t pitch, uint32_t n_rows) { return pitch > MULTI_STRIP_COLUMNS ? 2ull * n_rows : 0ull; }
 const char* const DENSE_CARRY_OVERFLOW = "multi-graph batch: the strip carries of one chunk exceed 2^32 words; cap workspace_bytes";
 
-// build_multi_dense_plan; `carries` false: the chunks' carries are left to the caller (the exact plan cuts its own chunks)
+// build_multi_dense_plan; `carries` false: the chunks' carries are left to the caller (the exact plan cuts its own chunks).
+// `five_planes`: build_multi_dense2_plan — the same plan over five full u16 planes per query; called with `wide` set (any
+// length) and `carries` not (the two-piece pass hands nothing from strip to strip).
 int dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
-               uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide, bool carries) {
+               uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide, bool carries, bool five_planes = false) {
     out = MultiPlan();
     if (!graph_qoff || !qoff || (n_graphs && !graphs)) { err = "dense multi-graph batch: null argument"; return ERR_INVALID_ARG; }
     if (graph_qoff[0] != 0) { err = "dense multi-graph batch: graph_qoff[0] is not 0"; return ERR_INVALID_ARG; }
@@ -159,7 +161,11 @@ int dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* gr
     }
 
     // per query: its compact planes and the padding, in two-byte elements
-    auto elems_of = [&](uint32_t i) { return multi_dense_query_elems(*graphs[out.graph_of[i]].g, qoff[i + 1] - qoff[i]) + MULTI_DENSE_PAD_ELEMS; };
+    auto elems_of = [&](uint32_t i) {
+        const FlatGraph& fg = *graphs[out.graph_of[i]].g;
+        const uint64_t L = qoff[i + 1] - qoff[i];
+        return (five_planes ? multi_dense2_query_elems(fg, L) : multi_dense_query_elems(fg, L)) + MULTI_DENSE_PAD_ELEMS;
+    };
     uint64_t scratch = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const MultiGraphPlan& gp = out.graphs[out.graph_of[i]];
@@ -206,6 +212,11 @@ int dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* gr
 int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                            uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide) {
     return dense_plan(graphs, n_graphs, graph_qoff, qoff, workspace_bytes, out, err, wide, true);
+}
+
+int build_multi_dense2_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                            uint64_t workspace_bytes, MultiPlan& out, std::string& err) {
+    return dense_plan(graphs, n_graphs, graph_qoff, qoff, workspace_bytes, out, err, true, false, true);
 }
 
 int multi_exact_slot(const MultiPlan& plan, const MultiExactCosts& costs, MultiExactSlot& out, std::string& err) {

@@ -44,6 +44,13 @@
 // build_multi_plan.  The exact variant cuts its own chunks and lays the carries out by them.  The tables a dense graph needs are rows and d_slot by row (row_base), pred_rows and pred_dslot by edge
 // (edge_base); the checkpoint fields of MultiGraphPlan stay empty.
 //
+// The dense two-piece variant (poa_multi_*_dense_2piece, poa_multi_dense2.hpp; build_multi_dense2_plan below) is the dense plan
+// over five full u16 planes: per query 5 x n_rows(graph) x pitch two-byte elements (M, I1, D1, I2, D2) + 256 bytes of padding,
+// region_off and Chunk::cells in two-byte elements relative to the query's chunk, the same greedy chunks.  Any query length and
+// no carries: the forward body loops over passes of 512 columns, and a row wider than the passes it keeps in registers reads its
+// predecessor back from the planes.  POA_CFG_WIDE_QUERIES is not read.  plane_bytes = sum of 2 x 5 x n_rows x pitch.  The
+// tables such a graph needs are rows (row_base) and pred_rows (edge_base).
+//
 // The exact variant (poa_multi_*_exact, poa_multi_exact.hpp; build_multi_exact_plan below) is the dense plan plus what the
 // replay of the reference's search needs (poa_wsearch.hpp):
 //   per query    a second region behind the chunk's dense regions: the u32 visited table of the search, 3 x n_rows(graph) x
@@ -161,7 +168,14 @@ inline uint64_t multi_dense_query_elems(const FlatGraph& g, uint64_t len) {
 int build_multi_dense_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
                            uint64_t workspace_bytes, MultiPlan& out, std::string& err, bool wide = false);
 
-constexpr uint64_t MULTI_EXACT_PAD_CELLS = 64;      // 256 bytes behind every query's visited table, in four-byte cells
+// two-byte elements a query of `len` symbols holds on that graph in a dense two-piece batch, padding NOT included: M, I1, D1, I2, D2
+inline uint64_t multi_dense2_query_elems(const FlatGraph& g, uint64_t len) { return 5ull * g.n * (((len + 1 + 63) / 64) * 64); }
+
+// The dense two-piece plan (see the head of this file): reads MultiGraphIn::g alone.  Same return values as build_multi_plan.
+int build_multi_dense2_plan(const MultiGraphIn* graphs, uint32_t n_graphs, const uint64_t* graph_qoff, const uint64_t* qoff,
+                            uint64_t workspace_bytes, MultiPlan& out, std::string& err);
+
+constexpr uint64_t MULTI_EXACT_PAD_CELLS = 64;     // 256 bytes behind every query's visited table, in four-byte cells
 // four-byte cells of the visited table of a query of `len` symbols on that graph, padding NOT included
 inline uint64_t multi_exact_table_cells(const FlatGraph& g, uint64_t len) { return 3ull * g.n * (((len + 1 + 63) / 64) * 64); }
 // THE rule for the width of the replay's descriptor ring (`win` priorities, a power of two from 64): prepare_exact,

@@ -205,14 +205,14 @@ __device__ __forceinline__ void tp_row_pass(const TpPassCosts& C, const RowMeta&
 // the bytes of a kernel that lives on its stores; arithmetic is u32 in registers either way (PlaneIO widens 0xFFFF to INF).
 // NP: passes whose previous row stays in registers (rows of up to NP * 64 * K columns): a chain row — one predecessor, the
 // previous row — then reads nothing back from the planes (6 of the 16 bytes of traffic per cell with u16 planes).
+// All rows of query qi, written against `const TwoPieceParams&`: the single-graph kernel below and poa2_forward_multi_kernel
+// (poa_multi_dense2.hpp, a wave per query on its own graph's parameter block) call this one body.
 template <typename T, int NP>
-__global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
+__device__ __forceinline__ void poa2_forward_query(const TwoPieceParams& P, const uint32_t qi, const uint32_t lane) {
     using IO = PlaneIO<T>;
     constexpr int K = IO::K;
     constexpr uint32_t PW = 64 * K;   // columns per pass
     constexpr uint32_t INF = 0xFFFFFFFFu;
-    const uint32_t slot = blockIdx.x, lane = threadIdx.x;
-    const uint32_t qi = P.first_query + slot;
     const uint64_t qbeg = P.qoff[qi];
     const uint32_t L = (uint32_t)(P.qoff[qi + 1] - qbeg);
     const uint8_t* q = P.qseq + qbeg;
@@ -273,6 +273,11 @@ __global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // the next rows read this one back (same wave)
     }
     if (lane == 0) P.score[qi] = IO::get(M + (uint64_t)P.end_row * pitch + L);
+}
+
+template <typename T, int NP>
+__global__ __launch_bounds__(64) void poa2_forward_kernel(TwoPieceParams P) {
+    poa2_forward_query<T, NP>(P, P.first_query + blockIdx.x, threadIdx.x);
 }
 
 // The walk of the two-piece traceback, shared by every kernel that takes it (poa2_traceback_kernel here on full planes,

@@ -33,6 +33,12 @@ of the one-shot poa_align_batch_ex in POA_MODE_DENSE; (s) the wide dense batch b
 chunks are one strip: against (w) per cell it shows what the strip loop itself costs.  With --exact also (e) poa_multi_run_exact +
 poa_multi_fetch in POA_MODE_HYBRID on the wide exact batch of --exact-reads reads per graph against (f) the per-graph hybrid loop on
 the same reads.  --dense is implied.  Writes profiles/pr_multi_wide/timing.json.
+
+--dense2: the two resident two-piece batches on the --two-piece workload, costs 4 / 6,24 / 2,1, in one process, pairs fetched:
+(a) poa_multi_run_2piece + poa_multi_fetch on the checkpointed batch of poa_multi_create_2piece; (d2) poa_multi_run_dense_2piece +
+poa_multi_fetch on the batch of poa_multi_create_dense_2piece.  Each step split into its two launches (pass 1 and pass 2; forward
+and walk) by the HIP-event sums of poa_stats_t, with both batches' plane bytes and workspaces and the results compared.  Writes
+profiles/pr_multi_dense2/timing.json.
 """
 import argparse
 import ctypes as C
@@ -57,9 +63,14 @@ def main():
     ap.add_argument("--dense", action="store_true", help="add the dense multi-graph batch (poa_multi_*_dense) to the one-piece paths")
     ap.add_argument("--exact", action="store_true", help="the exact multi-graph batch in hybrid mode against the per-graph hybrid loop, 1 and --reads reads per graph")
     ap.add_argument("--wide", action="store_true", help="reads of 1100 - 1300 bp on graphs of about 1300 rows: the wide dense batch (with --exact: and the wide exact batch)")
+    ap.add_argument("--dense2", action="store_true", help="the dense two-piece multi-graph batch (poa_multi_*_dense_2piece) against the checkpointed two-piece batch")
     ap.add_argument("--exact-reads", type=int, default=1, help="--wide --exact: reads per graph of the exact batch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.dense2:
+        if args.dense or args.exact or args.wide:
+            ap.error("--dense2 stands alone (it implies the --two-piece workload)")
+        return dense2_main(args)
     if args.wide:
         if args.two_piece:
             ap.error("--wide is one-piece")
@@ -191,6 +202,63 @@ def main():
         out["dense_run_stats"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in last_dense_stats.items()}
         md.close()
     mb.close()
+    print(json.dumps(out))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return 0 if out["results_equal"] else 1
+
+
+def dense2_main(args):
+    import numpy as np
+    from poasta_amd import aligner, workloads as W
+
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pr_multi_dense2", "timing.json")
+    graphs, seqs = [], []
+    for k in range(args.graphs):
+        g, (qseq, qoff) = W.scaled_linearish(190, 10, 5, args.reads, args.length, graph_seed=100 + k, query_seed=5000 + k)
+        graphs.append(g)
+        seqs.append([qseq[int(qoff[i]):int(qoff[i + 1])] for i in range(args.reads)])
+    costs = aligner.GapAffine2Piece(4, 2, 6, 1, 24)
+    batches = {"checkpoint2_run_fetch": aligner.MultiGraphBatch(graphs, seqs, two_piece=True),
+               "dense2_run_fetch": aligner.MultiGraphBatch(graphs, seqs, dense2=True)}
+    rows = {k: [] for k in batches}
+    sums, last = {}, {}
+    for rep in range(args.warmup + args.steps):
+        for name, mb in batches.items():
+            t0 = time.perf_counter()
+            mb.run(costs)
+            res = mb.fetch()
+            wall = (time.perf_counter() - t0) * 1e3
+            if rep >= args.warmup:
+                rows[name].append((wall, res.stats["ms_forward"], res.stats["ms_traceback"]))
+            last[name] = res.stats
+            sums[name] = {"score_sum": int(res.score.astype(np.uint64).sum()), "flags_crc32": zlib.crc32(res.flags.tobytes()),
+                          "n_pairs": int(res.pair_off[-1]), "pairs_crc32": zlib.crc32(np.ascontiguousarray(res.pairs).tobytes())}
+            del res
+
+    def med(v):
+        v = sorted(v)
+        return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+    out = {"workload": "%d graphs x %d reads of %d bp, LinearishPOA backbone 190" % (args.graphs, args.reads, args.length),
+           "costs": "4 / 6,24 / 2,1 (mismatch / open1,open2 / extend1,extend2)", "graphs": args.graphs, "queries": args.graphs * args.reads,
+           "rows_per_graph": {"min": min(g.n for g in graphs), "max": max(g.n for g in graphs)},
+           "cells": sum(g.n * (len(q) + 1) for g, qs in zip(graphs, seqs) for q in qs), "steps": args.steps, "warmup": args.warmup,
+           "results_equal": sums["dense2_run_fetch"] == sums["checkpoint2_run_fetch"]}
+    # ms_first_launch: pass 1 (the sweep with snapshots) / the forward launch; ms_second_launch: pass 2 (recompute and walk) / the
+    # walk launch, each with the scan and compaction of the pairs behind it
+    for name, mb in batches.items():
+        out[name] = {"ms_step": med([r[0] for r in rows[name]]), "ms_first_launch": med([r[1] for r in rows[name]]),
+                     "ms_second_launch": med([r[2] for r in rows[name]]), "plane_bytes": int(last[name]["plane_bytes"]),
+                     "workspace_bytes": mb.workspace_bytes(), "n_chunks": int(last[name]["n_chunks"])}
+        out[name].update(sums[name])
+        mb.close()
+    out["checkpoint2_footprint_bytes"] = aligner.multi_footprint(graphs, seqs, two_piece=True)[0]
+    out["dense2_footprint_bytes"] = aligner.multi_footprint(graphs, seqs, dense2=True)[0]
+    out["ms_step_ratio_dense2_over_checkpoint2"] = round(out["dense2_run_fetch"]["ms_step"]["median"] / out["checkpoint2_run_fetch"]["ms_step"]["median"], 4)
     print(json.dumps(out))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
